@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — collocation-point residual+grad evals/sec on the BASELINE.json workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path delivered in its last step as DIR/<name>.npy (float32 /
+float64, see dump_outputs): the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 One "step" = one evaluation of the PINN loss (all K term losses) AND its gradient w.r.t. all network
 weights for fixed theta and fixed collocation sets, delivered to the host (the reference's optimiser lives on
@@ -276,6 +279,9 @@ def bench_f64_sharded(args, eng, rep, sets, wl, npde, world, rank):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert torch.equal(first, h_out), "float64 sharded evaluation is not reproducible"
+    if args.dump_outputs and rank == 0:
+        res = h_out.numpy()
+        dump_outputs(args.dump_outputs, {"grad": res[:P], "loss_terms": res[P:] / np.array(n_glob, dtype=np.float64)})
     ms = dt / args.steps * 1e3
     path = eng.get_option("f64_path")
     eng.comm_destroy()
@@ -338,6 +344,8 @@ def bench_f64(args, eng, rep, sets, wl, npde=None, world=1, rank=0):
     dt = time.perf_counter() - t0
     out = d_out.cpu().numpy()
     assert np.array_equal(out[:P], g0) and np.allclose(out[P:] / np.array([s_.shape[1] for s_ in sets]), l0, rtol=1e-15, atol=0), "device-pointer and host entry disagree"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"grad": out[:P], "loss_terms": out[P:] / np.array([s_.shape[1] for s_ in sets], dtype=np.float64)})
     ms = dt / args.steps * 1e3
     ms_host = dt_host / args.steps * 1e3
     sizes = list(wl.chains[0].sizes)
@@ -370,6 +378,22 @@ def bench_f64(args, eng, rep, sets, wl, npde=None, world=1, rank=0):
                          "note": "executed f64 MFMA flops (forward + dA + dW hidden-layer GEMMs) / whole-evaluation wall time; kernel-level durations: profiles/r05_f64_kernel_stats.txt"},
             "loss_terms": [float(x) for x in l1]}
 
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float64 stays float64, everything else is written as float32).  The arrays are the
+    ones a caller of the timed path receives — the gradient and the per-term losses of the last timed step, or (--resident) theta and
+    the loss history after the last timed iteration — all of which are far below DUMP_LIMIT_BYTES for every BASELINE config."""
+    import numpy as np
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def emit(line):
@@ -414,6 +438,9 @@ def main():
     ap.add_argument("--event-every", type=int, default=0, help="record the HIP events on every M-th timed step (a start/stop pair plus "
                     "its read-back costs ~10 us of host+dispatch time per kernel; the sampled launches are inside the timed region). "
                     "0 (default): steps // 10, i.e. at least 10 sampled launches of every kernel")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (rank 0): grad + "
+                         "loss_terms, or with --resident theta + loss_history")
     args = ap.parse_args()
 
     # the host driver of this pool only supports dmabuf IPC: without this RCCL's peer-buffer exchange fails with hipIpcGetMemHandle errors
@@ -541,7 +568,7 @@ def main():
         eng.adam_init(theta0)
 
         def run_steps(n):
-            eng.adam(theta0, n, 1e-3, tw, init=False)          # pinn_adam_steps: n iterations, one host synchronisation at the end
+            return eng.adam(theta0, n, 1e-3, tw, init=False)   # pinn_adam_steps: n iterations, one host synchronisation at the end
 
     host_path_ms = None
     loss_only_ms = None
@@ -590,7 +617,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if args.resident:
-        run_steps(args.steps)
+        theta_last, hist_last = run_steps(args.steps)
     for i in range(0 if args.resident else args.steps):
         sampled = ev_level > 0 and i % every == 0
         if ev_level > 0 and every > 1:
@@ -608,6 +635,12 @@ def main():
         el = float(t.item())
 
     if rank == 0:
+        if args.dump_outputs:
+            if args.resident:
+                dump_outputs(args.dump_outputs, {"theta": theta_last, "loss_history": hist_last})
+            else:
+                res = out_h.numpy()
+                dump_outputs(args.dump_outputs, {"grad": res[:P], "loss_terms": res[P:] / np.array(n_glob)})
         if args.resident:                                     # the loss terms at the loop's final theta (outside the timed region)
             eng.set_timing(0, -1)
             step()

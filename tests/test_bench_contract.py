@@ -70,3 +70,27 @@ def test_bench_line_is_self_consistent():
     ref = np.asarray(g["losses_stencil"], dtype=float)
     got = np.asarray(d["loss_terms"], dtype=float)
     assert got.shape == ref.shape and np.max(np.abs(got - ref) / np.abs(ref)) < 1e-5
+
+
+def test_dump_outputs_writes_one_float_npy_per_array(tmp_path):
+    """`bench.py --dump-outputs DIR`: every array the timed path delivers is DIR/<name>.npy, float64 kept, anything else as float32,
+    and the whole dump is bounded (64 MB)."""
+    import sys
+    import numpy as np
+    import pytest
+    sys.path.insert(0, ROOT)
+    import bench
+    grad = np.linspace(-1.0, 1.0, 12737, dtype=np.float32)
+    losses = np.array([0.5, 0.25, 0.125], dtype=np.float64)
+    hist = np.arange(7, dtype=np.int64)
+    bench.dump_outputs(str(tmp_path / "out"), {"grad": grad, "loss_terms": losses, "loss_history": hist})
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["grad.npy", "loss_history.npy", "loss_terms.npy"]
+    g = np.load(tmp_path / "out" / "grad.npy")
+    assert g.dtype == np.float32 and np.array_equal(g, grad)
+    lt = np.load(tmp_path / "out" / "loss_terms.npy")
+    assert lt.dtype == np.float64 and np.array_equal(lt, losses)
+    lh = np.load(tmp_path / "out" / "loss_history.npy")
+    assert lh.dtype == np.float32 and np.array_equal(lh, hist.astype(np.float32))
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((64 << 20) // 8 + 1)})
+    assert not (tmp_path / "big").exists()
