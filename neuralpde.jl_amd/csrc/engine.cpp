@@ -6,6 +6,8 @@
 #include "engine_types.hpp"
 #include "aux_kernels.hpp"
 
+#include <type_traits>
+
 #ifdef PINN_EMU
 namespace wv {
 thread_local void (*emu_barrier_hook)(void*) = nullptr;
@@ -128,6 +130,35 @@ aux::ExprArgs expr_args(pinn_engine& E, Coupled& Cp, float scale, float* resid) 
     a.data = T.d_data;
     a.pw = (T.pw_n == T.n && T.pw_n > 0) ? T.d_pw : nullptr;
     return a;
+}
+
+// one caller array of n elements of type T, seen as element type V at the precision boundary of a float / double entry point: the caller's
+// own array when T is V; otherwise a converted copy — of the caller's values for an input (T const), or one that put() converts back into
+// the caller's array for an output.  A null array stays null.
+template <class V, class T> class As {
+    static constexpr bool same = std::is_same_v<V, std::remove_const_t<T>>;
+    T* x_;
+    std::vector<V> copy_;
+public:
+    As(T* x, size_t n) : x_(x) {
+        if constexpr (!same) {
+            if (x && std::is_const_v<T>) copy_.assign(x, x + n);      // an input: the caller's values, converted
+            else if (x) copy_.resize(n);                               // an output: written by the evaluation, converted back by put()
+        }
+    }
+    auto get() {
+        if constexpr (same) return x_;
+        else return x_ ? copy_.data() : nullptr;
+    }
+    int put() {                                          // (outputs; returns 0)
+        if constexpr (!same) if (x_) std::copy(copy_.begin(), copy_.end(), x_);
+        return 0;
+    }
+};
+template <class V, class T> As<V, T> as(T* x, size_t n) { return As<V, T>(x, n); }
+
+int check_theta(const pinn_engine& E, const char* who, int64_t p) {
+    return p == E.ntheta ? 0 : fail(std::string(who) + ": theta length " + std::to_string(p) + " != ntheta " + std::to_string(E.ntheta));
 }
 
 }  // namespace
@@ -552,10 +583,8 @@ int pinn_set_points_device(pinn_handle h, int term, const float* d_pts, int64_t 
 int pinn_set_points_f64(pinn_handle h, int term, const double* pts, int64_t n, int64_t n_norm) {
     if (!h || !pts || n <= 0) return fail("pinn_set_points_f64: null argument / empty point set");
     if (term < 0 || term >= (int)h->terms.size()) return fail("pinn_set_points_f64: term index out of range");
-    const int d = h->terms[term].d_user;
-    std::vector<float> p32((size_t)n * d);
-    for (size_t i = 0; i < p32.size(); ++i) p32[i] = (float)pts[i];
-    if (set_points_impl(h, term, p32.data(), n, n_norm, false)) return 1;       // the fp32 kernels' copy (EltypeAdaptor, src/eltype_matching.jl:8-10)
+    auto p32 = as<float>(pts, (size_t)n * h->terms[term].d_user);
+    if (set_points_impl(h, term, p32.get(), n, n_norm, false)) return 1;        // the fp32 kernels' copy (EltypeAdaptor, src/eltype_matching.jl:8-10)
     if (!h->f64) return 0;
     DeviceScope scope(h->device);
     return f64_set_points(*h, term, pts, n);                                    // the float64 mode reads the points as given
@@ -581,20 +610,10 @@ static int eval_and_sync(pinn_engine& E, float* d_out, const float* term_w, doub
     return 0;
 }
 
-int pinn_loss_grad(pinn_handle h, const float* theta, int64_t p, const float* term_w, double* term_losses, float* grad) {
-    if (!h || !theta) return fail("pinn_loss_grad: null argument");
-    pinn_engine& E = *h;
-    DeviceScope scope(E.device);
+// the fp32 body of pinn_loss_grad[_f64]: theta goes through the pinned staging block and the results land in it (no per-call host allocation)
+static int loss_grad_f32(pinn_engine& E, const float* theta, const float* term_w, double* term_losses, float* grad) {
     const int K = (int)E.terms.size();
-    if (E.f64) {                                         // float64 mode: converted at the boundary, evaluated in double
-        if (p != E.ntheta) return fail("theta length " + std::to_string(p) + " != ntheta " + std::to_string(E.ntheta));
-        std::vector<double> th(theta, theta + p), w(K, 1.0), g(grad ? p : 0);
-        if (term_w) for (int k = 0; k < K; ++k) w[k] = term_w[k];
-        if (f64_eval(E, th.data(), w.data(), term_losses, grad ? g.data() : nullptr)) return 1;
-        if (grad) for (int64_t i = 0; i < p; ++i) grad[i] = (float)g[i];
-        return 0;
-    }
-    if (upload_theta(E, theta, p)) return 1;
+    if (upload_theta(E, theta, E.ntheta)) return 1;
     // grad == NULL: loss-only evaluation (no records, no reverse sweep, no gradient reduction) — what a callback, an adaptive-weight
     // rule or a rejected line-search trial needs (the reference's per-term closures are value-only unless differentiated,
     // src/training_strategies.jl:215-221)
@@ -618,25 +637,6 @@ int pinn_loss_grad(pinn_handle h, const float* theta, int64_t p, const float* te
     return 0;
 }
 
-int pinn_loss_grad_f64(pinn_handle h, const double* theta, int64_t p, const double* term_w, double* term_losses, double* grad) {
-    if (!h || !theta) return fail("pinn_loss_grad_f64: null argument");
-    const int K = (int)h->terms.size();
-    if (h->f64) {                                        // float64 mode: native
-        if (p != h->ntheta) return fail("theta length " + std::to_string(p) + " != ntheta " + std::to_string(h->ntheta));
-        DeviceScope scope(h->device);
-        return f64_eval(*h, theta, term_w, term_losses, grad);
-    }
-    std::vector<float> th(p), w(K, 1.0f), g(grad ? p : 0);
-    for (int64_t i = 0; i < p; ++i) th[i] = (float)theta[i];
-    if (term_w)
-        for (int k = 0; k < K; ++k) w[k] = (float)term_w[k];
-    int rc = pinn_loss_grad(h, th.data(), p, w.data(), term_losses, grad ? g.data() : nullptr);
-    if (rc) return rc;
-    if (grad)
-        for (int64_t i = 0; i < p; ++i) grad[i] = (double)g[i];
-    return 0;
-}
-
 // l = sum_k logpdf(MvNormal(r_k, sigma_k^2 I), 0) = sum_k [ -N_k/2 log(2 pi) - N_k log sigma_k - SSE_k / (2 sigma_k^2) ]
 // (src/training_strategies.jl:113-127; "SSE not MSE", src/discretize.jl:681): an affine function of the per-term sums of squares,
 // so grad_theta l = - grad_theta sum_k w_k L_k with w_k = N_k / (2 sigma_k^2): ONE weighted evaluation.  sse[k]: raw sums of squares.
@@ -656,10 +656,7 @@ static void loglik_from_sse(const pinn_engine& E, const double* stds, const doub
 static int loglik_f64(pinn_engine& E, const double* theta, const double* stds, double* loglik, double* grad_theta, double* grad_std) {
     const int K = (int)E.terms.size();
     std::vector<double> w(K), L(K), g(grad_theta ? (size_t)E.ntheta : 0);
-    for (int k = 0; k < K; ++k) {
-        if (!(stds[k] > 0.0)) return fail("pinn_loglik_grad: standard deviations must be positive");
-        w[k] = (double)E.terms[k].n_norm / (2.0 * stds[k] * stds[k]);
-    }
+    for (int k = 0; k < K; ++k) w[k] = (double)E.terms[k].n_norm / (2.0 * stds[k] * stds[k]);
     if (f64_eval(E, theta, w.data(), L.data(), grad_theta ? g.data() : nullptr)) return 1;
     for (int k = 0; k < K; ++k) L[k] *= (double)E.terms[k].n_norm;           // mean -> SSE
     loglik_from_sse(E, stds, L.data(), loglik, grad_std);
@@ -667,44 +664,17 @@ static int loglik_f64(pinn_engine& E, const double* theta, const double* stds, d
     return 0;
 }
 
-int pinn_loglik_grad(pinn_handle h, const float* theta, int64_t p, const double* stds, double* loglik, float* grad_theta, double* grad_std) {
-    if (!h || !theta || !stds || !loglik) return fail("pinn_loglik_grad: null argument");
-    pinn_engine& E = *h;
-    DeviceScope scope(E.device);
+// ... and its fp32 counterpart
+static int loglik_f32(pinn_engine& E, const float* theta, const double* stds, double* loglik, float* grad_theta, double* grad_std) {
     const int K = (int)E.terms.size();
-    if (E.f64) {                                         // float64 mode: converted at the boundary, evaluated in double
-        if (p != E.ntheta) return fail("pinn_loglik_grad: theta length mismatch");
-        std::vector<double> th(theta, theta + p), g(grad_theta ? (size_t)p : 0);
-        if (loglik_f64(E, th.data(), stds, loglik, grad_theta ? g.data() : nullptr, grad_std)) return 1;
-        if (grad_theta) for (int64_t i = 0; i < p; ++i) grad_theta[i] = (float)g[(size_t)i];
-        return 0;
-    }
     std::vector<float> w(K);
-    for (int k = 0; k < K; ++k) {
-        if (!(stds[k] > 0.0)) return fail("pinn_loglik_grad: standard deviations must be positive");
-        w[k] = (float)((double)E.terms[k].n_norm / (2.0 * stds[k] * stds[k]));
-    }
-    if (upload_theta(E, theta, p)) return 1;
+    for (int k = 0; k < K; ++k) w[k] = (float)((double)E.terms[k].n_norm / (2.0 * stds[k] * stds[k]));
+    if (upload_theta(E, theta, E.ntheta)) return 1;
     if (run_loss_grad(E, E.d_theta, E.hp_out, w.data(), -1, false, E.hp_raw)) return 1;
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     loglik_from_sse(E, stds, E.hp_raw, loglik, grad_std);
     if (grad_theta)
         for (int64_t i = 0; i < E.ntheta; ++i) grad_theta[i] = -E.hp_out[i];
-    return 0;
-}
-
-int pinn_loglik_grad_f64(pinn_handle h, const double* theta, int64_t p, const double* stds, double* loglik, double* grad_theta, double* grad_std) {
-    if (!h || !theta || !stds || !loglik) return fail("pinn_loglik_grad_f64: null argument");
-    pinn_engine& E = *h;
-    if (p != E.ntheta) return fail("pinn_loglik_grad_f64: theta length mismatch");
-    if (E.f64) {
-        DeviceScope scope(E.device);
-        return loglik_f64(E, theta, stds, loglik, grad_theta, grad_std);
-    }
-    std::vector<float> th((size_t)p), g(grad_theta ? (size_t)p : 0);
-    for (int64_t i = 0; i < p; ++i) th[(size_t)i] = (float)theta[i];
-    if (pinn_loglik_grad(h, th.data(), p, stds, loglik, grad_theta ? g.data() : nullptr, grad_std)) return 1;
-    if (grad_theta) for (int64_t i = 0; i < p; ++i) grad_theta[i] = (double)g[(size_t)i];
     return 0;
 }
 
@@ -722,18 +692,10 @@ static int term_grads_f64(pinn_engine& E, const double* theta, double* term_loss
     return 0;
 }
 
-int pinn_term_grads(pinn_handle h, const float* theta, int64_t p, double* term_losses, float* term_grads) {
-    if (!h || !theta || !term_grads) return fail("pinn_term_grads: null argument");
-    pinn_engine& E = *h;
-    DeviceScope scope(E.device);
+// fp32: K evaluations of one term each; row k of term_grads (K x P floats)
+static int term_grads_f32(pinn_engine& E, const float* theta, double* term_losses, float* term_grads) {
     const int K = (int)E.terms.size();
-    if (E.f64) {                                         // float64 mode: converted at the boundary
-        if (p != E.ntheta) return fail("pinn_term_grads: theta length mismatch");
-        std::vector<double> th(theta, theta + p), g((size_t)K * p);
-        if (term_grads_f64(E, th.data(), term_losses, g.data())) return 1;
-        for (size_t i = 0; i < g.size(); ++i) term_grads[i] = (float)g[i];
-        return 0;
-    }
+    const int64_t p = E.ntheta;
     if (upload_theta(E, theta, p)) return 1;
     for (int k = 0; k < K; ++k) {
         if (run_loss_grad(E, E.d_theta, E.hp_out, nullptr, k, false, E.hp_raw)) return 1;
@@ -741,22 +703,6 @@ int pinn_term_grads(pinn_handle h, const float* theta, int64_t p, double* term_l
         std::memcpy(term_grads + (size_t)k * p, E.hp_out, sizeof(float) * p);
         if (term_losses) term_losses[k] = E.hp_raw[k] / (double)E.terms[k].n_norm;
     }
-    return 0;
-}
-
-int pinn_term_grads_f64(pinn_handle h, const double* theta, int64_t p, double* term_losses, double* term_grads) {
-    if (!h || !theta || !term_grads) return fail("pinn_term_grads_f64: null argument");
-    pinn_engine& E = *h;
-    if (p != E.ntheta) return fail("pinn_term_grads_f64: theta length mismatch");
-    const int K = (int)E.terms.size();
-    if (E.f64) {
-        DeviceScope scope(E.device);
-        return term_grads_f64(E, theta, term_losses, term_grads);
-    }
-    std::vector<float> th((size_t)p), g((size_t)K * p);
-    for (int64_t i = 0; i < p; ++i) th[(size_t)i] = (float)theta[i];
-    if (pinn_term_grads(h, th.data(), p, term_losses, g.data())) return 1;
-    for (size_t i = 0; i < g.size(); ++i) term_grads[i] = (double)g[i];
     return 0;
 }
 
@@ -807,21 +753,11 @@ int pinn_group_launched_by(pinn_handle h, int group) {
     return h->groups[group].launched_by;
 }
 
-int pinn_residual(pinn_handle h, int term, const float* theta, int64_t p, float* r) {
-    if (!h || !theta || !r) return fail("pinn_residual: null argument");
-    pinn_engine& E = *h;
-    DeviceScope scope(E.device);
-    if (term < 0 || term >= (int)E.terms.size()) return fail("pinn_residual: term index out of range");
+// fp32: residual_k(set_k, theta) at every point of the installed set (pinn_residual[_f64])
+static int residual_f32(pinn_engine& E, int term, const float* theta, float* r) {
     Term& T = E.terms[term];
     if (!T.d_pts) return fail("pinn_residual: term has no points");
-    if (E.f64) {                                         // float64 mode: converted at the boundary, evaluated in double
-        if (p != E.ntheta) return fail("pinn_residual: theta length mismatch");
-        std::vector<double> th(theta, theta + p), rd((size_t)T.n);
-        if (f64_residual(E, term, th.data(), rd.data())) return 1;
-        for (int64_t i = 0; i < T.n; ++i) r[i] = (float)rd[(size_t)i];
-        return 0;
-    }
-    if (upload_theta(E, theta, p)) return 1;
+    if (upload_theta(E, theta, E.ntheta)) return 1;
     pack_all(E);
     jit_take_launch_error();                             // (a stale message of an earlier call must not fail this one)
     if (T.resid_cap < T.n) {
@@ -865,30 +801,13 @@ int pinn_residual(pinn_handle h, int term, const float* theta, int64_t p, float*
     return 0;
 }
 
-int pinn_residual_f64(pinn_handle h, int term, const double* theta, int64_t p, double* r) {
-    if (!h || !theta || !r) return fail("pinn_residual_f64: null argument");
-    pinn_engine& E = *h;
-    if (term < 0 || term >= (int)E.terms.size()) return fail("pinn_residual_f64: term index out of range");
-    if (p != E.ntheta) return fail("pinn_residual_f64: theta length mismatch");
-    if (E.f64) {
-        DeviceScope scope(E.device);
-        return f64_residual(E, term, theta, r);
-    }
-    const int64_t n = E.terms[term].n;
-    std::vector<float> th((size_t)p), rf((size_t)std::max<int64_t>(n, 1));
-    for (int64_t i = 0; i < p; ++i) th[(size_t)i] = (float)theta[i];
-    if (pinn_residual(h, term, th.data(), p, rf.data())) return 1;
-    for (int64_t i = 0; i < n; ++i) r[i] = (double)rf[(size_t)i];
-    return 0;
-}
-
 // forward-only launch of one network on caller-supplied points with kernel `sp`: the jet channels land in E.d_phi_out as [C][n]
-static int forward_jets(pinn_engine& E, int net, const pk::SpecInfo* sp, const float* theta, int64_t p, const float* pts, int64_t n) {
+static int forward_jets(pinn_engine& E, int net, const pk::SpecInfo* sp, const float* theta, const float* pts, int64_t n) {
     const Net& N = E.nets[net];
     if (!E.netplans[net].spec) return fail("network is not used by any term");
     if (sp->family != E.netplans[net].spec->family || sp->PACKED != E.netplans[net].spec->PACKED)
         return fail("internal: forward kernel and the network's packed weight image disagree");
-    if (upload_theta(E, theta, p)) return 1;
+    if (upload_theta(E, theta, E.ntheta)) return 1;
     pack_all(E);
     jit_take_launch_error();                             // (clear: the check behind the launch below reports THIS launch)
     if (E.phi_cap < n || E.phi_chan < sp->C) {
@@ -900,26 +819,12 @@ static int forward_jets(pinn_engine& E, int net, const pk::SpecInfo* sp, const f
         E.d_phi_out = (float*)plat_malloc(sizeof(float) * E.phi_cap * E.phi_chan);
         if (!E.d_phi_pts || !E.d_phi_out) { E.phi_cap = 0; E.phi_chan = 0; return fail("device allocation failed (phi)"); }
     }
-    std::vector<float> feats;                                  // periodic embedding: [arguments] -> [features] on the host (this entry point takes host points)
-    if (!N.emb_idx.empty()) {
-        const int nin = N.n_inputs(), ne = (int)N.emb_idx.size(), F = N.sizes[0];
-        feats.resize((size_t)n * F);
-        for (int64_t q = 0; q < n; ++q) {
-            int pass = 0;
-            for (int a = 0; a < nin; ++a) {
-                const auto it = std::find(N.emb_idx.begin(), N.emb_idx.end(), a);
-                const double x = pts[q * nin + a];
-                if (it == N.emb_idx.end()) { feats[q * F + pass++] = (float)x; continue; }
-                const int k = (int)(it - N.emb_idx.begin());
-                const double ph = 6.283185307179586476925286766559 / N.emb_period[k] * x;
-                feats[q * F + nin - ne + k] = (float)std::sin(ph);
-                feats[q * F + nin + k] = (float)std::cos(ph);
-            }
-        }
-        plat_h2d(E.d_phi_pts, feats.data(), sizeof(float) * n * F, E.stream);
+    if (!N.emb_idx.empty()) {                                  // periodic embedding: [arguments] -> [features] on the host (this entry point takes host points)
+        const std::vector<float> feats = N.features(pts, n);
+        plat_h2d(E.d_phi_pts, feats.data(), sizeof(float) * feats.size(), E.stream);
         plat_sync(E.stream);                                   // (feats is a pageable temporary)
     } else
-    plat_h2d(E.d_phi_pts, pts, sizeof(float) * n * N.sizes[0], E.stream);
+        plat_h2d(E.d_phi_pts, pts, sizeof(float) * n * N.sizes[0], E.stream);
     pk::GroupArgs ga;
     std::memset(&ga, 0, sizeof ga);
     ga.packed = E.netplans[net].cur;
@@ -956,58 +861,15 @@ static int forward_jets(pinn_engine& E, int net, const pk::SpecInfo* sp, const f
     return 0;
 }
 
-int pinn_phi(pinn_handle h, int net, const float* theta, int64_t p, const float* pts, int64_t n, float* out) {
-    if (!h || !theta || !pts || !out) return fail("pinn_phi: null argument");
-    pinn_engine& E = *h;
-    DeviceScope scope(E.device);
+// fp32: d^order phi_net / dx_axes (order 0: the trial function itself) at n caller-supplied argument points [n][n_inputs]
+static int net_eval_f32(const char* who, pinn_engine& E, int net, const float* theta, const float* pts, int64_t n, int order, const int* axes, float* out) {
     GemmScope gs(E.gemm);
-    if (net < 0 || net >= (int)E.nets.size()) return fail("pinn_phi: net index out of range");
-    if (n <= 0) return fail("pinn_phi: n must be positive");
     const Net& N = E.nets[net];
-    if (E.f64) {                                         // float64 mode: converted at the boundary, evaluated in double
-        if (p != E.ntheta) return fail("pinn_phi: theta length mismatch");
-        const size_t np_ = (size_t)n * N.sizes[0];
-        std::vector<double> th(theta, theta + p), xd(pts, pts + np_), od((size_t)n);
-        if (f64_net_eval(E, net, th.data(), xd.data(), n, 0, nullptr, od.data())) return 1;
-        for (int64_t i = 0; i < n; ++i) out[i] = (float)od[(size_t)i];
-        return 0;
-    }
-    if (!E.netplans[net].spec) return fail("pinn_phi: network is not used by any term");
-    const int LH = (int)N.sizes.size() - 2;
-    (void)LH;
-    const pk::SpecInfo* sp = ensure_spec(N, 0, {}, 0u, E.netplans[net].spec->family);
-    if (!sp) return fail("pinn_phi: no value-only kernel for this network shape (" + g_err + ")");
-    if (forward_jets(E, net, sp, theta, p, pts, n)) return 1;
-    if (plat_d2h(out, E.d_phi_out, sizeof(float) * n, E.stream)) return fail("D2H copy failed");
-    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-    return 0;
-}
-
-int pinn_derivative(pinn_handle h, int net, const float* theta, int64_t p, const float* pts, int64_t n, int order, const int* axes, float* out) {
-    if (!h || !theta || !pts || !out) return fail("pinn_derivative: null argument");
-    pinn_engine& E = *h;
-    DeviceScope scope(E.device);
-    GemmScope gs(E.gemm);
-    if (net < 0 || net >= (int)E.nets.size()) return fail("pinn_derivative: net index out of range");
-    if (n <= 0) return fail("pinn_derivative: n must be positive");
-    if (order < 0 || order > MAX_DERIV_ORDER || (order > 0 && !axes)) return fail("pinn_derivative: order must be 0..6 (with `order` axes)");
-    const Net& N = E.nets[net];
-    if (E.f64) {                                         // float64 mode: converted at the boundary, evaluated in double
-        if (p != E.ntheta) return fail("pinn_derivative: theta length mismatch");
-        const size_t np_ = (size_t)n * N.sizes[0];
-        std::vector<double> th(theta, theta + p), xd(pts, pts + np_), od((size_t)n);
-        if (f64_net_eval(E, net, th.data(), xd.data(), n, order, axes, od.data())) return 1;
-        for (int64_t i = 0; i < n; ++i) out[i] = (float)od[(size_t)i];
-        return 0;
-    }
-    if (!E.netplans[net].spec) return fail("pinn_derivative: network is not used by any term");
-    if (!N.emb_idx.empty()) return fail("pinn_derivative: not available for a network behind a periodic input embedding (use pinn_residual on a term that carries the derivative)");
+    if (!E.netplans[net].spec) return fail(std::string(who) + ": network is not used by any term");
     Slot sl;
     sl.net = net; sl.order = order; sl.lap = 0;
     for (int a = 0; a < MAX_DERIV_ORDER; ++a) sl.axes[a] = a < order ? axes[a] : 0;
     std::sort(sl.axes, sl.axes + order);
-    for (int a = 0; a < order; ++a)
-        if (sl.axes[a] < 0 || sl.axes[a] >= N.sizes[0]) return fail("pinn_derivative: axis out of range");
     unsigned need_first = 0, need_hi = 0;
     std::vector<std::pair<int, int>> need_pairs;
     if (slot_is_general(sl)) need_hi = GEN_FLAG | (unsigned)gen_set_id({slot_mi(sl)});      // mixed of order >= 3, orders 5-6: generated jet set
@@ -1016,41 +878,13 @@ int pinn_derivative(pinn_handle h, int net, const float* theta, int64_t p, const
         if (order >= 2) need_pairs.push_back({sl.axes[0], sl.axes[1]});
         if (order >= 3) need_hi = (unsigned)order << (4 * sl.axes[0]);
     }
-    const int LH = (int)N.sizes.size() - 2;
-    (void)LH;
     const pk::SpecInfo* sp = ensure_spec(N, need_first, need_pairs, need_hi, E.netplans[net].spec->family);
-    if (!sp) return fail("pinn_derivative: no kernel carries this derivative for this network shape (" + g_err + ")");
+    if (!sp) return fail(std::string(who) + (order == 0 ? ": no value-only kernel" : ": no kernel carries this derivative") + " for this network shape (" + g_err + ")");
     const int ch = chan_of(*sp, sl);
     if (ch < 0) return fail("internal: derivative has no channel");
-    if (forward_jets(E, net, sp, theta, p, pts, n)) return 1;
+    if (forward_jets(E, net, sp, theta, pts, n)) return 1;
     if (plat_d2h(out, E.d_phi_out + (size_t)ch * n, sizeof(float) * n, E.stream)) return fail("D2H copy failed");
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-    return 0;
-}
-
-// phi(x, theta) and numeric_derivative in double (r06): the reference's closures compute in eltype(theta) = Float64 by default
-// (src/pinn_types.jl:88-90, 445-482; src/discretize.jl:432-449).  Native on a handle in float64 mode; on an fp32 handle they narrow at the boundary.
-int pinn_phi_f64(pinn_handle h, int net, const double* theta, int64_t p, const double* pts, int64_t n, double* out) {
-    return pinn_derivative_f64(h, net, theta, p, pts, n, 0, nullptr, out);
-}
-int pinn_derivative_f64(pinn_handle h, int net, const double* theta, int64_t p, const double* pts, int64_t n, int order, const int* axes, double* out) {
-    if (!h || !theta || !pts || !out) return fail("pinn_derivative_f64: null argument");
-    pinn_engine& E = *h;
-    if (net < 0 || net >= (int)E.nets.size()) return fail("pinn_derivative_f64: net index out of range");
-    if (n <= 0) return fail("pinn_derivative_f64: n must be positive");
-    if (p != E.ntheta) return fail("pinn_derivative_f64: theta length mismatch");
-    if (order < 0 || order > MAX_DERIV_ORDER || (order > 0 && !axes)) return fail("pinn_derivative_f64: order must be 0..6 (with `order` axes)");
-    if (E.f64) {
-        DeviceScope scope(E.device);
-        return f64_net_eval(E, net, theta, pts, n, order, axes, out);
-    }
-    const size_t np_ = (size_t)n * E.nets[net].n_inputs();
-    std::vector<float> th((size_t)p), xf(np_), of((size_t)n);
-    for (int64_t i = 0; i < p; ++i) th[(size_t)i] = (float)theta[i];
-    for (size_t i = 0; i < np_; ++i) xf[i] = (float)pts[i];
-    const int rc = order == 0 ? pinn_phi(h, net, th.data(), p, xf.data(), n, of.data()) : pinn_derivative(h, net, th.data(), p, xf.data(), n, order, axes, of.data());
-    if (rc) return rc;
-    for (int64_t i = 0; i < n; ++i) out[i] = (double)of[(size_t)i];
     return 0;
 }
 
@@ -1108,9 +942,8 @@ int pinn_set_point_data(pinn_handle h, int term, const float* data, int ndata, i
 }
 int pinn_set_point_data_f64(pinn_handle h, int term, const double* data, int ndata, int64_t n) {
     if (!h || !data || ndata <= 0 || n <= 0) return fail("pinn_set_point_data_f64: null argument / empty data");
-    std::vector<float> d32((size_t)ndata * (size_t)n);
-    for (size_t i = 0; i < d32.size(); ++i) d32[i] = (float)data[i];
-    if (pinn_set_point_data(h, term, d32.data(), ndata, n)) return 1;           // the fp32 kernels' rows (and every check)
+    auto d32 = as<float>(data, (size_t)ndata * (size_t)n);
+    if (pinn_set_point_data(h, term, d32.get(), ndata, n)) return 1;            // the fp32 kernels' rows (and every check)
     if (!h->f64) return 0;
     DeviceScope scope(h->device);
     return f64_set_point_data(*h, term, data);                                  // the float64 mode reads the observations as given
@@ -1282,15 +1115,9 @@ int pinn_get_option(pinn_handle h, const char* name, char* buf, int64_t buflen) 
     return fail("pinn_get_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, grad_health, gemm_delta, adam_path, eval_path, f64_path, f64_merged, f64_affine)");
 }
 
-int pinn_adam_init(pinn_handle h, const float* theta, int64_t p) {
-    if (!h || !theta) return fail("pinn_adam_init: null argument");
-    pinn_engine& E = *h;
-    DeviceScope scope(E.device);
-    if (p != E.ntheta) return fail("pinn_adam_init: theta length mismatch");
-    if (E.f64) {                                         // float64 mode: the optimiser state lives in double (f64.cpp)
-        std::vector<double> th(theta, theta + p);
-        return f64_adam_init(E, th.data());
-    }
+// fp32 optimiser state (float64 mode: f64.cpp keeps its own, in double)
+static int adam_init_f32(pinn_engine& E, const float* theta) {
+    const int64_t p = E.ntheta;
     const int K = (int)E.terms.size();
     if (!E.d_opt_theta) {
         E.d_opt_theta = (float*)plat_malloc(sizeof(float) * p);
@@ -1740,27 +1567,6 @@ static int adam_prepare(pinn_engine& E, int nsteps, const float* term_w, const c
     return plat_sync(E.stream) ? fail(std::string("device error: ") + plat_last_error()) : 0;      // (wn is a pageable temporary)
 }
 
-int pinn_adam_init_f64(pinn_handle h, const double* theta, int64_t p) {
-    if (!h || !theta) return fail("pinn_adam_init_f64: null argument");
-    pinn_engine& E = *h;
-    DeviceScope scope(E.device);
-    if (p != E.ntheta) return fail("pinn_adam_init_f64: theta length mismatch");
-    if (E.f64) return f64_adam_init(E, theta);
-    std::vector<float> th(theta, theta + p);             // fp32 mode: narrowed at the boundary
-    return pinn_adam_init(h, th.data(), p);
-}
-int pinn_adam_get_f64(pinn_handle h, double* theta, int64_t p) {
-    if (!h || !theta) return fail("pinn_adam_get_f64: null argument");
-    pinn_engine& E = *h;
-    DeviceScope scope(E.device);
-    if (p != E.ntheta) return fail("pinn_adam_get_f64: theta length mismatch");
-    if (E.f64) return f64_adam_get(E, theta);
-    std::vector<float> th((size_t)p);
-    if (pinn_adam_get(h, th.data(), p)) return 1;
-    for (int64_t i = 0; i < p; ++i) theta[i] = (double)th[(size_t)i];
-    return 0;
-}
-
 int pinn_adam_steps(pinn_handle h, int nsteps, float lr, float beta1, float beta2, float eps, const float* term_w, double* loss_history) {
     if (!h) return fail("null handle");
     pinn_engine& E = *h;
@@ -1998,19 +1804,9 @@ int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int histor
     return 0;
 }
 
-int pinn_adam_get(pinn_handle h, float* theta, int64_t p) {
-    if (!h || !theta) return fail("pinn_adam_get: null argument");
-    pinn_engine& E = *h;
-    DeviceScope scope(E.device);
-    if (E.f64) {
-        if (p != E.ntheta) return fail("pinn_adam_get: length mismatch");
-        std::vector<double> th((size_t)p);
-        if (f64_adam_get(E, th.data())) return 1;
-        for (int64_t i = 0; i < p; ++i) theta[i] = (float)th[(size_t)i];
-        return 0;
-    }
-    if (!E.d_opt_theta || p != E.ntheta) return fail("pinn_adam_get: no optimiser state / length mismatch");
-    if (plat_d2h(theta, E.d_opt_theta, sizeof(float) * p, E.stream)) return fail("D2H copy failed");
+static int adam_get_f32(pinn_engine& E, float* theta) {
+    if (!E.d_opt_theta) return fail("pinn_adam_get: no optimiser state (call pinn_adam_init first)");
+    if (plat_d2h(theta, E.d_opt_theta, sizeof(float) * E.ntheta, E.stream)) return fail("D2H copy failed");
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     return 0;
 }
@@ -2104,6 +1900,161 @@ int pinn_describe(pinn_handle h, char* buf, int64_t buflen) {
     std::snprintf(buf, (size_t)buflen, "%s", s.c_str());
     return 0;
 }
+
+}  // extern "C"
+
+// =================================================================================================
+// The float / double twins of the host entry points (pinn_X, pinn_X_f64).  One rule for all of them: T, the ABI's element type, is the
+// caller's; the evaluation runs in the HANDLE'S precision — the fp32 kernels (the *_f32 bodies above) or, in float64 mode, the double
+// kernels (f64.cpp).  One body per pair: the arguments are checked once (null pointers, index ranges, theta length) before the handle's
+// device is made current; where T is not the handle's type, the arrays are converted at this boundary (As), their lengths taken from
+// the engine.  The reference's closures compute in eltype(theta) (src/pinn_types.jl:88-90, 445-482; src/discretize.jl:432-449).
+// =================================================================================================
+namespace {
+
+template <class T> int loss_grad_twin(const char* who, pinn_handle h, const T* theta, int64_t p, const T* term_w, double* term_losses, T* grad) {
+    if (!h || !theta) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (check_theta(E, who, p)) return 1;
+    DeviceScope scope(E.device);
+    const size_t P = (size_t)p, K = E.terms.size();
+    if (E.f64) {
+        auto th = as<double>(theta, P); auto w = as<double>(term_w, K); auto g = as<double>(grad, P);
+        return f64_eval(E, th.get(), w.get(), term_losses, g.get()) ? 1 : g.put();
+    }
+    auto th = as<float>(theta, P); auto w = as<float>(term_w, K); auto g = as<float>(grad, P);
+    return loss_grad_f32(E, th.get(), w.get(), term_losses, g.get()) ? 1 : g.put();
+}
+
+template <class T> int loglik_twin(const char* who, pinn_handle h, const T* theta, int64_t p, const double* stds, double* loglik, T* grad_theta, double* grad_std) {
+    if (!h || !theta || !stds || !loglik) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (check_theta(E, who, p)) return 1;
+    for (size_t k = 0; k < E.terms.size(); ++k)
+        if (!(stds[k] > 0.0)) return fail(std::string(who) + ": standard deviations must be positive");
+    DeviceScope scope(E.device);
+    if (E.f64) {
+        auto th = as<double>(theta, (size_t)p); auto g = as<double>(grad_theta, (size_t)p);
+        return loglik_f64(E, th.get(), stds, loglik, g.get(), grad_std) ? 1 : g.put();
+    }
+    auto th = as<float>(theta, (size_t)p); auto g = as<float>(grad_theta, (size_t)p);
+    return loglik_f32(E, th.get(), stds, loglik, g.get(), grad_std) ? 1 : g.put();
+}
+
+template <class T> int term_grads_twin(const char* who, pinn_handle h, const T* theta, int64_t p, double* term_losses, T* term_grads) {
+    if (!h || !theta || !term_grads) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (check_theta(E, who, p)) return 1;
+    DeviceScope scope(E.device);
+    const size_t P = (size_t)p, KP = E.terms.size() * P;
+    if (E.f64) {
+        auto th = as<double>(theta, P); auto g = as<double>(term_grads, KP);
+        return term_grads_f64(E, th.get(), term_losses, g.get()) ? 1 : g.put();
+    }
+    auto th = as<float>(theta, P); auto g = as<float>(term_grads, KP);
+    return term_grads_f32(E, th.get(), term_losses, g.get()) ? 1 : g.put();
+}
+
+template <class T> int residual_twin(const char* who, pinn_handle h, int term, const T* theta, int64_t p, T* r) {
+    if (!h || !theta || !r) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (term < 0 || term >= (int)E.terms.size()) return fail(std::string(who) + ": term index out of range");
+    if (check_theta(E, who, p)) return 1;
+    DeviceScope scope(E.device);
+    const size_t P = (size_t)p, n = (size_t)E.terms[term].n;
+    if (E.f64) {
+        auto th = as<double>(theta, P); auto o = as<double>(r, n);
+        return f64_residual(E, term, th.get(), o.get()) ? 1 : o.put();
+    }
+    auto th = as<float>(theta, P); auto o = as<float>(r, n);
+    return residual_f32(E, term, th.get(), o.get()) ? 1 : o.put();
+}
+
+// phi (order 0) and its derivatives at n points of the dependent variable's arguments, pts [n][n_inputs]
+template <class T> int net_eval_twin(const char* who, pinn_handle h, int net, const T* theta, int64_t p, const T* pts, int64_t n, int order, const int* axes, T* out) {
+    if (!h || !theta || !pts || !out) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (net < 0 || net >= (int)E.nets.size()) return fail(std::string(who) + ": net index out of range");
+    if (n <= 0) return fail(std::string(who) + ": n must be positive");
+    if (order < 0 || order > MAX_DERIV_ORDER || (order > 0 && !axes)) return fail(std::string(who) + ": order must be 0..6 (with `order` axes)");
+    const Net& N = E.nets[net];
+    if (order > 0 && !N.emb_idx.empty())
+        return fail(std::string(who) + ": not available for a network behind a periodic input embedding (use pinn_residual on a term that carries the derivative)");
+    for (int a = 0; a < order; ++a)
+        if (axes[a] < 0 || axes[a] >= N.n_inputs()) return fail(std::string(who) + ": axis out of range");
+    if (check_theta(E, who, p)) return 1;
+    DeviceScope scope(E.device);
+    const size_t P = (size_t)p, X = (size_t)n * N.n_inputs();
+    if (E.f64) {
+        auto th = as<double>(theta, P); auto x = as<double>(pts, X); auto o = as<double>(out, (size_t)n);
+        return f64_net_eval(E, net, th.get(), x.get(), n, order, axes, o.get()) ? 1 : o.put();
+    }
+    auto th = as<float>(theta, P); auto x = as<float>(pts, X); auto o = as<float>(out, (size_t)n);
+    return net_eval_f32(who, E, net, th.get(), x.get(), n, order, axes, o.get()) ? 1 : o.put();
+}
+
+template <class T> int adam_init_twin(const char* who, pinn_handle h, const T* theta, int64_t p) {
+    if (!h || !theta) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (check_theta(E, who, p)) return 1;
+    DeviceScope scope(E.device);
+    if (E.f64) return f64_adam_init(E, as<double>(theta, (size_t)p).get());
+    return adam_init_f32(E, as<float>(theta, (size_t)p).get());
+}
+
+template <class T> int adam_get_twin(const char* who, pinn_handle h, T* theta, int64_t p) {
+    if (!h || !theta) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (check_theta(E, who, p)) return 1;
+    DeviceScope scope(E.device);
+    if (E.f64) {
+        auto th = as<double>(theta, (size_t)p);
+        return f64_adam_get(E, th.get()) ? 1 : th.put();
+    }
+    auto th = as<float>(theta, (size_t)p);
+    return adam_get_f32(E, th.get()) ? 1 : th.put();
+}
+
+}  // namespace
+
+extern "C" {
+
+int pinn_loss_grad(pinn_handle h, const float* theta, int64_t p, const float* term_w, double* term_losses, float* grad) {
+    return loss_grad_twin(__func__, h, theta, p, term_w, term_losses, grad);
+}
+int pinn_loss_grad_f64(pinn_handle h, const double* theta, int64_t p, const double* term_w, double* term_losses, double* grad) {
+    return loss_grad_twin(__func__, h, theta, p, term_w, term_losses, grad);
+}
+int pinn_loglik_grad(pinn_handle h, const float* theta, int64_t p, const double* stds, double* loglik, float* grad_theta, double* grad_std) {
+    return loglik_twin(__func__, h, theta, p, stds, loglik, grad_theta, grad_std);
+}
+int pinn_loglik_grad_f64(pinn_handle h, const double* theta, int64_t p, const double* stds, double* loglik, double* grad_theta, double* grad_std) {
+    return loglik_twin(__func__, h, theta, p, stds, loglik, grad_theta, grad_std);
+}
+int pinn_term_grads(pinn_handle h, const float* theta, int64_t p, double* term_losses, float* term_grads) {
+    return term_grads_twin(__func__, h, theta, p, term_losses, term_grads);
+}
+int pinn_term_grads_f64(pinn_handle h, const double* theta, int64_t p, double* term_losses, double* term_grads) {
+    return term_grads_twin(__func__, h, theta, p, term_losses, term_grads);
+}
+int pinn_residual(pinn_handle h, int term, const float* theta, int64_t p, float* r) { return residual_twin(__func__, h, term, theta, p, r); }
+int pinn_residual_f64(pinn_handle h, int term, const double* theta, int64_t p, double* r) { return residual_twin(__func__, h, term, theta, p, r); }
+int pinn_phi(pinn_handle h, int net, const float* theta, int64_t p, const float* pts, int64_t n, float* out) {
+    return net_eval_twin(__func__, h, net, theta, p, pts, n, 0, nullptr, out);
+}
+int pinn_phi_f64(pinn_handle h, int net, const double* theta, int64_t p, const double* pts, int64_t n, double* out) {
+    return net_eval_twin(__func__, h, net, theta, p, pts, n, 0, nullptr, out);
+}
+int pinn_derivative(pinn_handle h, int net, const float* theta, int64_t p, const float* pts, int64_t n, int order, const int* axes, float* out) {
+    return net_eval_twin(__func__, h, net, theta, p, pts, n, order, axes, out);
+}
+int pinn_derivative_f64(pinn_handle h, int net, const double* theta, int64_t p, const double* pts, int64_t n, int order, const int* axes, double* out) {
+    return net_eval_twin(__func__, h, net, theta, p, pts, n, order, axes, out);
+}
+int pinn_adam_init(pinn_handle h, const float* theta, int64_t p) { return adam_init_twin(__func__, h, theta, p); }
+int pinn_adam_init_f64(pinn_handle h, const double* theta, int64_t p) { return adam_init_twin(__func__, h, theta, p); }
+int pinn_adam_get(pinn_handle h, float* theta, int64_t p) { return adam_get_twin(__func__, h, theta, p); }
+int pinn_adam_get_f64(pinn_handle h, double* theta, int64_t p) { return adam_get_twin(__func__, h, theta, p); }
 
 }  // extern "C"
 

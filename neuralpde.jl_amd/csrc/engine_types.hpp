@@ -44,6 +44,25 @@ struct Net {
     std::vector<int> emb_idx;
     std::vector<double> emb_period;
     int n_inputs() const { return sizes[0] - (int)emb_idx.size(); }       // arguments of the dependent variable
+    // the features [n][sizes[0]] the first Dense layer takes at n points of the arguments x [n][n_inputs()]: pass-through arguments, then sin,
+    // then cos of the embedded ones — phases and sin / cos in double, narrowed to T only at the store
+    template <class T> std::vector<T> features(const T* x, int64_t n) const {
+        const int nin = n_inputs(), ne = (int)emb_idx.size(), F = sizes[0];
+        std::vector<T> f((size_t)n * F);
+        for (int64_t q = 0; q < n; ++q) {
+            int pass = 0;
+            for (int a = 0; a < nin; ++a) {
+                const double xa = x[(size_t)q * nin + a];
+                const auto it = std::find(emb_idx.begin(), emb_idx.end(), a);
+                if (it == emb_idx.end()) { f[(size_t)q * F + pass++] = (T)xa; continue; }
+                const int k = (int)(it - emb_idx.begin());
+                const double ph = 6.283185307179586476925286766559 / emb_period[k] * xa;
+                f[(size_t)q * F + nin - ne + k] = (T)std::sin(ph);
+                f[(size_t)q * F + nin + k] = (T)std::cos(ph);
+            }
+        }
+        return f;
+    }
     int nparams() const {
         if (kind == 1) { const int d = sizes[0], M = sizes[1]; return M * d + M + dgm_layers * (4 * M * d + 4 * M * M + 4 * M) + M + 1; }
         int n = 0;

@@ -1067,8 +1067,8 @@ int f64_residual(pinn_engine& E, int term, const double* theta, double* r) {
     if (plat_d2h(r, S.d_aux_out, sizeof(double) * (size_t)F.n, E.stream) || plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     return 0;
 }
-// d^order phi_net / dx_axes (order 0: the trial function itself) at n caller-supplied points (pinn_phi_f64, pinn_derivative_f64 and their float
-// counterparts in float64 mode): a pseudo-term of one slot and an empty tape on the jet set that carries the derivative
+// d^order phi_net / dx_axes (order 0: the trial function itself) at n caller-supplied points (pinn_phi[_f64], pinn_derivative[_f64] in float64 mode;
+// engine.cpp has checked order, axes and the embedding): a pseudo-term of one slot and an empty tape on the jet set that carries the derivative
 int f64_net_eval(pinn_engine& E, int net, const double* theta, const double* pts, int64_t n, int order, const int* axes, double* out) {
     F64State& S = *(F64State*)E.f64;
     const Net& N = E.nets[net];
@@ -1077,33 +1077,17 @@ int f64_net_eval(pinn_engine& E, int net, const double* theta, const double* pts
     if (N.act != pk::ACT_TANH && N.act != pk::ACT_SIGMOID && N.act != pk::ACT_SIN && N.act != pk::ACT_MIXED) return fail(who + "this activation is not covered by the float64 mode");
     if ((int)N.sizes.size() - 1 > pk::F64_MAX_LAYERS || N.sizes[0] > 4) return fail(who + "more than 16 Dense layers / more than 4 inputs");
     const int d = N.sizes[0];
-    // a network behind a periodic input embedding (r06): the caller's points are the dependent variable's ARGUMENTS [n][n_inputs]; the Dense chain takes
-    // the features (pass-through arguments, then sin, then cos of the embedded ones — engine_types.hpp: Net::emb_idx), formed here in double
+    // a network behind a periodic input embedding (r06; value only): the caller's points are the dependent variable's ARGUMENTS [n][n_inputs]; the
+    // Dense chain takes the features, formed here in double
     std::vector<double> feats;
     if (!N.emb_idx.empty()) {
-        if (order > 0) return fail("pinn_derivative: not available for a network behind a periodic input embedding (use pinn_residual on a term that carries the derivative)");
-        const int nin = N.n_inputs(), ne = (int)N.emb_idx.size();
-        feats.resize((size_t)n * d);
-        for (int64_t q = 0; q < n; ++q) {
-            int pass = 0;
-            for (int a = 0; a < nin; ++a) {
-                const double x = pts[(size_t)q * nin + a];
-                const auto it = std::find(N.emb_idx.begin(), N.emb_idx.end(), a);
-                if (it == N.emb_idx.end()) { feats[(size_t)q * d + pass++] = x; continue; }
-                const int k = (int)(it - N.emb_idx.begin());
-                const double ph = 6.283185307179586476925286766559 / N.emb_period[k] * x;
-                feats[(size_t)q * d + nin - ne + k] = std::sin(ph);
-                feats[(size_t)q * d + nin + k] = std::cos(ph);
-            }
-        }
+        feats = N.features(pts, n);
         pts = feats.data();
     }
     Slot sl;
     sl.net = net; sl.order = order; sl.lap = 0;
     for (int q = 0; q < MAX_DERIV_ORDER; ++q) sl.axes[q] = q < order ? axes[q] : 0;
     std::sort(sl.axes, sl.axes + order);
-    for (int q = 0; q < order; ++q)
-        if (sl.axes[q] < 0 || sl.axes[q] >= d) return fail("pinn_derivative: axis out of range");
     F64Term F;
     std::string why;
     F.k = f64_find(d, std::vector<Slot>{sl}, F.slot_chan, why);

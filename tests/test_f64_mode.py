@@ -510,6 +510,52 @@ def test_f64_per_point_and_per_term_entry_points(npde, use_emu, name):
     assert abs(ll32 - ll) < 1e-6 * abs(ll) and np.linalg.norm(g32 - g) < 1e-5 * np.linalg.norm(g)      # (theta itself is narrowed to float at that boundary)
 
 
+@pytest.mark.parametrize("name", ["cfg2", "cfg4"])
+def test_float_and_double_twins_follow_one_precision_rule(npde, use_emu, name):
+    """every float / double pair of host entry points evaluates in the HANDLE'S precision and converts at the ABI boundary: on a handle in
+    float64 mode the float entry point returns the narrowed double result, on an fp32 handle the double entry point returns the widened
+    float result — bit for bit, since every double input below is a float and both kernel paths are deterministic"""
+    from neuralpde_jl_amd import workloads
+    wl = {"cfg2": lambda: workloads.cfg2_poisson2d(points=40, bcs_points=12, width=16, hidden=2),
+          "cfg4": lambda: workloads.cfg4_cavity(points=40, bcs_points=12, width=16, hidden=2)}[name]()
+    rep64, e64, sets, _ = _engine_f64(npde, wl)
+    e32 = npde.symbolic_discretize(wl.pde_system, wl.discretization()).engine
+    e32.set_option("precision", "f32")
+    for k, s in enumerate(sets):
+        e32.set_points_f64(k, s)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    th = f32(rep64.flat_init_params).astype(np.float64)
+    w = f32(np.linspace(1.0, 2.0, e64.K)).astype(np.float64)
+    stds = f32(np.linspace(0.05, 0.2, e64.K)).astype(np.float64)
+    pts = f32(np.random.default_rng(3).uniform(0, 1, size=(2, 37))).astype(np.float64)
+    for eng in (e64, e32):
+        # narrow: the float entry point's output as the narrowing of the double one (f64 handle), or the double one's as the widening (fp32)
+        if eng is e64:
+            same = lambda lo, hi: np.array_equal(lo, f32(hi)) and lo.dtype == np.float32
+        else:
+            same = lambda lo, hi: np.array_equal(hi, np.asarray(lo, dtype=np.float64)) and lo.dtype == np.float32
+        for want_grad in (True, False):
+            lf, gf = eng.loss_grad(f32(th), f32(w), want_grad=want_grad)
+            ld, gd = eng.loss_grad_f64(th, w, want_grad=want_grad)
+            assert np.array_equal(lf, ld) and (gf is None and gd is None or same(gf, gd)), (eng is e64, want_grad)
+        llf, gf, gsf = eng.loglik_grad(f32(th), stds)
+        lld, gd, gsd = eng.loglik_grad_f64(th, stds)
+        assert llf == lld and np.array_equal(gsf, gsd) and same(gf, gd)
+        Lf, tgf = eng.term_grads(f32(th))
+        Ld, tgd = eng.term_grads_f64(th)
+        assert np.array_equal(Lf, Ld) and same(tgf, tgd)
+        for k in range(eng.K):
+            assert same(eng.residual(k, f32(th), sets[k].shape[1]), eng.residual_f64(k, th, sets[k].shape[1])), k
+        for net in range(len(wl.chains)):
+            assert same(eng.phi(net, f32(th), f32(pts)), eng.phi_f64(net, th, pts)), net
+            for axes in ([0], [0, 1]):
+                assert same(eng.derivative(net, f32(th), f32(pts), axes), eng.derivative_f64(net, th, pts, axes)), (net, axes)
+        tf, hf = eng.adam(f32(th), 2, 1e-3)
+        td, hd = eng.adam_f64(th, 2, 1e-3)
+        assert np.array_equal(hf, hd) and same(tf, td)
+        assert same(eng.adam_get(), eng.adam_get_f64())
+
+
 def test_f64_adam_iterate_survives_evaluations_between_chunks(npde, use_emu):
     """in float64 mode the Adam iterate lived in the evaluation buffer — any evaluation between two pinn_adam_steps calls
     (adaptive reweighting, a callback that evaluates the loss) destroyed it.  The iterate has its own buffer now: a chunked run with
@@ -840,6 +886,12 @@ def test_f64_periodic_embedding(npde, use_emu):
     np.testing.assert_allclose(eng.phi_f64(0, th, pts), eng.phi_f64(0, th, pts + np.array([[0.0], [2 * np.pi]])), rtol=0, atol=1e-13)
     with pytest.raises(Exception, match="periodic input embedding"):
         eng.derivative_f64(0, th, pts, [1])
+    # the float trial function of the same handle reads the caller's ARGUMENTS (2 per point, not the 3 features): enough points that the
+    # argument buffer is a heap block of its own
+    many = np.random.default_rng(8).uniform([[0.0], [0.0]], [[1.0], [2 * np.pi]], size=(2, 1200))
+    got = eng.phi(0, th, many)
+    ex = po.phi_values(prob.chains[0], th, many).reshape(-1)
+    assert got.dtype == np.float32 and np.max(np.abs(got - ex)) < 1e-6 * max(1.0, np.max(np.abs(ex)))
     # the float entry point of the same handle: converted at the boundary
     l32, g32 = eng.loss_grad(th.astype(np.float32), np.asarray(w, dtype=np.float32))
     assert np.linalg.norm(g32 - ref.grad) / np.linalg.norm(ref.grad) < 1e-5
