@@ -333,6 +333,7 @@ int f64_enable(pinn_engine& E);
 void f64_destroy(pinn_engine& E);
 std::string f64_describe(const pinn_engine& E);
 int f64_affine_terms(const pinn_engine& E);      // terms whose residual the matrix-pipe tile kernel evaluates in affine form, without the tape interpreter
+int f64_chunks(const pinn_engine& E);            // the most launches (scratch-sized chunks) one point set took in the last float64 call: 1 = none chunked
 int f64_merged(const pinn_engine& E);            // merged launch sequences of the last float64 evaluation (small problems: f64.cpp f64_make_groups)
 const char* f64_path(const pinn_engine& E);      // kernels of the last float64 evaluation: "mfma" | "lanes" | "mfma+lanes" | "none" | "off"
 int f64_points_changed(pinn_engine& E, int term);

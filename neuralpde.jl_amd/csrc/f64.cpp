@@ -90,6 +90,7 @@ struct F64State {
     std::vector<Group> groups;
     std::vector<int64_t> groups_sig;     // the point counts the grouping was made for (empty: not made yet)
     int merged_launches = 0;             // of the last evaluation (pinn_get_option "f64_merged")
+    int max_chunks = 0;                  // the most launches one point set took in the last float64 call (pinn_get_option "f64_chunks"; f64_buffers)
 };
 
 static void f64_free(F64State* S) {
@@ -749,6 +750,7 @@ static int f64_stencil_term(pinn_engine& E, int t, const double* theta, double* 
         a.seed = S.d_seeds + (size_t)v * n * stride; a.seed_stride = stride;
         int64_t chunk = 0;
         if (f64_buffers(E, S, L, n, true, chunk)) { F.d_pts = nullptr; return 1; }
+        S.max_chunks = std::max(S.max_chunks, (int)((n + chunk - 1) / chunk));
         for (int64_t p0 = 0; p0 < n; p0 += chunk) {
             a.p0 = (int)p0;
             a.npts = (int)std::min<int64_t>(chunk, n - p0);
@@ -899,6 +901,7 @@ static int f64_eval_device(pinn_engine& E, const double* theta, double* grad, do
     };
     S.path = 0;
     S.merged_launches = 0;
+    S.max_chunks = 0;
     std::vector<char> done(K, 0);
     if (!S.stencil) {
         f64_make_groups(E, S);
@@ -944,6 +947,7 @@ static int f64_eval_device(pinn_engine& E, const double* theta, double* grad, do
             if (chunk < a.npts) continue;                // (does not fit one launch: the members go one by one below)
             S.path |= 2;
             ++S.merged_launches;
+            S.max_chunks = std::max(S.max_chunks, 1);
             const int nblocks = f64_short_blocks(E, S, L);
             f64_launch_tile(G.km, a, E.stream);
             G.km->launch_dwt(a, E.stream);
@@ -982,6 +986,7 @@ static int f64_eval_device(pinn_engine& E, const double* theta, double* grad, do
         S.path |= L.mfma ? 2 : 1;
         int64_t chunk = 0;
         if (f64_buffers(E, S, L, F.n, true, chunk)) return 1;
+        S.max_chunks = std::max(S.max_chunks, (int)((F.n + chunk - 1) / chunk));
         for (int64_t p0 = 0; p0 < F.n; p0 += chunk) {
             a.p0 = (int)p0;
             a.npts = (int)std::min<int64_t>(chunk, F.n - p0);
@@ -1036,6 +1041,7 @@ static int f64_values(pinn_engine& E, F64State& S, const F64Term& F, F64Launch& 
     S.path |= L.mfma ? 2 : 1;
     int64_t chunk = 0;
     if (f64_buffers(E, S, L, n, false, chunk)) return 1;
+    S.max_chunks = std::max(S.max_chunks, (int)((n + chunk - 1) / chunk));
     for (int64_t p0 = 0; p0 < n; p0 += chunk) {
         a.p0 = (int)p0;
         a.npts = (int)std::min<int64_t>(chunk, n - p0);
@@ -1055,6 +1061,7 @@ int f64_residual(pinn_engine& E, int term, const double* theta, double* r) {
     if (!grow(S.d_aux_out, cap, (size_t)F.n, E.stream)) { S.aux_out_cap = 0; return fail("device allocation failed (float64 residuals)"); }
     S.aux_out_cap = (int64_t)cap;
     S.path = 0;
+    S.max_chunks = 0;
     if (S.stencil && S.sten[term].active) {
         S.path = 1;
         if (f64_stencil_term(E, term, S.d_theta, nullptr, nullptr, 1.0, 2, S.d_aux_out)) return 1;
@@ -1110,6 +1117,7 @@ int f64_net_eval(pinn_engine& E, int net, const double* theta, const double* pts
     int rc = f64_build(E, F, d, nullptr, L);
     L.a.theta = S.d_theta;
     S.path = 0;
+    S.max_chunks = 0;
     if (!rc) rc = f64_values(E, S, F, L, n, S.d_aux_out);
     if (!rc && (plat_d2h(out, S.d_aux_out, sizeof(double) * (size_t)n, E.stream) || plat_sync(E.stream))) rc = fail(std::string("device error: ") + plat_last_error());
     F.d_pts = nullptr;                                   // (borrowed: the pseudo-term owns nothing)
@@ -1300,6 +1308,7 @@ std::string f64_describe(const pinn_engine& E) {
 }
 
 int f64_merged(const pinn_engine& E) { return E.f64 ? ((const F64State*)E.f64)->merged_launches : 0; }
+int f64_chunks(const pinn_engine& E) { return E.f64 ? ((const F64State*)E.f64)->max_chunks : 0; }
 int f64_affine_terms(const pinn_engine& E) {
     if (!E.f64) return 0;
     int n = 0;
