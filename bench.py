@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — collocation-point residual+grad evals/sec on the BASELINE.json workload.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
+
+A plain run does what the headline figure needs and nothing else: set-up, a short device settling, the W warm-up steps, the K timed steps
+(with the HIP events sampled inside them, which the `roofline` objects are computed from), the dump, the JSON line.  --full adds the legs
+that take runs of their own, before the warm-up or after the timed region, and their fields of the line: the cross-check of the zero-copy
+host delivery against a device-buffer evaluation, the C-ABI host entry point (`value_incl_theta_h2d`, `host_entry_ms_per_step`), the
+loss-only evaluation and its check against the fused one (`loss_only_host_entry_ms`), and the CPU baseline (`cpu_baseline`, about a
+minute; --no-cpu-baseline leaves it out of a --full run).  Without --full those fields are null / absent.  The timed steps are the same.
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what the timed path delivered in its last step as DIR/<name>.npy (float32 /
 float64, see dump_outputs): the inputs are seeded, so two builds run with the same arguments can be compared output for output.
@@ -27,8 +34,8 @@ matrix pipe that EXECUTES its hidden-layer products: in the default "split" GEMM
 bf16 MFMA peak, `frac` <= 1 by construction; the fp32-equivalent rate against the fp32 MFMA peak — what BASELINE.json's north star
 names — is kept as `frac_fp32_equiv`), "roofline_kernels" (the same for every fused kernel of the step) and "cpu_baseline" (the float64
 oracle = CPU restatement of the reference algorithm, timed on this box's host cores on the same full-size workload at 32 / 64 / 96 / 128 threads,
-the faster one reported; rank 0, N=1 only).  `value` keeps theta resident in HBM; `value_incl_theta_h2d` is SURVEY.md section 8d's
-definition (theta crosses PCIe every step: the C-ABI host entry point).
+the fastest one reported; rank 0, N=1, --full only).  `value` keeps theta resident in HBM; `value_incl_theta_h2d` (--full) is SURVEY.md
+section 8d's definition (theta crosses PCIe every step: the C-ABI host entry point).
 """
 import argparse
 import json
@@ -396,6 +403,42 @@ def dump_outputs(out_dir, arrays):
         np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
+# Untimed evaluations before the warm-up of a run without the host-entry legs.  Those legs keep the device busy for about 14 ms (2 device
+# evaluations, 31 host-entry calls of 0.33 ms, 27 loss-only calls of 0.13 ms) before a --full run warms up, and the shader clock is still
+# ramping over that time: with W = 5 and 50 timed steps a run without any settling measures 9 % more per step.  50 steps of 0.28 ms are the
+# same 14 ms, so a plain and a --full run enter their warm-up in the same device state.
+SETTLE_STEPS = 50
+
+
+def host_entry_legs(eng, step, theta_d, out_d, out_h, theta0, tw, stream):
+    """--full, N = 1: the checks and timings around the C-ABI host entry point, run before the warm-up.  Returns the ms per call of
+    pinn_loss_grad with and without the gradient."""
+    import numpy as np
+    # cross-check of the zero-copy delivery against a plain device-buffer evaluation + copy
+    step()
+    eng.loss_grad_device(theta_d.data_ptr(), out_d.data_ptr(), tw, stream.cuda_stream)
+    stream.synchronize()
+    assert np.array_equal(out_d.cpu().numpy(), out_h.numpy()), "zero-copy host delivery differs from the device buffer"
+    # the C-ABI host entry point (theta from host memory, loss + gradient back to host memory: PCIe both ways)
+    th = np.ascontiguousarray(theta0, dtype=np.float32)
+    for _ in range(5):
+        eng.loss_grad(th, tw)
+    nh = 25
+    t1 = time.perf_counter()
+    for _ in range(nh):
+        eng.loss_grad(th, tw)
+    host_path_ms = (time.perf_counter() - t1) / nh * 1e3
+    # the loss-only evaluation through the same entry point (grad = NULL: no reverse sweep), same numbers for the losses
+    l_full, _ = eng.loss_grad(th, tw)
+    l_only, _ = eng.loss_grad(th, tw, want_grad=False)
+    assert np.allclose(l_only, l_full, rtol=1e-13, atol=0), "loss-only evaluation differs from the fused evaluation's losses"
+    t1 = time.perf_counter()
+    for _ in range(nh):
+        eng.loss_grad(th, tw, want_grad=False)
+    loss_only_ms = (time.perf_counter() - t1) / nh * 1e3
+    return host_path_ms, loss_only_ms
+
+
 def emit(line):
     """the ONE JSON line, as the LAST line of stdout: native libraries (RCCL prints a version banner through C stdio when a communicator is made) keep
     their text in C buffers that would otherwise be flushed at exit, i.e. behind the JSON"""
@@ -408,7 +451,7 @@ def emit(line):
     print(json.dumps(line), flush=True)
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -432,7 +475,11 @@ def main():
                     help="f64: the engine's FLOAT64 evaluation mode (pinn_set_option(h, \"precision\", \"f64\"): the reference's default eltype, "
                          "src/discretize.jl:432-449) on the same workload — its own line with a roofline entry against the f64 MFMA peak (r05: "
                          "v_mfma_f64_16x16x4_f64 tile kernels, csrc/pinn_kernels5.hpp).  Not the headline metric (north star: fp32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline figure does not need (N = 1): before the warm-up the cross-check of the zero-copy host "
+                         "delivery, the C-ABI host entry point and the loss-only evaluation, after the timed region the CPU baseline.  Off by "
+                         "default: a plain run sets up, warms up, times the steps, dumps and prints; the timed steps are the same either way")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--events", choices=["all", "none"], default="all",
                     help="HIP events recorded inside the timed region around every fused residual kernel (sampled steps only), or none")
     ap.add_argument("--event-every", type=int, default=0, help="record the HIP events on every M-th timed step (a start/stop pair plus "
@@ -441,7 +488,11 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (rank 0): grad + "
                          "loss_terms, or with --resident theta + loss_history")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = make_parser().parse_args()
 
     # the host driver of this pool only supports dmabuf IPC: without this RCCL's peer-buffer exchange fails with hipIpcGetMemHandle errors
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -574,33 +625,16 @@ def main():
     loss_only_ms = None
     if args.resident:
         run_steps(30 + args.warmup)
-    elif world == 1 and not sharded:
-        # (measured BEFORE the warm-up and the timed region: it doubles as the clock / cache warm-up of the device)
-        # cross-check of the zero-copy delivery against a plain device-buffer evaluation + copy
+    elif args.full and world == 1 and not sharded:
+        # (measured BEFORE the warm-up and the timed region: it doubles as the clock / cache settling of the device)
         eng.set_timing(0, -1)
-        step()
-        eng.loss_grad_device(theta_d.data_ptr(), out_d.data_ptr(), tw, stream.cuda_stream)
-        stream.synchronize()
-        assert np.array_equal(out_d.cpu().numpy(), out_h.numpy()), "zero-copy host delivery differs from the device buffer"
-        # the C-ABI host entry point (theta from host memory, loss + gradient back to host memory: PCIe both ways)
-        th = np.ascontiguousarray(theta0, dtype=np.float32)
-        for _ in range(5):
-            eng.loss_grad(th, tw)
-        nh = 25
-        t1 = time.perf_counter()
-        for _ in range(nh):
-            eng.loss_grad(th, tw)
-        host_path_ms = (time.perf_counter() - t1) / nh * 1e3
-        # the loss-only evaluation through the same entry point (grad = NULL: no reverse sweep), same numbers for the losses
-        l_full, _ = eng.loss_grad(th, tw)
-        l_only, _ = eng.loss_grad(th, tw, want_grad=False)
-        assert np.allclose(l_only, l_full, rtol=1e-13, atol=0), "loss-only evaluation differs from the fused evaluation's losses"
-        t1 = time.perf_counter()
-        for _ in range(nh):
-            eng.loss_grad(th, tw, want_grad=False)
-        loss_only_ms = (time.perf_counter() - t1) / nh * 1e3
+        host_path_ms, loss_only_ms = host_entry_legs(eng, step, theta_d, out_d, out_h, theta0, tw, stream)
+    elif world == 1 and not sharded:
+        eng.set_timing(0, -1)
+        for _ in range(SETTLE_STEPS):        # the device clock / cache settling a --full run gets from its host-entry legs
+            step()
     else:
-        for _ in range(30):                  # N > 1: the same device clock / cache settling the N = 1 leg gets from the checks above
+        for _ in range(30):                  # N > 1: the device clock / cache settling of the N = 1 leg
             step()
     for _ in range(0 if args.resident else args.warmup):
         step()
@@ -708,7 +742,7 @@ def main():
                                   "(null: no committed profile for this kernel and size)")})
             line["roofline"] = roof
             line["roofline_kernels"] = per_kernel
-        if world == 1 and not sharded and not args.no_cpu_baseline and args.workload == "cfg2":
+        if args.full and world == 1 and not sharded and not args.no_cpu_baseline and args.workload == "cfg2":
             line["cpu_baseline"] = cpu_baseline(npde, wl, sets)
         emit(line)
     if world > 1:

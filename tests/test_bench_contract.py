@@ -1,5 +1,5 @@
-"""The committed bench line (the newest profiles/rNN_bench.json, written by `python bench.py` on an MI355X) keeps the driver's contract: metric / unit /
-value / timing fields, the `roofline` object of the dominant kernel and the `cpu_baseline` object — and its numbers are mutually consistent.
+"""The committed bench line (the newest profiles/rNN_bench.json, written by `python bench.py --full` on an MI355X) keeps the driver's contract: metric /
+unit / value / timing fields, the `roofline` object of the dominant kernel and the `cpu_baseline` object — and its numbers are mutually consistent.
 Runs on CPU: it reads the committed evidence, not the GPU."""
 import json
 import os
@@ -94,3 +94,18 @@ def test_dump_outputs_writes_one_float_npy_per_array(tmp_path):
     with pytest.raises(AssertionError):
         bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((64 << 20) // 8 + 1)})
     assert not (tmp_path / "big").exists()
+
+
+def test_full_option_exists_and_is_off_by_default():
+    """`bench.py --full` switches on everything the headline figure does not need; a plain run has it off.  Argument parsing needs no GPU."""
+    import subprocess
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    ap = bench.make_parser()
+    plain = ap.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert plain.full is False and plain.no_cpu_baseline is False and (plain.steps, plain.warmup, plain.dump_outputs) == (7, 3, None)
+    assert ap.parse_args(["--full"]).full is True
+    assert ap.parse_args(["--full", "--no-cpu-baseline", "--dump-outputs", "d"]).dump_outputs == "d"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout

@@ -429,3 +429,30 @@ def test_bench_two_ranks_share_the_gpu(hip_lib):
     l2 = json.loads([l for l in two.stdout.splitlines() if l.startswith("{")][-1])
     assert l2["n_gpus"] == 2 and l2["config"]["parallelism"] == "point-shard x2"
     np.testing.assert_allclose(l2["loss_terms"], l1["loss_terms"], rtol=1e-6)
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_rest(hip_lib, tmp_path):
+    """A plain bench.py run carries the headline fields and the roofline of its timed steps and none of the legs that take runs of their own;
+    --full adds them (host entry point, loss-only evaluation; the CPU baseline is left out here for time) and delivers the same outputs."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = {}, {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "2", "--points", "8192",
+                            "--dump-outputs", str(tmp_path / tag)] + extra, cwd=root, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert r.stdout.splitlines()[-1].startswith("{")                  # the JSON line is the last line of stdout
+        lines[tag] = json.loads(r.stdout.splitlines()[-1])
+        dumps[tag] = {n: np.load(tmp_path / tag / (n + ".npy")) for n in ("grad", "loss_terms")}
+    for d in lines.values():
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline", "roofline_kernels", "loss_terms"):
+            assert k in d, k
+        assert d["steps"] == 20 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 / d["config"]["interior_points"] - 1.0) < 1e-6
+        assert "cpu_baseline" not in d
+    for k in ("metric", "unit", "higher_is_better", "dtype", "config", "loss_terms"):
+        assert lines["plain"][k] == lines["full"][k], k
+    for k in ("value_incl_theta_h2d", "host_entry_ms_per_step", "loss_only_host_entry_ms"):
+        assert lines["plain"][k] is None and lines["full"][k] > 0, k
+    for n in ("grad", "loss_terms"):
+        assert np.array_equal(dumps["plain"][n], dumps["full"][n]), n

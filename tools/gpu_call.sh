@@ -5,7 +5,8 @@
 # Steps:
 #   tests            python -m pytest tests -m gpu -q                              -> tests.txt
 #   tests:<expr>     ... -k "<expr>" -s                                             -> tests_<n>.txt
-#   bench[:args]     python bench.py [args]                                         -> bench.json / bench.err
+#   bench            python bench.py --full (every leg: the line profiles/rNN_bench.json keeps) -> bench.json / bench.err
+#   bench:<args>     python bench.py <args> (a plain run unless <args> has --full)   -> bench_<n>.json / bench_<n>.err
 #   trace            rocprofv3 --kernel-trace --stats of bench.py                   -> trace/ + kernel_stats.txt
 #   trace:<args>     the same with bench.py <args> (e.g. --precision f64)                        -> trace_<n>/ + kernel_stats_<n>.txt
 #   pmc              tools/pmc_profile.sh (separate --pmc passes, kernel-trace only) -> pmc/
@@ -30,7 +31,7 @@ for step in "$@"; do
     case "$step" in
         tests)      timeout 1500 python -m pytest tests -m gpu -q --durations=30 > "$O/tests.txt" 2>&1; tail -n 3 "$O/tests.txt" ;;
         tests:*)    timeout 1500 python -m pytest tests -m gpu -q -s -k "${step#tests:}" > "$O/tests_$n.txt" 2>&1; grep -v "^$" "$O/tests_$n.txt" | tail -n 60 ;;
-        bench)      timeout 900 python bench.py > "$O/bench.json" 2> "$O/bench.err"; tail -c 1500 "$O/bench.json" ;;
+        bench)      timeout 900 python bench.py --full > "$O/bench.json" 2> "$O/bench.err"; tail -c 1500 "$O/bench.json" ;;
         bench:*)    timeout 900 python bench.py ${step#bench:} > "$O/bench_$n.json" 2> "$O/bench_$n.err"; head -c 600 "$O/bench_$n.json"; echo ;;
         trace)      (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d "$OLDPWD/$O/trace" -o t -- python "$OLDPWD/bench.py" --steps 80 --warmup 5 --no-cpu-baseline > "$OLDPWD/$O/bench_under_rocprof.json" 2> "$OLDPWD/$O/trace.err")
                     python profiles/rocpd_stats.py "$(find "$O/trace" -name '*_results.db' | head -n 1)" > "$O/kernel_stats.txt" 2>&1; head -n 12 "$O/kernel_stats.txt"; find "$O/trace" -name '*.db' -size +20M -delete ;;
