@@ -286,7 +286,7 @@ int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int histor
  *   v_mfma_f64_16x16x4_f64 (csrc/pinn_kernels5.hpp) for tanh / sigmoid nets with hidden layers up to 64 wide and the instantiated jet sets,
  *   one lane per point on the fp64 VALU (csrc/pinn_kernels4.hpp) for everything else the mode covers; pinn_get_option(h, "f64_path") reports
  *   what the last evaluation ran ("mfma" | "lanes" | "mfma+lanes").  7-8x the time of the fp32 kernels on the matrix pipe.
- *   Covers equations of up to 6 dependent variables (same argument count), Dense chains with tanh / sigmoid / sin, derivative orders <= 2
+ *   Covers equations of up to 6 dependent variables (same argument count), Dense chains with tanh / sigmoid / sin / swish (sin, swish: one lane per point), derivative orders <= 2
  *   in 1-3 inputs (1-D, and mixed / pure in 2-D and 3-D where instantiated: <= 4; 4-D: first and pure second), PDE parameters, quadrature
  *   weights, per-point DATA channels, device samplers, periodic input embeddings (r06); anything else (DGM) fails HERE with a message and leaves the fp32
  *   plan usable.  In this mode EVERY evaluating entry point runs the double kernels (r06): pinn_loss_grad / pinn_loss_grad_device /

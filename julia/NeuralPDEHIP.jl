@@ -366,7 +366,7 @@ end
 # 2. descriptor ("pinnir 2")
 # ------------------------------------------------------------------------------------------------
 const ACT_NAMES = Dict{Any, String}(tanh => "tanh", Lux.tanh_fast => "tanh", Lux.sigmoid => "sigmoid", Lux.sigmoid_fast => "sigmoid",
-                                    sin => "sin", identity => "identity")
+                                    sin => "sin", Lux.swish => "swish", identity => "identity")       # (Lux.swish is NNlib.swish: Lux re-exports it)
 
 chains_of(pinnrep::PINNRepresentation) = pinnrep.phi isa AbstractVector ? [p.smodel.model for p in pinnrep.phi] : [pinnrep.phi.smodel.model]
 
@@ -379,7 +379,7 @@ function dgm_lines(i::Int, dgm, θoff::Int, depvar::Symbol, inputs)
     gated = collect(values(block.layers))
     lstm = gated[1] isa Lux.SkipConnection ? gated[1].layers : gated[1]
     a1, a2 = act_name(lstm.activation1), act_name(lstm.activation2)
-    (a1 === nothing || a2 === nothing || a1 == "identity" || a2 == "identity") &&
+    (a1 === nothing || a2 === nothing || a1 in ("identity", "swish") || a2 in ("identity", "swish")) &&
         throw(HIPEngineError("unsupported DGM activations ($(lstm.activation1), $(lstm.activation2)); supported: tanh, sigmoid, sin"))
     act_name(first_dense.activation) == a1 || throw(HIPEngineError("DGM: the first Dense layer must use activation1"))
     act_name(last_dense.activation) == "identity" || throw(HIPEngineError("the HIP engine runs DGM networks with the identity output activation"))
@@ -413,7 +413,7 @@ function chain_lines(i::Int, chain, θoff::Int, depvar::Symbol, inputs)
     all(l -> l isa Lux.Dense, layers) || throw(HIPEngineError("the HIP engine runs Chains of Dense layers, optionally behind a PeriodicEmbedding (got $(typeof.(layers)))"))
     length(layers) >= 2 || throw(HIPEngineError("the HIP engine needs at least one hidden layer"))
     acts = [act_name(l.activation) for l in layers]
-    any(isnothing, acts) && throw(HIPEngineError("unsupported activation in chain $i: $([l.activation for l in layers]) (supported: tanh, sigmoid, sin)"))
+    any(isnothing, acts) && throw(HIPEngineError("unsupported activation in chain $i: $([l.activation for l in layers]) (supported: tanh, sigmoid, sin, swish)"))
     acts[end] == "identity" || throw(HIPEngineError("the last layer must have identity activation"))
     layers[end].out_dims == 1 || throw(HIPEngineError("each chain must have a single output (one chain per dependent variable, src/pinn_types.jl:106-108)"))
     all(l -> Lux.LuxCore.parameterlength(l) == l.in_dims * l.out_dims + l.out_dims, layers) ||

@@ -44,7 +44,7 @@ int parse_descriptor(const char* text, pinn_engine& E) {
         std::string act;
         if (!expect("net") || !(in >> id >> act >> E.nets[i].theta_off >> ns) || id != i) return fail("descriptor: net line");
         // one activation for all hidden layers, or a comma-separated list with one entry per hidden layer: tanh and sigmoid may be mixed
-        // (e.g. the reference's Dense(1, n, tanh), Dense(n, n, sigma), Dense(n, 1)); sin only on all layers
+        // (e.g. the reference's Dense(1, n, tanh), Dense(n, n, sigma), Dense(n, 1)); sin and swish only on all layers
         std::vector<int> kinds;
         bool dgm = false;
         {
@@ -60,7 +60,8 @@ int parse_descriptor(const char* text, pinn_engine& E) {
                 if (tok == "tanh") kinds.push_back(pk::ACT_TANH);
                 else if (tok == "sigmoid") kinds.push_back(pk::ACT_SIGMOID);
                 else if (tok == "sin") kinds.push_back(pk::ACT_SIN);
-                else return fail("descriptor: unsupported activation '" + tok + "' (supported: tanh, sigmoid, sin)");
+                else if (tok == "swish") kinds.push_back(pk::ACT_SWISH);
+                else return fail("descriptor: unsupported activation '" + tok + "' (supported: tanh, sigmoid, sin, swish)");
             }
         }
         E.nets[i].sizes.resize(ns);
@@ -99,6 +100,7 @@ int parse_descriptor(const char* text, pinn_engine& E) {
             if (kinds.size() != 2 || E.nets[i].dgm_layers < 1 || ns != 3 || E.nets[i].sizes[2] != 1)
                 return fail("descriptor: a DGM net line reads `net <i> dgm,<activation1>,<activation2>,<layers> <theta_off> 3 <d> <modes> 1`");
             if (E.nets[i].sizes[1] > 64) return fail("descriptor: DGM networks are supported up to 64 modes");
+            if (kinds[0] == pk::ACT_SWISH || kinds[1] == pk::ACT_SWISH) return fail("descriptor: unsupported DGM activations (supported: tanh, sigmoid, sin)");
             E.nets[i].kind = 1;
             E.nets[i].act = kinds[0];
             E.nets[i].act2 = kinds[1];
@@ -118,6 +120,7 @@ int parse_descriptor(const char* text, pinn_engine& E) {
             if (nhidden > 8) return fail("descriptor: per-layer activations cover at most 8 hidden layers");
             for (int l = 0; l < nhidden; ++l) {
                 if (kinds[l] == pk::ACT_SIN) return fail("descriptor: sin cannot be mixed with other activations inside one chain");
+                if (kinds[l] == pk::ACT_SWISH) return fail("descriptor: swish cannot be mixed with other activations inside one chain");
                 E.nets[i].act_layers |= kinds[l] << (4 * l);
             }
             E.nets[i].act = pk::ACT_MIXED;

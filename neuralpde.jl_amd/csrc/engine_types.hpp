@@ -31,7 +31,7 @@ struct Slot {
     unsigned lap = 0;        // != 0: the sum of the pure second derivatives over these axes (one "forward Laplacian" jet channel)
 };
 struct Net {
-    int act;                         // ACT_TANH / ACT_SIGMOID / ACT_SIN on every hidden layer, or ACT_MIXED with
+    int act;                         // ACT_TANH / ACT_SIGMOID / ACT_SIN / ACT_SWISH on every hidden layer, or ACT_MIXED with
     int act_layers = 0;              //   the kind of hidden layer l (tanh / sigmoid) in bits 4l .. 4l+3
     int theta_off;
     std::vector<int> sizes;          // n0 .. nL (nL == 1); DGM: {d, modes, 1}
@@ -388,7 +388,7 @@ const std::vector<unsigned>& gen_set(int id);
 unsigned slot_mi(const Slot& s);                               // multi-index of a slot
 bool slot_is_general(const Slot& s);                           // not representable by the fixed channel categories      // jet channel of a slot in a kernel's channel set (-1: not carried)
 // kernel-variant bit a network's activation needs beyond the tanh / sigmoid kernels every spec has (SpecInfo::has_sin)
-inline int variant_of(int act) { return act == pk::ACT_SIN ? 1 : (act == pk::ACT_MIXED ? 2 : 0); }
+inline int variant_of(int act) { return act == pk::ACT_SIN ? pk::VARIANT_SIN : (act == pk::ACT_MIXED ? pk::VARIANT_MIXED : (act == pk::ACT_SWISH ? pk::VARIANT_SWISH : 0)); }
 std::string spec_name(const pk::SpecInfo& s);
 int build_plan(pinn_engine& E);
 void free_plan(pinn_engine& E);            // releases everything build_plan allocated (the terms keep their point sets)

@@ -137,7 +137,7 @@ static const pk::F64MKernel* f64_find_m(const pinn_engine& E, const pk::F64Kerne
     int maxh = 0;
     for (int net : nets) {
         const Net& N = E.nets[net];
-        if (N.act == pk::ACT_SIN || N.sizes.size() < 3) return nullptr;
+        if (pk::act_records_z(pk::act_class(N.act)) || N.sizes.size() < 3) return nullptr;        // sin, swish: family 4
         for (size_t j = 1; j + 1 < N.sizes.size(); ++j) maxh = std::max(maxh, N.sizes[j]);
     }
     // a register-resident kernel (family 4m) before a channel-sliced one (family 4s: every layer through the scratch rows); the narrowest that covers the width
@@ -317,17 +317,20 @@ int f64_enable(pinn_engine& E) {
         if (nets.empty()) return fail(who + "references no dependent variable");
         if ((int)nets.size() > pk::F64_MAX_NETS) return fail(who + "references more than 6 dependent variables");
         F.nets = nets;
-        bool any_sin = false, all_sin = true;
+        bool any_sin = false, all_sin = true, any_swish = false, all_swish = true;
         for (int net : nets) {
             const Net& N = E.nets[net];
             if (N.kind != 0) return fail(who + "DGM networks are not covered by the float64 mode");
-            if (N.act != pk::ACT_TANH && N.act != pk::ACT_SIGMOID && N.act != pk::ACT_SIN && N.act != pk::ACT_MIXED) return fail(who + "this activation is not covered by the float64 mode");
+            if (N.act != pk::ACT_TANH && N.act != pk::ACT_SIGMOID && N.act != pk::ACT_SIN && N.act != pk::ACT_MIXED && N.act != pk::ACT_SWISH) return fail(who + "this activation is not covered by the float64 mode");
             if (N.act == pk::ACT_MIXED && (int)N.sizes.size() - 2 > 8) return fail(who + "per-layer tanh / sigmoid mixes of more than 8 hidden layers are not covered by the float64 mode");
             if ((int)N.sizes.size() - 1 > pk::F64_MAX_LAYERS) return fail(who + "more than 16 Dense layers");
             if (N.sizes[0] != E.nets[nets[0]].sizes[0]) return fail(who + "its dependent variables take different numbers of arguments (one jet set serves all networks of an equation in the float64 mode)");
             any_sin = any_sin || N.act == pk::ACT_SIN;
             all_sin = all_sin && N.act == pk::ACT_SIN;
+            any_swish = any_swish || N.act == pk::ACT_SWISH;
+            all_swish = all_swish && N.act == pk::ACT_SWISH;
         }
+        if (any_swish && !all_swish) return fail(who + "mixes swish networks with networks of another activation");
         if (any_sin && !all_sin) return fail(who + "mixes sin networks with tanh / sigmoid networks");
         // (periodic input embeddings, r06: the descriptor has rewritten the term already — sin / cos feature rows behind the user's coordinates, the
         // network mapped onto them, derivative slots as chain-rule combinations (descriptor.cpp: apply_embeddings); this mode fills the feature rows in DOUBLE)
@@ -413,7 +416,8 @@ int f64_set_point_data(pinn_engine& E, int term, const double* data) {
 struct F64Launch {
     pk::F64Args a;
     int rows = 0;                        // scratch rows per point
-    bool sin_act = false, mfma = false;
+    int acls = pk::ACLS_A;               // activation class of the term's networks (one per term: f64_prepare)
+    bool mfma = false;
     bool sliced = false;                 // family 4s: the tile kernel passes every layer through the scratch rows (needed in every mode)
 };
 // everything of F64Args that does not depend on the evaluation (theta, weights, mode, chunk): networks, scratch row numbering, tape, slots
@@ -428,7 +432,7 @@ static int f64_build(pinn_engine& E, const F64Term& F, int dt, const std::map<in
     a.C = F.k->C;
     for (int i = 0; i < 8; ++i) a.first_ch[i] = F.k->first_ch[i];
     int rows = 0, ent = 0;
-    L.sin_act = false;
+    L.acls = pk::ACLS_A;
     L.mfma = F.km && std::getenv("PINN_F64_NO_MFMA") == nullptr;
     L.sliced = L.mfma && F.km->sliced != 0;
     a.use_ceff = L.sliced ? 1 : 0;
@@ -455,7 +459,7 @@ static int f64_build(pinn_engine& E, const F64Term& F, int dt, const std::map<in
         n.ceff = 1;
         for (int sl = 0; sl < F.nslots; ++sl) if (F.slot_net[sl] == ni) n.ceff = std::max(n.ceff, F.slot_chan[sl] + 1);
         if (std::getenv("PINN_F64_FULL_CHANNELS")) n.ceff = a.C;              // (A/B, tests)
-        L.sin_act = L.sin_act || N.act == pk::ACT_SIN;
+        if (pk::act_class(N.act) != pk::ACLS_A) L.acls = pk::act_class(N.act);
         n.theta0 = N.theta_off; n.nparams = N.nparams(); n.ent0 = ent;
         ent += n.nparams;
         n.tp0 = a.tp_p;                                       // (running column count of the tile partial sums)
@@ -465,7 +469,7 @@ static int f64_build(pinn_engine& E, const F64Term& F, int dt, const std::map<in
         for (int l = 0; l < LH; ++l) { n.r_rec[l] = rows; rows += N.sizes[l + 1] * a.C; }
         // value-only terms of tanh / sigmoid networks: the record of an element IS its post-activation value (act_record), so the
         // matrix-pipe kernels keep ONE copy (a third of the tile kernel's stores less; 4 of the bench workload's 5 terms)
-        const bool post_is_rec = L.mfma && a.C == 1 && N.act != pk::ACT_SIN;
+        const bool post_is_rec = L.mfma && a.C == 1 && !pk::act_records_z(pk::act_class(N.act));
         a.post_alias = post_is_rec ? 1 : 0;
         for (int l = 0; l < LH; ++l) { if (post_is_rec) n.r_post[l] = n.r_rec[l]; else { n.r_post[l] = rows; rows += N.sizes[l + 1] * a.C; } }
         for (int l = 0; l < LH; ++l) { n.r_dz[l] = rows; rows += N.sizes[l + 1] * a.C; }
@@ -754,7 +758,7 @@ static int f64_stencil_term(pinn_engine& E, int t, const double* theta, double* 
         for (int64_t p0 = 0; p0 < n; p0 += chunk) {
             a.p0 = (int)p0;
             a.npts = (int)std::min<int64_t>(chunk, n - p0);
-            F.k->launch_point(a, L.sin_act, E.stream);
+            F.k->launch_point(a, L.acls, E.stream);
             pk::launch_f64_dw(a, E.stream);
             pk::launch_f64_dwt(a, E.stream);
             pk::F64ReduceArgs r;
@@ -992,7 +996,7 @@ static int f64_eval_device(pinn_engine& E, const double* theta, double* grad, do
             a.npts = (int)std::min<int64_t>(chunk, F.n - p0);
             const int nblocks = f64_short_blocks(E, S, L);
             if (L.mfma) f64_launch_tile(F.km, a, E.stream);
-            else F.k->launch_point(a, L.sin_act, E.stream);
+            else F.k->launch_point(a, L.acls, E.stream);
             if (!L.mfma) pk::launch_f64_dw(a, E.stream);         // (matrix-pipe path: those entries come out of the tile kernel, summed in the dW launch)
             if (L.mfma) F.km->launch_dwt(a, E.stream);
             else pk::launch_f64_dwt(a, E.stream);
@@ -1046,7 +1050,7 @@ static int f64_values(pinn_engine& E, F64State& S, const F64Term& F, F64Launch& 
         a.p0 = (int)p0;
         a.npts = (int)std::min<int64_t>(chunk, n - p0);
         if (L.mfma) f64_launch_tile(F.km, a, E.stream);
-        else F.k->launch_point(a, L.sin_act, E.stream);
+        else F.k->launch_point(a, L.acls, E.stream);
     }
     return 0;
 }
@@ -1081,7 +1085,7 @@ int f64_net_eval(pinn_engine& E, int net, const double* theta, const double* pts
     const Net& N = E.nets[net];
     const std::string who = "float64 trial-function evaluation: ";
     if (N.kind != 0) return fail(who + "DGM networks are not covered by the float64 mode");
-    if (N.act != pk::ACT_TANH && N.act != pk::ACT_SIGMOID && N.act != pk::ACT_SIN && N.act != pk::ACT_MIXED) return fail(who + "this activation is not covered by the float64 mode");
+    if (N.act != pk::ACT_TANH && N.act != pk::ACT_SIGMOID && N.act != pk::ACT_SIN && N.act != pk::ACT_MIXED && N.act != pk::ACT_SWISH) return fail(who + "this activation is not covered by the float64 mode");
     if ((int)N.sizes.size() - 1 > pk::F64_MAX_LAYERS || N.sizes[0] > 4) return fail(who + "more than 16 Dense layers / more than 4 inputs");
     const int d = N.sizes[0];
     // a network behind a periodic input embedding (r06; value only): the caller's points are the dependent variable's ARGUMENTS [n][n_inputs]; the
@@ -1302,7 +1306,8 @@ std::string f64_describe(const pinn_engine& E) {
     for (size_t t = 0; t < S.terms.size(); ++t) {
         const F64Term& F = S.terms[t];
         c += (t ? "," : "") + std::to_string(F.k ? F.k->C : 0);
-        k += (t ? "," : "") + (F.km ? std::string(F.km->sliced ? "mfma-sliced:HT" : "mfma:HT") + std::to_string(F.km->HT) + "xPG" + std::to_string(F.km->PG) : std::string("lanes"));
+        k += (t ? "," : "") + (F.km ? std::string(F.km->sliced ? "mfma-sliced:HT" : "mfma:HT") + std::to_string(F.km->HT) + "xPG" + std::to_string(F.km->PG) : std::string("lanes"))
+             + (!F.nets.empty() && E.nets[F.nets[0]].act == pk::ACT_SWISH ? "+swish" : "");
     }
     return c + k;
 }

@@ -29,7 +29,7 @@ struct SpecInfo {
     unsigned LAP;                    // axis mask of the forward-Laplacian channel (0: none)
     int NPAIR, PG, C, NG, TP, MT, LH, NFIRST;
     int PACKED, SLAB, SCR, LDS_WG, COOP, SH, PW;
-    int has_sin;                     // extra kernel variants compiled for this spec: bit 0 = sin activation, bit 1 = per-layer tanh / sigmoid (ACT_MIXED)
+    int has_sin;                     // extra kernel variants compiled for this spec (VARIANT_* bits): sin activation, per-layer tanh / sigmoid (ACT_MIXED), swish activation
     int REC;                         // floats per tile of the HBM record store (MODE_FWDREC / MODE_GRADREC); 0: not supported
     int jit;                         // 1: specialised at run time (jit.cpp), 0: from the ahead-of-time table
     int act1, act2, dgm_rows;        // family 3 (DGM): gate / output-gate activation kinds, scratch rows per point

@@ -50,9 +50,19 @@ namespace pk {
 using namespace wv;
 
 // The record of a layer keeps r0 = phi(z) for tanh / sigmoid (their derivatives are polynomials in phi) and r0 = z for sin
-// (cos z cannot be recovered from sin z); act_derivs_n / act_from_record take that r0.
+// (cos z cannot be recovered from sin z) and swish (z sigma(z) is not invertible); act_derivs_n / act_from_record take that r0.
 enum Act : int { ACT_TANH = 0, ACT_SIGMOID = 1, ACT_SIN = 2,
-                 ACT_MIXED = 3 /* kernel variant only: tanh / sigmoid chosen per hidden layer at run time, branch-free */ };
+                 ACT_MIXED = 3 /* kernel variant only: tanh / sigmoid chosen per hidden layer at run time, branch-free */,
+                 ACT_SWISH = 4 /* z sigma(z) */ };
+constexpr int NUM_ACTS = 5;
+// The activation class of a kernel: what a layer's record holds and which rules read it.  A compile-time parameter of every activation /
+// jet rule below (a later activation takes the next value and its own branch in act_value / act_derivs_n / act_from_record).
+enum ActClass : int { ACLS_A = 0 /* record = a = phi(z): tanh / sigmoid / mixed, rules are polynomials in a */,
+                      ACLS_Z_SIN = 1 /* record = z, sin rules */, ACLS_Z_SWISH = 2 /* record = z, swish rules */ };
+constexpr int act_class(int actk) { return actk == ACT_SIN ? ACLS_Z_SIN : (actk == ACT_SWISH ? ACLS_Z_SWISH : ACLS_A); }
+constexpr bool act_records_z(int acls) { return acls != ACLS_A; }
+// kernel-variant bits: what a spec carries beyond the tanh / sigmoid kernels every spec has (SpecInfo::has_sin, engine_types.hpp variant_of)
+enum Variant : int { VARIANT_SIN = 1, VARIANT_MIXED = 2, VARIANT_SWISH = 4 };
 // FUSED: forward + residual tape + reverse sweep.  RESID: forward + tape, writes r.  FWD: forward only, writes the jet
 // channels per point.  GRADIN: forward + reverse sweep seeded with per-point d(loss)/d(jet) read from memory (equations that
 // couple several networks: the tape runs in k_expr between the FWD and GRADIN launches of every network involved).
@@ -260,7 +270,7 @@ struct GroupArgs {
     int ntiles;
     int nparams;                 // NP rows in the tape
     int nparams_estim;           // first NE params get adjoints
-    int act;                     // ACT_TANH / ACT_SIGMOID / ACT_SIN for all hidden layers, or ACT_MIXED:
+    int act;                     // ACT_TANH / ACT_SIGMOID / ACT_SIN / ACT_SWISH for all hidden layers, or ACT_MIXED:
     int act_layers;              //   kind of hidden layer l (tanh / sigmoid) in bits 4l .. 4l+3
     // family 3 (DGM, pinn_kernels3.hpp): `packed` points at the network's parameters inside theta (unpacked), `scratch` at the
     // point-major scratch rows [Spec3::ROWS][dgm_npad]
@@ -291,7 +301,7 @@ template <class V> DEV V sig_poly6(V s) {
 template <class V> DEV V sig_poly7(V s) {
     return vfma(vfma(vfma(vfma(vfma(vfma(V(5040.0f), s, V(-15120.0f)), s, V(16800.0f)), s, V(-8400.0f)), s, V(1806.0f)), s, V(-126.0f)), s, V(1.0f));
 }
-template <int NORD, bool SINACT, bool MIXED = false, class V = vfloat>
+template <int NORD, int ACLS, bool MIXED = false, class V = vfloat>
 DEV void act_derivs_n(int act, V a, V (&d)[ND]) {
     if (MIXED) {
         const float m = 2.0f - (float)act, im = 0.5f + 0.5f * (float)act, m2 = m * m;      // act in {ACT_TANH = 0, ACT_SIGMOID = 1}
@@ -308,7 +318,31 @@ DEV void act_derivs_n(int act, V a, V (&d)[ND]) {
         if (NORD >= 7) d[7] = V(m2 * m2 * m2 * m2) * s1 * sig_poly7(s);
         return;
     }
-    if (SINACT) {
+    if (ACLS == ACLS_Z_SWISH) {
+        // f = z s with s = sigma(z): f^(k) = z s^(k) + k s^(k-1), the logistic derivatives s^(k) as in the sigmoid branch below.
+        // One transcendental (the sigmoid).  |z| large: s -> 0 or 1 exactly, every s^(k>0) = 0, so f' -> 0 or 1 and the rest -> 0 (no inf * 0: z is finite)
+        const V z = a, s = vsigmoid_fast(z);
+        const V s1 = s * (V(1.0f) - s);
+        const V s2 = s1 * vfma(V(-2.0f), s, V(1.0f));
+        const V s3 = s1 * vfma(V(-6.0f), s1, V(1.0f));
+        d[1] = vfma(z, s1, s);
+        d[2] = vfma(z, s2, V(2.0f) * s1);
+        d[3] = vfma(z, s3, V(3.0f) * s2);
+        if (NORD >= 4) {
+            const V q = vfma(V(-12.0f), s1, V(1.0f));
+            const V s4 = s2 * q;
+            d[4] = vfma(z, s4, V(4.0f) * s3);
+            if (NORD >= 5) {
+                const V s5 = vfma(s3, q, V(-12.0f) * s2 * s2);
+                d[5] = vfma(z, s5, V(5.0f) * s4);
+                if (NORD >= 6) {
+                    const V s6 = s1 * sig_poly6(s);
+                    d[6] = vfma(z, s6, V(6.0f) * s5);
+                    if (NORD >= 7) d[7] = vfma(z, s1 * sig_poly7(s), V(7.0f) * s6);
+                }
+            }
+        }
+    } else if (ACLS == ACLS_Z_SIN) {
         V sn, cs;
         vsincos(a, sn, cs);
         d[1] = cs;
@@ -435,29 +469,31 @@ DEV void jet_adjoint(V (&g)[J::C], const V (&s)[J::C], const V (&d)[ND]) {
     PINN_UNROLL for (int k = 0; k < J::N3; ++k) g[J::CH_3 + k] = z3b[k];
 }
 
-template <bool SINACT, bool MIXED = false, class V = vfloat>
+template <int ACLS, bool MIXED = false, class V = vfloat>
 DEV V act_value(int act, V z) {
     if (MIXED) {
         const float m = 2.0f - (float)act;
         return vfma(vsigmoid_fast(V(m) * z), V(m), V(1.0f - m));
     }
-    if (SINACT) { V sn, cs; vsincos(z, sn, cs); return sn; }
+    if (ACLS == ACLS_Z_SWISH) return z * vsigmoid_fast(z);       // exp overflow: sigma = 0 or 1 exactly, the value 0 or z
+    if (ACLS == ACLS_Z_SIN) { V sn, cs; vsincos(z, sn, cs); return sn; }
     if (act == ACT_TANH) return vtanh_fast(z);
     return vsigmoid_fast(z);
 }
 // the four elements of an accumulator fragment at once (tanh: the pairwise form, vec.hpp vtanh_fast4 — same bits)
-template <bool SINACT>
+template <int ACLS>
 DEV vfloat4 act_value4(int act, vfloat4 z) {
-    if (!SINACT && act == ACT_TANH) return vtanh_fast4(z);
+    if (ACLS == ACLS_A && act == ACT_TANH) return vtanh_fast4(z);
     vfloat4 a;
-    PINN_UNROLL for (int r = 0; r < 4; ++r) a[r] = act_value<SINACT>(act, z[r]);
+    PINN_UNROLL for (int r = 0; r < 4; ++r) a[r] = act_value<ACLS>(act, z[r]);
     return a;
 }
 // record value r0 of an element with pre-activation z and activation a, and the activation back from r0
-template <bool SINACT, class V> DEV V act_record(V z, V a) { return SINACT ? z : a; }
-template <bool SINACT, class V>
+template <int ACLS, class V> DEV V act_record(V z, V a) { return act_records_z(ACLS) ? z : a; }
+template <int ACLS, class V>
 DEV V act_from_record(V r0) {
-    if (!SINACT) return r0;
+    if (ACLS == ACLS_A) return r0;
+    if (ACLS == ACLS_Z_SWISH) return r0 * vsigmoid_fast(r0);
     V sn, cs;
     vsincos(r0, sn, cs);
     return sn;
@@ -494,8 +530,9 @@ DEV void wave_main(const GroupArgs& ga, int blk, int nblocks, int w, float* lds_
     const vbool g0 = veq(g, 0);
     const float* P = ga.packed;
     // the activation kind is a template parameter: every kernel is straight-line code behind its GEMMs (no activation branches for the
-    // optimiser to hoist); sin variants are compiled only for the specs registered with PINN_INSTANTIATE*_SIN
-    constexpr bool SINACT = (ACTK == ACT_SIN);
+    // optimiser to hoist); sin / swish variants are compiled only for the specs registered with them (PINN_INSTANTIATE*_SIN / _SWISH / _SIN_SWISH)
+    constexpr int ACLS = act_class(ACTK);
+    constexpr bool RECZ = act_records_z(ACLS);              // the record keeps z (sin, swish), not a
     constexpr bool MIXED = (ACTK == ACT_MIXED);             // tanh / sigmoid per hidden layer (GroupArgs::act: one nibble per layer), branch-free
     auto act_of = [&](int layer) -> int { return MIXED ? ((ga.act_layers >> (4 * layer)) & 15) : ACTK; };
 
@@ -611,11 +648,11 @@ DEV void wave_main(const GroupArgs& ga, int blk, int nblocks, int w, float* lds_
             const int act = act_of(layer);
             PINN_UNROLL for (int pg = 0; pg < PG; ++pg)
                 PINN_UNROLL for (int m = 0; m < MT; ++m) {
-                    vfloat4 av;                                       // sin: activation values; Z[pg*C] holds the RECORD value z meanwhile
+                    vfloat4 av;                                       // sin / swish: activation values; Z[pg*C] holds the RECORD value z meanwhile
                     PINN_UNROLL for (int r = 0; r < 4; ++r) {
                         const vfloat z0 = Z[pg * C][m][r];
-                        av[r] = act_value<SINACT, MIXED>(act, z0);
-                        Z[pg * C][m][r] = SINACT ? z0 : av[r];
+                        av[r] = act_value<ACLS, MIXED>(act, z0);
+                        Z[pg * C][m][r] = RECZ ? z0 : av[r];
                     }
                     if (BWD) {
                         if (layer == LH - 1) {
@@ -633,11 +670,11 @@ DEV void wave_main(const GroupArgs& ga, int blk, int nblocks, int w, float* lds_
                     PINN_UNROLL for (int r = 0; r < 4; ++r) {
                         vfloat zz[C], dd[ND];
                         PINN_UNROLL for (int ch = 0; ch < C; ++ch) zz[ch] = Z[pg * C + ch][m][r];
-                        act_derivs_n<J::NORD - 1, SINACT, MIXED>(act, zz[0], dd);
+                        act_derivs_n<J::NORD - 1, ACLS, MIXED>(act, zz[0], dd);
                         jet_forward<J>(zz, dd);
                         PINN_UNROLL for (int ch = 1; ch < C; ++ch) Z[pg * C + ch][m][r] = zz[ch];
                     }
-                    if (SINACT) Z[pg * C][m] = av;
+                    if (RECZ) Z[pg * C][m] = av;
                 }
         };
         // k-steps (mi, rr) of hidden layer hl's GEMM; the fragment of step ks+1 is requested before the MFMAs of step ks (software pipeline:
@@ -826,10 +863,10 @@ DEV void wave_main(const GroupArgs& ga, int blk, int nblocks, int w, float* lds_
                 vfloat zz[C], dd[ND];
                 PINN_UNROLL for (int k = 0; k < C; ++k) zz[k] = Sr[pg * C + k][m][r];
                 if (ch > 0) {
-                    act_derivs_n<J::NORD - 1, SINACT, MIXED>(act, zz[0], dd);
+                    act_derivs_n<J::NORD - 1, ACLS, MIXED>(act, zz[0], dd);
                     jet_forward<J>(zz, dd);                 // (ch is a constant after unrolling: the other channels are dead code)
                 }
-                out[r] = (ch == 0) ? act_from_record<SINACT>(zz[0]) : zz[ch];
+                out[r] = (ch == 0) ? act_from_record<ACLS>(zz[0]) : zz[ch];
             }
             return out;
         };
@@ -840,7 +877,7 @@ DEV void wave_main(const GroupArgs& ga, int blk, int nblocks, int w, float* lds_
                     PINN_UNROLL for (int r = 0; r < 4; ++r) {
                         vfloat gg[C], ss[C], dd[ND];
                         PINN_UNROLL for (int k = 0; k < C; ++k) { gg[k] = G[pg * C + k][m][r]; ss[k] = Sr[pg * C + k][m][r]; }
-                        act_derivs_n<J::NORD, SINACT, MIXED>(act, ss[0], dd);
+                        act_derivs_n<J::NORD, ACLS, MIXED>(act, ss[0], dd);
                         jet_adjoint<J>(gg, ss, dd);
                         PINN_UNROLL for (int k = 0; k < C; ++k) G[pg * C + k][m][r] = gg[k];
                     }

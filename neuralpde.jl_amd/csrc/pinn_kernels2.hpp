@@ -328,10 +328,11 @@ DEV void wave_tiles2(const GroupArgs& ga, int blk, int nblocks, int w, float* ld
     const vbool klo = vlt(g, 2);                             // lanes whose k < 16 (first column group of a pair)
     const float* P = ga.packed;
     // the activation kind is a template parameter: every kernel is straight-line code behind its GEMMs (no activation branches for the
-    // optimiser to hoist); sin variants are compiled only for the specs registered with PINN_INSTANTIATE*_SIN
+    // optimiser to hoist); sin / swish variants are compiled only for the specs registered with them (PINN_INSTANTIATE2_HI_SIN / _SWISH / _SIN_SWISH)
     constexpr int act = ACTK;
     static_assert(ACTK != ACT_MIXED, "per-layer activation kinds are compiled for family 1 (small nets) only");
-    constexpr bool SINACT = (ACTK == ACT_SIN);
+    constexpr int ACLS = act_class(ACTK);
+    constexpr bool RECZ = act_records_z(ACLS);              // the record keeps z (sin, swish), not a
     const ubuf PB = ub_make(P, S::PACKED);
     const ubuf SB = ub_make(ga.scratch + (size_t)blk * (ga.scr_stride ? ga.scr_stride : S::SCR), S::SCR);
     float* X0 = lds;
@@ -398,9 +399,9 @@ DEV void wave_tiles2(const GroupArgs& ga, int blk, int nblocks, int w, float* ld
         auto act_forward = [&](vfloat4 (&Z)[NG][MTW], int layer) {
             PINN_UNROLL for (int pg = 0; pg < PG; ++pg)
                 PINN_UNROLL for (int t = 0; t < MTW; ++t) {
-                    vfloat4 av;                                       // sin: activation values; Z[pg*C] holds the RECORD value z meanwhile
-                    av = act_value4<SINACT>(act, Z[pg * C][t]);
-                    if (!SINACT) Z[pg * C][t] = av;
+                    vfloat4 av;                                       // sin / swish: activation values; Z[pg*C] holds the RECORD value z meanwhile
+                    av = act_value4<ACLS>(act, Z[pg * C][t]);
+                    if (!RECZ) Z[pg * C][t] = av;
                     if (RECOUT && layer > 0)
                         PINN_UNROLL for (int ch = 0; ch < C; ++ch)
                             ub_store4(RB, (((layer - 1) * NG + pg * C + ch) * MT + w * MTW + t) * 256, lane << 2, Z[pg * C + ch][t]);
@@ -422,11 +423,11 @@ DEV void wave_tiles2(const GroupArgs& ga, int blk, int nblocks, int w, float* ld
                     PINN_UNROLL for (int r = 0; r < 4; ++r) {
                         vfloat zz[C], dd[ND];
                         PINN_UNROLL for (int ch = 0; ch < C; ++ch) zz[ch] = Z[pg * C + ch][t][r];
-                        act_derivs_n<J::NORD - 1, SINACT>(act, zz[0], dd);
+                        act_derivs_n<J::NORD - 1, ACLS>(act, zz[0], dd);
                         jet_forward<J>(zz, dd);
                         PINN_UNROLL for (int ch = 1; ch < C; ++ch) Z[pg * C + ch][t][r] = zz[ch];
                     }
-                    if (SINACT) Z[pg * C][t] = av;
+                    if (RECZ) Z[pg * C][t] = av;
                 }
         };
         // publish this wave's tiles of a [NG][MT] tensor in B-fragment order: X[q][tile][lane][4]
@@ -702,7 +703,7 @@ DEV void wave_tiles2(const GroupArgs& ga, int blk, int nblocks, int w, float* ld
                         vfloat4 z = b1;
                         PINN_UNROLL for (int i = 0; i < D; ++i)
                             PINN_UNROLL for (int r = 0; r < 4; ++r) z[r] = vfma(w1[i][r], x[pg][i], z[r]);
-                        if (!SINACT) z = act_value4<SINACT>(act, z);
+                        if (!RECZ) z = act_value4<ACLS>(act, z);
                         Rlast[pg * C][t] = z;
                         PINN_UNROLL for (int kf = 0; kf < NFIRST; ++kf) Rlast[pg * C + 1 + kf][t] = w1[S::first_axis(kf)];
                         PINN_UNROLL for (int ch = 1 + NFIRST; ch < C; ++ch) Rlast[pg * C + ch][t] = vzero4();
@@ -718,9 +719,9 @@ DEV void wave_tiles2(const GroupArgs& ga, int blk, int nblocks, int w, float* ld
                     PINN_UNROLL for (int r = 0; r < 4; ++r) {
                         vfloat zz[C], dd[ND];
                         PINN_UNROLL for (int k2 = 0; k2 < C; ++k2) zz[k2] = Rlast[pg * C + k2][t][r];
-                        act_derivs_n<J::NORD - 1, SINACT>(act, zz[0], dd);
+                        act_derivs_n<J::NORD - 1, ACLS>(act, zz[0], dd);
                         jet_forward<J>(zz, dd);
-                        A[pg * C][t][r] = act_from_record<SINACT>(Rlast[pg * C][t][r]);
+                        A[pg * C][t][r] = act_from_record<ACLS>(Rlast[pg * C][t][r]);
                         PINN_UNROLL for (int k2 = 1; k2 < C; ++k2) A[pg * C + k2][t][r] = zz[k2];
                     }
         }
@@ -887,10 +888,10 @@ DEV void wave_tiles2(const GroupArgs& ga, int blk, int nblocks, int w, float* ld
                 vfloat zz[C], dd[ND];
                 PINN_UNROLL for (int k = 0; k < C; ++k) zz[k] = Sr[pg * C + k][t][r];
                 if (ch > 0) {
-                    act_derivs_n<J::NORD - 1, SINACT>(act, zz[0], dd);
+                    act_derivs_n<J::NORD - 1, ACLS>(act, zz[0], dd);
                     jet_forward<J>(zz, dd);                 // (ch is a constant after unrolling: the other channels are dead code)
                 }
-                out[r] = (ch == 0) ? act_from_record<SINACT>(zz[0]) : zz[ch];
+                out[r] = (ch == 0) ? act_from_record<ACLS>(zz[0]) : zz[ch];
             }
             return out;
         };
@@ -900,7 +901,7 @@ DEV void wave_tiles2(const GroupArgs& ga, int blk, int nblocks, int w, float* ld
                     PINN_UNROLL for (int r = 0; r < 4; ++r) {
                         vfloat gg[C], ss[C], dd[ND];
                         PINN_UNROLL for (int k = 0; k < C; ++k) { gg[k] = G[pg * C + k][t][r]; ss[k] = Sr[pg * C + k][t][r]; }
-                        act_derivs_n<J::NORD, SINACT>(act, ss[0], dd);
+                        act_derivs_n<J::NORD, ACLS>(act, ss[0], dd);
                         jet_adjoint<J>(gg, ss, dd);
                         PINN_UNROLL for (int k = 0; k < C; ++k) G[pg * C + k][t][r] = gg[k];
                     }
@@ -918,7 +919,7 @@ DEV void wave_tiles2(const GroupArgs& ga, int blk, int nblocks, int w, float* ld
             const int pg = j >> 2, r = j & 3;
             vfloat gg[C], ss[C], dd[ND];
             PINN_UNROLL for (int k = 0; k < C; ++k) { gg[k] = G[pg * C + k][0][r]; ss[k] = Sr[pg * C + k][0][r]; }
-            act_derivs_n<J::NORD, SINACT>(act, ss[0], dd);
+            act_derivs_n<J::NORD, ACLS>(act, ss[0], dd);
             jet_adjoint<J>(gg, ss, dd);
             PINN_UNROLL for (int k = 0; k < C; ++k) G[pg * C + k][0][r] = gg[k];
         };
@@ -947,7 +948,7 @@ DEV void wave_tiles2(const GroupArgs& ga, int blk, int nblocks, int w, float* ld
                         vfloat4 z = b1;
                         PINN_UNROLL for (int i = 0; i < D; ++i)
                             PINN_UNROLL for (int r = 0; r < 4; ++r) z[r] = vfma(w1[i][r], x[pg][i], z[r]);
-                        if (!SINACT) z = act_value4<SINACT>(act, z);
+                        if (!RECZ) z = act_value4<ACLS>(act, z);
                         Sr[pg * C][t] = z;
                         PINN_UNROLL for (int kf = 0; kf < NFIRST; ++kf) Sr[pg * C + 1 + kf][t] = w1[S::first_axis(kf)];
                         PINN_UNROLL for (int ch = 1 + NFIRST; ch < C; ++ch) Sr[pg * C + ch][t] = vzero4();
@@ -977,10 +978,10 @@ DEV void wave_tiles2(const GroupArgs& ga, int blk, int nblocks, int w, float* ld
                             vfloat zz[C], dd[ND];
                             PINN_UNROLL for (int k = 0; k < C; ++k) zz[k] = Sr[pg * C + k][t][r];
                             if (C > 1) {
-                                act_derivs_n<J::NORD - 1, SINACT>(act, zz[0], dd);
+                                act_derivs_n<J::NORD - 1, ACLS>(act, zz[0], dd);
                                 jet_forward<J>(zz, dd);
                             }
-                            AJ[pg * C][t][r] = act_from_record<SINACT>(Sr[pg * C][t][r]);
+                            AJ[pg * C][t][r] = act_from_record<ACLS>(Sr[pg * C][t][r]);
                             PINN_UNROLL for (int k = 1; k < C; ++k) AJ[pg * C + k][t][r] = zz[k];
                         }
                 publish(XA, AJ);

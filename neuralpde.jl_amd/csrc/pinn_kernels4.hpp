@@ -37,7 +37,7 @@ struct F64Net {
                                                                                   // jets / dZ, H_l * C rows each (row = base + neuron * C + channel)
     int r_ubar;                         // seeds d(loss)/d(jet channel) of this network [C]
     int act_layers;                     // act == ACT_MIXED: kind (tanh / sigmoid) of hidden layer l in bits 4l .. 4l+3 (<= 8 hidden layers), as GroupArgs::act_layers
-    int act;                            // ACT_TANH / ACT_SIGMOID / ACT_SIN on every hidden layer, or ACT_MIXED
+    int act;                            // ACT_TANH / ACT_SIGMOID / ACT_SIN / ACT_SWISH on every hidden layer, or ACT_MIXED
     int theta0, nparams, ent0;          // the network's slice of theta; its first slab entry
     int tp0;                            // matrix-pipe kernels: first column of this network in a tile's row of partial sums (F64Args::tpart):
                                         // [W_0: n_1 * d][b_0: n_1][W_L: n_L][b_L]
@@ -116,10 +116,10 @@ HD int f64_nsq(const F64Args& a) { return a.nsub > 0 ? a.nsub : 1; }
 HD int f64_act(const F64Net& n, int l) { return n.act == ACT_MIXED ? ((n.act_layers >> (4 * l)) & 15) : n.act; }
 
 // ---- kernel A: forward jets of every network, residual tape, reverse sweep of ONE point ----
-template <class J, int ACTK /* ACT_TANH: tanh / sigmoid by run-time kind; ACT_SIN: sin */>
+template <class J, int ACTK /* ACT_TANH: tanh / sigmoid by run-time kind; ACT_SIN: sin; ACT_SWISH: swish */>
 DEV void f64_point(int lp, const F64Args& a) {
     constexpr int C = J::C;
-    constexpr bool SIN = (ACTK == ACT_SIN);
+    constexpr int ACLS = act_class(ACTK);
     constexpr int MB = (C <= 3) ? 8 : 4;                         // neurons per register block (MB * C accumulators in double)
     const int p = a.p0 + lp;
     double* S = a.scratch + lp;                                  // element `row` of this point: S[row * npad]
@@ -167,11 +167,11 @@ DEV void f64_point(int lp, const F64Args& a) {
                 PINN_UNROLL for (int j = 0; j < MB; ++j) {
                     if (j >= nb) break;
                     const int m = m0 + j;
-                    const double a0 = act_value<SIN>(f64_act(n, l), z[j][0]);
-                    z[j][0] = act_record<SIN>(z[j][0], a0);          // the record: a (tanh / sigmoid) or z (sin), then the pre-activation channels
+                    const double a0 = act_value<ACLS>(f64_act(n, l), z[j][0]);
+                    z[j][0] = act_record<ACLS>(z[j][0], a0);          // the record: a (tanh / sigmoid) or z (sin, swish), then the pre-activation channels
                     PINN_UNROLL for (int c = 0; c < C; ++c) S[((size_t)n.r_rec[l] + (size_t)m * C + c) * np_] = z[j][c];
                     double dd[ND];
-                    act_derivs_n<J::NORD - 1, SIN>(f64_act(n, l), z[j][0], dd);
+                    act_derivs_n<J::NORD - 1, ACLS>(f64_act(n, l), z[j][0], dd);
                     jet_forward<J>(z[j], dd);
                     z[j][0] = a0;
                     PINN_UNROLL for (int c = 0; c < C; ++c) S[((size_t)n.r_post[l] + (size_t)m * C + c) * np_] = z[j][c];
@@ -285,7 +285,7 @@ DEV void f64_point(int lp, const F64Args& a) {
                     const int k = k0 + j;
                     double s[C], dd[ND];
                     PINN_UNROLL for (int c = 0; c < C; ++c) s[c] = S[((size_t)n.r_rec[l] + (size_t)k * C + c) * np_];
-                    act_derivs_n<J::NORD, SIN>(f64_act(n, l), s[0], dd);
+                    act_derivs_n<J::NORD, ACLS>(f64_act(n, l), s[0], dd);
                     jet_adjoint<J>(gq[j], s, dd);
                     PINN_UNROLL for (int c = 0; c < C; ++c) S[((size_t)n.r_dz[l] + (size_t)k * C + c) * np_] = gq[j][c];
                 }
@@ -533,7 +533,7 @@ struct F64Kernel {
     unsigned D1MASK, HI;
     unsigned long long PAIRS;
     int first_ch[8];
-    void (*launch_point)(const F64Args&, bool sin_act, plat_stream);
+    void (*launch_point)(const F64Args&, int acls, plat_stream);       // acls: the ActClass every network of the term shares
 };
 std::deque<F64Kernel>& f64_registry();
 
@@ -606,11 +606,12 @@ inline void launch_f64_reduce(const F64ReduceArgs& a, plat_stream st) {
 #define PINN_LAUNCH_F64(J, ACT, a, st) hipLaunchKernelGGL((k_f64_point<J, ACT>), dim3((a.npts + 63) / 64), dim3(64), 0, st, a)
 #endif
 
-// tanh and sigmoid are a RUN-TIME kind per network here (the activation rules branch on it: no matrix pipe to keep fed); sin needs the other
-// record convention and is its own instantiation (every network of the equation then uses sin)
-template <class J> void launch_f64_point(const F64Args& a, bool sin_act, plat_stream st) {
+// tanh and sigmoid are a RUN-TIME kind per network here (the activation rules branch on it: no matrix pipe to keep fed); sin and swish need the other
+// record convention and are instantiations of their own (every network of the equation then uses that activation)
+template <class J> void launch_f64_point(const F64Args& a, int acls, plat_stream st) {
     (void)st;
-    if (sin_act) PINN_LAUNCH_F64(J, ACT_SIN, a, st);
+    if (acls == ACLS_Z_SIN) PINN_LAUNCH_F64(J, ACT_SIN, a, st);
+    else if (acls == ACLS_Z_SWISH) PINN_LAUNCH_F64(J, ACT_SWISH, a, st);
     else PINN_LAUNCH_F64(J, ACT_TANH, a, st);
 }
 template <int D, unsigned D1MASK, unsigned long long PAIRS, int NPAIR, unsigned HI> F64Kernel make_f64_kernel() {

@@ -80,7 +80,7 @@ static const pk::SpecInfo* ensure_spec_dgm(const Net& N, unsigned need_first, st
 
 const pk::SpecInfo* ensure_spec(const Net& N, unsigned need_first, const std::vector<std::pair<int, int>>& need_pairs, unsigned need_hi, int need_family) {
     if (N.kind == 1) return ensure_spec_dgm(N, need_first, need_pairs, need_hi);
-    ActScope as((N.act >= 0 && N.act < 4) ? N.act : -1);
+    ActScope as((N.act >= 0 && N.act < pk::NUM_ACTS) ? N.act : -1);
     const int HP = round_hp(N.maxhidden()), NHH = (int)N.sizes.size() - 3, D = N.sizes[0], variant = variant_of(N.act);
     if (need_hi & GEN_FLAG) {                    // general multi-index channel set: always generated (jit.cpp: jit_spec_gen)
         const pk::SpecInfo* g = find_spec(HP, NHH, D, 0, {}, need_hi, nullptr, variant, need_family);
@@ -322,10 +322,10 @@ static int plan_assign_terms(pinn_engine& E) {
         g_err = prev;
         if (!sp) {
             if (!why.empty() && why.find("PINN_NO_JIT") == std::string::npos) return fail("term " + std::to_string(t) + ": " + why);
-            char b[256];
+            char b[384];
             std::snprintf(b, sizeof b,
                           "term %zu: no compiled kernel for hidden width %d (padded %d), %d hidden layers, d=%d, first-derivative axes mask 0x%x, %zu second derivatives, higher-order mask 0x%x%s; add a PINN_INSTANTIATE line in csrc/inst_*.hip",
-                          t, N.maxhidden(), HP, LH, d, need_first, need_pairs.size(), need_hi, N.act == pk::ACT_SIN ? ", sin activation (PINN_INSTANTIATE*_SIN)" : (N.act == pk::ACT_MIXED ? ", per-layer tanh/sigmoid (PINN_INSTANTIATE_HI_MIX, family 1 only)" : ""));
+                          t, N.maxhidden(), HP, LH, d, need_first, need_pairs.size(), need_hi, N.act == pk::ACT_SIN ? ", sin activation (PINN_INSTANTIATE*_SIN)" : (N.act == pk::ACT_SWISH ? ", swish activation (PINN_INSTANTIATE*_SWISH)" : (N.act == pk::ACT_MIXED ? ", per-layer tanh/sigmoid (PINN_INSTANTIATE_HI_MIX, family 1 only)" : "")));
             return fail(b);
         }
         return 0;

@@ -122,7 +122,8 @@ void run_emu2m(const GroupArgs& ga, int blocks) {
 #endif
 
 // The activation kind is a template parameter of the kernels (ACTK): tanh and sigmoid variants for every spec; sin variants (sincos in
-// every jet rule) only for the specs registered with PINN_INSTANTIATE*_SIN.  The launch picks the variant from GroupArgs::act.
+// every jet rule), swish variants (z sigma(z), record = z) and per-layer tanh / sigmoid variants only for the specs registered with them
+// (PINN_INSTANTIATE*_SIN / _SWISH / _SIN_SWISH / _MIX: the VARIANTS mask, SpecInfo::has_sin).  The launch picks the variant from GroupArgs::act.
 template <class S, int ACTK>
 void launch_modes2(const GroupArgs& ga, int mode, int blocks, plat_stream st) {
     (void)st;
@@ -163,14 +164,17 @@ template <class S0, class S1> void launch_pair2(const GroupArgs& ga, int mode, i
         if (ga.act == ACT_TANH) PINN_LAUNCH2M(S0, S1, ACT_TANH, MODE_FUSED, ga, blocks, st); else PINN_LAUNCH2M(S0, S1, ACT_SIGMOID, MODE_FUSED, ga, blocks, st);
     }
 }
-template <class S> void launch_spec2_sin(const GroupArgs& ga, int mode, int blocks, plat_stream st) {
-    if (ga.act == ACT_SIN) launch_modes2<S, ACT_SIN>(ga, mode, blocks, st); else launch_spec2<S>(ga, mode, blocks, st);
+// VARIANTS: the extra kernel variants compiled for S (bits as SpecInfo::has_sin); a kind outside the mask is never planned onto S (plan.cpp)
+template <class S, int VARIANTS> void launch_spec2_var(const GroupArgs& ga, int mode, int blocks, plat_stream st) {
+    if constexpr ((VARIANTS & VARIANT_SIN) != 0) if (ga.act == ACT_SIN) return launch_modes2<S, ACT_SIN>(ga, mode, blocks, st);
+    if constexpr ((VARIANTS & VARIANT_SWISH) != 0) if (ga.act == ACT_SWISH) return launch_modes2<S, ACT_SWISH>(ga, mode, blocks, st);
+    launch_spec2<S>(ga, mode, blocks, st);
 }
-template <class S> void launch_spec_sin(const GroupArgs& ga, int mode, int blocks, plat_stream st) {
-    if (ga.act == ACT_SIN) launch_modes1<S, ACT_SIN>(ga, mode, blocks, st); else launch_spec<S>(ga, mode, blocks, st);
-}
-template <class S> void launch_spec_mix(const GroupArgs& ga, int mode, int blocks, plat_stream st) {
-    if (ga.act == ACT_MIXED) launch_modes1<S, ACT_MIXED>(ga, mode, blocks, st); else launch_spec<S>(ga, mode, blocks, st);
+template <class S, int VARIANTS> void launch_spec_var(const GroupArgs& ga, int mode, int blocks, plat_stream st) {
+    if constexpr ((VARIANTS & VARIANT_SIN) != 0) if (ga.act == ACT_SIN) return launch_modes1<S, ACT_SIN>(ga, mode, blocks, st);
+    if constexpr ((VARIANTS & VARIANT_MIXED) != 0) if (ga.act == ACT_MIXED) return launch_modes1<S, ACT_MIXED>(ga, mode, blocks, st);
+    if constexpr ((VARIANTS & VARIANT_SWISH) != 0) if (ga.act == ACT_SWISH) return launch_modes1<S, ACT_SWISH>(ga, mode, blocks, st);
+    launch_spec<S>(ga, mode, blocks, st);
 }
 
 
@@ -263,7 +267,9 @@ PairInfo make_pair_info() {
 #define PINN_TRAIN_OF(S) nullptr
 #endif
 template <class S> struct Launch2Plain { static void fn(const GroupArgs& ga, int mode, int blocks, plat_stream st) { launch_spec2<S>(ga, mode, blocks, st); } };
-template <class S> struct Launch2Sin { static void fn(const GroupArgs& ga, int mode, int blocks, plat_stream st) { launch_spec2_sin<S>(ga, mode, blocks, st); } };
+template <class S> struct Launch2Sin { static void fn(const GroupArgs& ga, int mode, int blocks, plat_stream st) { launch_spec2_var<S, VARIANT_SIN>(ga, mode, blocks, st); } };
+template <class S> struct Launch2Swish { static void fn(const GroupArgs& ga, int mode, int blocks, plat_stream st) { launch_spec2_var<S, VARIANT_SWISH>(ga, mode, blocks, st); } };
+template <class S> struct Launch2SinSwish { static void fn(const GroupArgs& ga, int mode, int blocks, plat_stream st) { launch_spec2_var<S, VARIANT_SIN | VARIANT_SWISH>(ga, mode, blocks, st); } };
 template <class S, template <class> class L, bool ENABLE> struct Registrar2 {
     explicit Registrar2(int has_sin) { registry().push_back(make_info2<S>(&L<S>::fn, has_sin)); }
 };
@@ -285,19 +291,21 @@ template <class S0, class S1> struct PairRegistrar2<S0, S1, false> { PairRegistr
     using NAME##_spec = pk::Spec<HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI>;                  \
     pk::Registrar NAME##_reg(pk::make_info<NAME##_spec>(&pk::launch_spec<NAME##_spec>, 0, PINN_TRAIN_OF(NAME##_spec))); \
     }
-// the same with the sin-activation kernels compiled in as well
-#define PINN_INSTANTIATE2_HI_SIN(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI) PINN_INSTANTIATE2_ANY(NAME, Launch2Sin, 1, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)
-#define PINN_INSTANTIATE_HI_SIN(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)              \
+// family 1 spec with extra kernel variants compiled in as well (VARIANTS: bits as SpecInfo::has_sin)
+#define PINN_INSTANTIATE_HI_VAR(NAME, VARIANTS, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)    \
     namespace {                                                                              \
     using NAME##_spec = pk::Spec<HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI>;                  \
-    pk::Registrar NAME##_reg(pk::make_info<NAME##_spec>(&pk::launch_spec_sin<NAME##_spec>, 1, PINN_TRAIN_OF(NAME##_spec))); \
+    pk::Registrar NAME##_reg(pk::make_info<NAME##_spec>(&pk::launch_spec_var<NAME##_spec, (VARIANTS)>, (VARIANTS), PINN_TRAIN_OF(NAME##_spec))); \
     }
+// the sin-activation kernels; the swish kernels; both
+#define PINN_INSTANTIATE2_HI_SIN(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI) PINN_INSTANTIATE2_ANY(NAME, Launch2Sin, pk::VARIANT_SIN, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)
+#define PINN_INSTANTIATE2_HI_SWISH(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI) PINN_INSTANTIATE2_ANY(NAME, Launch2Swish, pk::VARIANT_SWISH, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)
+#define PINN_INSTANTIATE2_HI_SIN_SWISH(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI) PINN_INSTANTIATE2_ANY(NAME, Launch2SinSwish, pk::VARIANT_SIN | pk::VARIANT_SWISH, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)
+#define PINN_INSTANTIATE_HI_SIN(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI) PINN_INSTANTIATE_HI_VAR(NAME, pk::VARIANT_SIN, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)
+#define PINN_INSTANTIATE_HI_SWISH(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI) PINN_INSTANTIATE_HI_VAR(NAME, pk::VARIANT_SWISH, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)
+#define PINN_INSTANTIATE_HI_SIN_SWISH(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI) PINN_INSTANTIATE_HI_VAR(NAME, pk::VARIANT_SIN | pk::VARIANT_SWISH, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)
 // family 1 spec that also carries the per-layer tanh / sigmoid variant (small nets such as the reference's Dense(1, 8, tanh), Dense(8, 8, sigma))
-#define PINN_INSTANTIATE_HI_MIX(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)                  \
-    namespace {                                                                              \
-    using NAME##_spec = pk::Spec<HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI>;                  \
-    pk::Registrar NAME##_reg(pk::make_info<NAME##_spec>(&pk::launch_spec_mix<NAME##_spec>, 2, PINN_TRAIN_OF(NAME##_spec))); \
-    }
+#define PINN_INSTANTIATE_HI_MIX(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI) PINN_INSTANTIATE_HI_VAR(NAME, pk::VARIANT_MIXED, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)
 // DGM network (family 3): modes padded to MP, L gated layers, D inputs, jet set, gate activation ACT1, output-gate activation ACT2
 #define PINN_INSTANTIATE_DGM(NAME, MP, L, D, D1MASK, PAIRS, NPAIR, HI, ACT1, ACT2)           \
     namespace pk {                                                                           \

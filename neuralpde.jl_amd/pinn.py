@@ -48,7 +48,7 @@ class PeriodicEmbedding:
 
 class Chain:
     """Lux.Chain of Dense layers, optionally behind a PeriodicEmbedding.  The engine supports the shape every PINN chain in the
-    reference's PDE tests has: tanh / sigmoid (per layer) or sin (all layers) on the hidden layers, identity on the last, single output."""
+    reference's PDE tests has: tanh / sigmoid (per layer), sin or swish (all layers) on the hidden layers, identity on the last, single output."""
 
     def __init__(self, *layers):
         self.embed = ()
@@ -81,7 +81,7 @@ class Chain:
             self.act = acts[0]
         else:
             # per-layer activations (e.g. the reference's Dense(1, n, tanh), Dense(n, n, σ), Dense(n, 1)): tanh and sigmoid may be
-            # mixed (kernel variant ACT_MIXED, compiled for the small-net shapes); sin has kernels of its own and cannot be mixed
+            # mixed (kernel variant ACT_MIXED, compiled for the small-net shapes); sin and swish have kernels of their own and cannot be mixed
             if not set(acts) <= {"tanh", "sigmoid"}:
                 raise ValueError("the HIP engine mixes only tanh and sigmoid inside one chain (got " + ", ".join(acts) + ")")
             self.act = ",".join(acts)
