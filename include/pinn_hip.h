@@ -46,6 +46,24 @@ const char* pinn_last_error(void);
  * per term: dimension, jet slots, residual tape <- symbolic_pde/bc_loss_functions   (src/discretize.jl:505-525)
  * Replaces: build_loss_function + RuntimeGeneratedFunction (src/discretize.jl:163-175).
  * Unsupported expressions / network shapes fail HERE (never a silent fallback).
+ *
+ * INTEGRAL TERMS ("pinnir 1" extension; the reference's `Integral(s in ClosedInterval(lo, hi))(f)`, src/discretize.jl:355-396).  A term whose
+ * residual holds integral nodes I(x) = int_lo^hi f(s; x, u, du, p) ds carries them between its `term` line and its own `slot` lines:
+ *     term <k> <d> <#slots> <#ops> <out row>
+ *     integrals <NI>                                        1 <= NI <= 4
+ *     integral <var> <lo> <hi> <#slots> <#ops> <out row>    NI blocks; <var>: coordinate index of the integration variable; <lo>, <hi>: a finite
+ *     slot ... / op ...                                       number, or x<i> = coordinate i of the collocation point (x<var> gives the reference's 0..t)
+ *     slot ... / op ...                                     the term's own slots and ops
+ * Rows of the term's tape: [coordinates | parameters | slots | integral nodes | ops] — node j is row d + np + #slots + j, read like a jet slot.
+ * Rows of a node's tape (the integrand): [coordinates, row <var> holding the quadrature abscissa | parameters | the node's slots | its ops]; its
+ * slots are evaluated at the substituted point.  The node is evaluated as a Q-node Gauss-Legendre rule on [lo, hi],
+ * (hi - lo)/2 * sum_q w_q f(lo + (hi - lo)(xi_q + 1)/2), Q = option "integral_nodes"; nodes and weights are computed in double by the library.
+ * Refused at pinn_create with the limit named: bounds that are not a finite number or a coordinate, integrands without a dependent variable,
+ * lap slots / DATA ops inside a node, integral terms that reference several networks, a DGM network or a periodically embedded network.
+ * "pinnir 2": the node is the list `(integral <var> <lo> <hi> <body>)` inside lhs / rhs — <var> an independent variable of the term, <lo> / <hi> a
+ * number or an independent variable, <body> any expression of the form's grammar holding a dependent variable — lowered to the same nodes;
+ * nested integrals, a list in place of <var> (multi-variable), Inf bounds, bounds that are expressions and bodies without a dependent
+ * variable are refused by name.  A term with integral nodes may list a slot only once per node and once among its own slots.
  */
 int pinn_create(const char* descriptor, pinn_handle* out);          /* on the caller's current HIP device */
 int pinn_create_on(const char* descriptor, int device, pinn_handle* out);   /* on HIP device `device` (single process, several GPUs) */
@@ -317,6 +335,12 @@ int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int histor
  *   (julia: NeuralPDEHIP.selftest) and with the stencil oracle.  How close two correct implementations of these formulas can be is bounded by the
  *   formulas themselves: u(x +- eps) carries ~1e-16 relative rounding and 1 / eps^2 ~ 7e7 multiplies it — 1e-8 at initialisation, 1e-5 ... 1e-4
  *   of the gradient at trained parameters (tests/test_f64_mode.py measures it as the stencil oracle against itself with permuted neurons).
+ * "integral_nodes" = "2" ... "64" (default "16"): Gauss-Legendre nodes per integral node of the handle's integral terms (fp32 kernels only:
+ *   "precision" = "f64" is refused on a handle with integral terms, and the refusal names "f32").  Setting it on a live handle RE-PLANS the
+ *   integral terms: their installed point sets, samplers and the optimiser state stay, the site sets (every point plus Q abscissae per
+ *   integral node) are rebuilt for the new rule; site buffers that have room are kept, larger ones are allocated BEFORE anything changes.  A value
+ *   outside the range, one whose site set exceeds 32-bit indexing, or a failed site-buffer allocation is refused and the handle stays as it was
+ *   (a failure later, in the per-term jet buffers, reports the error and leaves the handle to be destroyed).  pinn_describe marks the launch groups of such terms `+integral(Q)`.
  * "persistent" = "on" (default) | "off": pinn_adam_steps runs a SMALL problem — one network of the one-wave-per-tile kernel family, at most
  *   32 workgroups (~2,000 points of a 3 x 32 net), fixed or device-redrawn point sets (pinn_set_sampler), no estimated PDE parameters, no communicator — as ONE persistent launch
  *   per call (csrc/pinn_train.hpp: evaluation, fixed-order reduction, Adam and the weight-image update of every iteration inside the kernel,

@@ -332,6 +332,8 @@ strings are committed under tests/golden/descriptors/ and exercised by tests/tes
     cfg3 (Burgers)      lhs (+ (D t 1 (u t x)) (* (u t x) (D x 1 (u t x))) (* -0.01 (/ 1 pi) (D x 2 (u t x))))   rhs 0
     cfg5 (heat, κ est.) lhs (D t 1 (u t x y z))     rhs (* kappa (+ (D x 2 (u t x y z)) (D y 2 (u t x y z)) (D z 2 (u t x y z))))
     boundary terms      lhs (u 0 y)   rhs 0          (call arguments are dropped by the lowering, symbolic_utilities.jl:145-160)
+    integral terms      lhs (+ (D t 1 (i t)) (* 2 (i t)) (* 5 (integral t 0 t (i t))))   rhs 1      (`Integral(t in ClosedInterval(0, t))(i(t))`:
+                        variable, lower and upper bound — numbers or independent variables —, integrand)
 """
 sexpr(x::Irrational{:π}) = "pi"
 sexpr(x::Irrational{:ℯ}) = string(Float64(x))
@@ -348,6 +350,16 @@ function sexpr(ex::Expr)
         length(args) == 1 || throw(HIPEngineError("Differential with $(length(args)) operands"))
         order = hasproperty(f, :order) ? Int(f.order) : 1
         return string("(D ", sexpr(toexpr(f.x)), " ", order, " ", sexpr(args[1]), ")")
+    end
+    if f isa Symbolics.Integral
+        # `Integral(t in ClosedInterval(0, t))(i(t))`: the head carries the domain (the reference reads `domain.variables` and the
+        # interval's end points the same way, src/discretize.jl:355-396); the library evaluates it with its fixed Gauss-Legendre rule
+        length(args) == 1 || throw(HIPEngineError("Integral with $(length(args)) operands"))
+        vars = f.domain.variables
+        (vars isa Tuple || vars isa AbstractVector) && throw(HIPEngineError(
+            "multi-variable integrals (ProductDomain) are not supported by the HIP engine: an integral term runs over ONE independent variable"))
+        dom = f.domain.domain
+        return string("(integral ", sexpr(vars), " ", sexpr(minimum(dom)), " ", sexpr(maximum(dom)), " ", sexpr(args[1]), ")")
     end
     name = f isa Symbol ? string(f) : string(nameof(f))
     name == "σ" && (name = "sigmoid")

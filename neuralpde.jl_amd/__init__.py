@@ -26,7 +26,7 @@ from .pinn import (PeriodicEmbedding, DGM, DeepGalerkin, DataLoss, depvar_params
 from .strategies import (AbstractTrainingStrategy, QuadratureTraining, GridTraining, LatinHypercubeSample, QuasiRandomTraining,
                          SobolSample, StochasticTraining, generate_random_points, generate_training_sets, get_bounds,
                          get_loss_function, merge_strategy_with_loss_function)
-from .symbolic import (Differential, Eq, Equation, In, Interval, LoweringError, PDESystem, get_argument, get_variables,
-                       get_vars, lower_equation, parameters, variables)
+from .symbolic import (Differential, Eq, Equation, In, Integral, Interval, LoweringError, PDESystem, ProductDomain, get_argument,
+                       get_variables, get_vars, lower_equation, parameters, variables)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

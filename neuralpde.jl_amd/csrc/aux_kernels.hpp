@@ -9,6 +9,7 @@
 #pragma once
 #include <cstdlib>
 #include "aux_limits.hpp"
+#include "int_limits.hpp"
 #include "plat.hpp"
 #include "rprog.hpp"
 #include "update_rules.hpp"
@@ -125,6 +126,156 @@ AUX_DEV float expr_point(int p, const ExprArgs& a, float (&pb)[4]) {
     for (int s = 0; s < a.nslots; ++s) a.ubar[s][p] = rbar * g[a.d + a.nparams + s];
     for (int z = 0; z < a.nzero; ++z) a.zero[z][p] = 0.f;
     for (int j = 0; j < a.nparams_estim; ++j) pb[j] = rbar * g[a.d + j];
+    return rs;
+}
+
+// ---- integral terms: I(x) = int_lo^hi f(s; x, u, du, p) ds as a Q-node Gauss-Legendre rule ----
+// The term's SITE SET is [S][N][d] with S = 1 + nnodes Q: block 0 the collocation points themselves, block 1 + k Q + q the points with
+// the integration variable of node k moved to quadrature node q of ITS interval [lo, hi] (each bound a constant or a coordinate of the
+// point).  k_int_sites builds blocks 1.. from block 0 whenever the point set changes; the network kernels run on all S N sites
+// (forward-with-records, then the seeded reverse launch) and k_int_expr sits between them, one thread per collocation point.
+struct IntNodeDev {
+    int var, lo_row, hi_row;              // bound rows >= 0: that coordinate of the collocation point; < 0: the constant below
+    float lo, hi;
+    double lo64, hi64;
+    int slot0, nslots;                    // its slots: entries [slot0, slot0 + nslots) of IntExprArgs::chan
+    int prog_off, nops, out_row;          // its tape in IntExprArgs::iprog, rows [coords | params | its slots | ops]
+};
+struct IntSitesArgs {
+    float* sites;                         // [S][N][d]; block 0 is read, blocks 1.. are written
+    int N, d, nnodes, Q;
+    const double* xi;                     // [Q] Gauss-Legendre nodes on [-1, 1]
+    IntNodeDev node[INT_MAX_NODES];
+};
+// site (k, q) of point p: the abscissa lo + (hi - lo)(xi_q + 1)/2 is formed in double and narrowed once
+AUX_DEV void int_site_body(int e, const IntSitesArgs& a) {
+    const int per = a.nnodes * a.Q;
+    if (e >= a.N * per) return;
+    const int p = e % a.N, j = e / a.N;                  // consecutive threads: consecutive points of one site block
+    const int k = j / a.Q, q = j % a.Q;
+    const IntNodeDev nd = a.node[k];
+    const float* x = a.sites + (size_t)p * a.d;
+    const double lo = nd.lo_row >= 0 ? (double)x[nd.lo_row] : nd.lo64;
+    const double hi = nd.hi_row >= 0 ? (double)x[nd.hi_row] : nd.hi64;
+    const float s = (float)(lo + (hi - lo) * (0.5 * (a.xi[q] + 1.0)));
+    float* y = a.sites + ((size_t)(1 + j) * a.N + p) * a.d;
+    for (int i = 0; i < a.d; ++i) y[i] = (i == nd.var) ? s : x[i];
+}
+
+struct IntExprArgs {
+    const float* sites;                   // [S][N][d]
+    int N, d, nparams, nparams_estim;
+    const float* params;
+    const float* jets;                    // [C][S N]: the forward launch's channels over the site set
+    float* ubar;                          // [C][S N]: d(loss)/d(jet), EVERY element written (zero where the term does not read the channel)
+    int C;
+    int n_outer, nnodes, Q;
+    int chan[EXPR_MAX_SLOTS];             // slot -> jet channel: the outer slots first, then the nodes'
+    int outer_slot_of_chan[INT_MAX_C];    // channel -> outer slot reading it at the point itself, -1: none
+    int node_slot_of_chan[INT_MAX_NODES][INT_MAX_C];      // channel -> slot of node k reading it at the node's sites (index into chan), -1: none
+    IntNodeDev node[INT_MAX_NODES];
+    const float* w;                       // [Q] Gauss-Legendre weights on [-1, 1]
+    const rp::Instr* prog;                // outer tape: rows [coords | params | outer slots | integral nodes | ops]
+    const rp::Instr* iprog;               // the nodes' tapes
+    int nops, out_row;
+    float scale;                          // 2 w / N_norm
+    double* losspart;                     // [nblocks*4][K]
+    float* pslab;                         // [nblocks][4 waves][4 params]
+    int K, term_id;
+    float* resid;                         // nullable: write r[N] and skip the adjoint
+    int loss_only;
+    const float* data;                    // [ndata][N] (OP_DATA of the outer tape), nullable
+    const float* pw;                      // per-point factors sqrt(N w_i), nullable
+};
+// integrand of node `nd` at site block `site` of point p: forward tape into v, returns f
+AUX_DEV float int_integrand(int p, int site, const IntNodeDev& nd, const IntExprArgs& a, float (&v)[EXPR_MAX_ROWS]) {
+    const size_t sp = (size_t)site * a.N + p, SN = (size_t)(1 + a.nnodes * a.Q) * a.N;
+    const int R0 = a.d + a.nparams + nd.nslots;
+    for (int i = 0; i < a.d; ++i) v[i] = a.sites[sp * a.d + i];
+    for (int j = 0; j < a.nparams; ++j) v[a.d + j] = a.params[j];
+    for (int s = 0; s < nd.nslots; ++s) v[a.d + a.nparams + s] = a.jets[(size_t)a.chan[nd.slot0 + s] * SN + sp];
+    for (int q = 0; q < nd.nops; ++q) {
+        const rp::Instr ins = a.iprog[nd.prog_off + q];
+        const float va = rp::is_nullary(ins.code) ? 0.f : v[ins.a];
+        const float vb = rp::is_binary(ins.code) ? v[ins.b] : 0.f;
+        v[R0 + q] = rp::apply<float>(ins.code, va, vb, ins.imm);
+    }
+    return v[nd.out_row];
+}
+// one collocation point: the nodes' weighted sums in the fixed order q = 0 .. Q-1 (double accumulator), the outer tape, its adjoint, the
+// adjoint of every node's integrand at every site; returns r (times the point factor), writes ubar for all S sites and dL/dp into pb[]
+AUX_DEV float int_expr_point(int p, const IntExprArgs& a, float (&pb)[4]) {
+    float v[EXPR_MAX_ROWS], g[EXPR_MAX_ROWS], vi[EXPR_MAX_ROWS], gi[EXPR_MAX_ROWS];
+    float half[INT_MAX_NODES];
+    const size_t SN = (size_t)(1 + a.nnodes * a.Q) * a.N;
+    const int RI = a.d + a.nparams + a.n_outer, R0 = RI + a.nnodes;
+    for (int i = 0; i < a.d; ++i) v[i] = a.sites[(size_t)p * a.d + i];
+    for (int j = 0; j < a.nparams; ++j) v[a.d + j] = a.params[j];
+    for (int s = 0; s < a.n_outer; ++s) v[a.d + a.nparams + s] = a.jets[(size_t)a.chan[s] * SN + p];
+    for (int k = 0; k < a.nnodes; ++k) {
+        const IntNodeDev nd = a.node[k];
+        const float lo = nd.lo_row >= 0 ? v[nd.lo_row] : nd.lo, hi = nd.hi_row >= 0 ? v[nd.hi_row] : nd.hi;
+        half[k] = 0.5f * (hi - lo);
+        double acc = 0.0;
+        for (int q = 0; q < a.Q; ++q) acc += (double)a.w[q] * (double)int_integrand(p, 1 + k * a.Q + q, nd, a, vi);
+        v[RI + k] = (float)((double)half[k] * acc);
+    }
+    for (int q = 0; q < a.nops; ++q) {
+        const rp::Instr ins = a.prog[q];
+        const float va = rp::is_nullary(ins.code) ? 0.f : v[ins.a];
+        const float vb = rp::is_binary(ins.code) ? v[ins.b] : 0.f;
+        v[R0 + q] = (ins.code == rp::OP_DATA) ? a.data[(size_t)(int)ins.imm * a.N + p] : rp::apply<float>(ins.code, va, vb, ins.imm);
+    }
+    const float r = v[a.out_row];
+    for (int j = 0; j < 4; ++j) pb[j] = 0.f;
+    if (a.resid) { a.resid[p] = r; return r; }
+    if (a.loss_only) return r * (a.pw ? a.pw[p] : 1.0f);
+    for (int q = 0; q < R0 + a.nops; ++q) g[q] = 0.f;
+    g[a.out_row] = 1.0f;
+    for (int q = a.nops - 1; q >= 0; --q) {
+        const rp::Instr ins = a.prog[q];
+        if (rp::is_nullary(ins.code)) continue;
+        const float vb = rp::is_binary(ins.code) ? v[ins.b] : 0.f;
+        float da, db;
+        rp::adjoint<float>(ins.code, v[ins.a], vb, v[R0 + q], ins.imm, g[R0 + q], da, db);
+        g[ins.a] += da;
+        if (rp::is_binary(ins.code)) g[ins.b] += db;
+    }
+    const float sw = a.pw ? a.pw[p] : 1.0f;
+    const float rs = r * sw;
+    const float rbar = rs * a.scale * sw;
+    for (int c = 0; c < a.C; ++c) {                      // the point itself: site block 0
+        const int s = a.outer_slot_of_chan[c];
+        a.ubar[(size_t)c * SN + p] = s >= 0 ? rbar * g[a.d + a.nparams + s] : 0.f;
+    }
+    for (int j = 0; j < a.nparams_estim; ++j) pb[j] = rbar * g[a.d + j];
+    for (int k = 0; k < a.nnodes; ++k) {
+        const IntNodeDev nd = a.node[k];
+        const float ibar = rbar * g[RI + k] * half[k];    // d(loss)/d(sum_q w_q f_q)
+        const int Ri = a.d + a.nparams + nd.nslots;
+        for (int q = 0; q < a.Q; ++q) {
+            const int site = 1 + k * a.Q + q;
+            int_integrand(p, site, nd, a, vi);
+            for (int t = 0; t < Ri + nd.nops; ++t) gi[t] = 0.f;
+            gi[nd.out_row] = 1.0f;
+            for (int t = nd.nops - 1; t >= 0; --t) {
+                const rp::Instr ins = a.iprog[nd.prog_off + t];
+                if (rp::is_nullary(ins.code)) continue;
+                const float vb = rp::is_binary(ins.code) ? vi[ins.b] : 0.f;
+                float da, db;
+                rp::adjoint<float>(ins.code, vi[ins.a], vb, vi[Ri + t], ins.imm, gi[Ri + t], da, db);
+                gi[ins.a] += da;
+                if (rp::is_binary(ins.code)) gi[ins.b] += db;
+            }
+            const float fbar = ibar * a.w[q];
+            const size_t sp = (size_t)site * a.N + p;
+            for (int c = 0; c < a.C; ++c) {
+                const int s = a.node_slot_of_chan[k][c];
+                a.ubar[(size_t)c * SN + sp] = s >= 0 ? fbar * gi[a.d + a.nparams + (s - nd.slot0)] : 0.f;
+            }
+            for (int j = 0; j < a.nparams_estim; ++j) pb[j] += fbar * gi[a.d + j];
+        }
+    }
     return rs;
 }
 
@@ -459,6 +610,28 @@ inline void launch_expr(const ExprArgs& a, int nblocks, plat_stream) {
             }
         }
 }
+inline void launch_int_sites(const IntSitesArgs& a, plat_stream) {
+    for (int e = 0; e < a.N * a.nnodes * a.Q; ++e) int_site_body(e, a);
+}
+inline void launch_int_expr(const IntExprArgs& a, int nblocks, plat_stream) {
+    for (int b = 0; b < nblocks; ++b)
+        for (int w = 0; w < 4; ++w) {
+            double ls = 0.0;
+            double ps[4] = {0, 0, 0, 0};
+            for (int l = 0; l < 64; ++l) {
+                const int p = (b * 4 + w) * 64 + l;
+                if (p >= a.N) continue;
+                float pb[4];
+                const float r = int_expr_point(p, a, pb);
+                ls += (double)r * (double)r;
+                for (int j = 0; j < 4; ++j) ps[j] += (double)pb[j];
+            }
+            if (!a.resid) {
+                a.losspart[(size_t)(b * 4 + w) * a.K + a.term_id] = ls;
+                for (int j = 0; j < 4; ++j) a.pslab[(size_t)(b * 4 + w) * 4 + j] = (float)ps[j];
+            }
+        }
+}
 inline void launch_reduce_one(const ReduceOneArgs& a, plat_stream) {
     for (int e4 = 0; e4 < a.nent / 4; ++e4) {
         double tot[4] = {0, 0, 0, 0}, s[4];
@@ -632,6 +805,32 @@ inline void launch_src(const SrcArgs& a, plat_stream st) {
 }
 inline void launch_expr(const ExprArgs& a, int nblocks, plat_stream st) {
     hipLaunchKernelGGL(k_expr, dim3(nblocks), dim3(256), 0, st, a);
+}
+__global__ void __launch_bounds__(256) k_int_sites(const IntSitesArgs a) { int_site_body((int)(blockIdx.x * 256 + threadIdx.x), a); }
+inline void launch_int_sites(const IntSitesArgs& a, plat_stream st) {
+    hipLaunchKernelGGL(k_int_sites, dim3((a.N * a.nnodes * a.Q + 255) / 256), dim3(256), 0, st, a);
+}
+// the tail kernel of an integral term: as k_expr, per-wave fixed-order sums of the loss and dL/dp
+__global__ void __launch_bounds__(256) k_int_expr(const IntExprArgs a) {
+    __shared__ double sh[5][256];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    float pb[4] = {0.f, 0.f, 0.f, 0.f};
+    float r = 0.f;
+    if (p < a.N) r = int_expr_point(p, a, pb);
+    if (a.resid) return;
+    sh[0][threadIdx.x] = (double)r * (double)r;
+    for (int j = 0; j < 4; ++j) sh[1 + j][threadIdx.x] = (double)pb[j];
+    __syncthreads();
+    if (threadIdx.x < 20) {
+        const int w = threadIdx.x & 3, q = threadIdx.x >> 2;
+        double s = 0.0;
+        for (int l = 0; l < 64; ++l) s += sh[q][w * 64 + l];
+        if (q == 0) a.losspart[(size_t)(blockIdx.x * 4 + w) * a.K + a.term_id] = s;
+        else a.pslab[(size_t)(blockIdx.x * 4 + w) * 4 + (q - 1)] = (float)s;
+    }
+}
+inline void launch_int_expr(const IntExprArgs& a, int nblocks, plat_stream st) {
+    hipLaunchKernelGGL(k_int_expr, dim3(nblocks), dim3(256), 0, st, a);
 }
 __global__ void __launch_bounds__(256) k_reduce_one(const ReduceOneArgs a) {
     __shared__ double sh[RONE_CHUNKS][RONE_ENT + 1];

@@ -150,9 +150,7 @@ int parse_descriptor(const char* text, pinn_engine& E) {
             continue;
         }
         if (tok != "term" || !(in >> id >> T.d >> ns >> no >> T.out_row) || id != i) return fail("descriptor: term line");
-        T.slots.resize(ns);
-        for (int s = 0; s < ns; ++s) {
-            Slot& S = T.slots[s];
+        auto parse_slot = [&](Slot& S) -> int {
             std::string ord;
             if (!expect("slot") || !(in >> S.net >> ord)) return fail("descriptor: slot line");
             if (S.net < 0 || S.net >= nn) return fail("descriptor: slot net id");
@@ -165,7 +163,7 @@ int parse_descriptor(const char* text, pinn_engine& E) {
                     if (!(in >> ax) || ax < 0 || ax > 7) return fail("descriptor: lap slot axes");
                     S.lap |= 1u << ax;
                 }
-                continue;
+                return 0;
             }
             S.order = std::atoi(ord.c_str());
             if (ord.empty() || ord.find_first_not_of("0123456789") != std::string::npos) return fail("descriptor: slot order");
@@ -173,30 +171,107 @@ int parse_descriptor(const char* text, pinn_engine& E) {
             for (int a = 0; a < S.order; ++a)
                 if (!(in >> S.axes[a])) return fail("descriptor: slot axes");
             std::sort(S.axes, S.axes + S.order);
-        }
-        T.ops.resize(no);
-        T.imm64.clear();
-        for (int q = 0; q < no; ++q) {
+            return 0;
+        };
+        auto parse_op = [&](rp::Instr& I, int lim, double& immd) -> int {      // operands may only reference rows below `lim`
             std::string name;
-            rp::Instr& I = T.ops[q];
-            double immd = 0.0;
             if (!expect("op") || !(in >> name >> I.a >> I.b >> immd)) return fail("descriptor: op line");
             I.imm = (float)immd;
-            T.imm64.push_back(immd);
             I.code = -1;
             for (int c = 0; c < rp::OP_COUNT; ++c)
                 if (name == OPNAMES[c]) I.code = c;
             if (I.code < 0) return fail("descriptor: unknown op '" + name + "'");
-            const int lim = T.d + E.np + ns + q;          // operands may only reference earlier rows
             if (!rp::is_nullary(I.code) && (I.a < 0 || I.a >= lim)) return fail("descriptor: op operand row out of range");
             if (rp::is_binary(I.code) && (I.b < 0 || I.b >= lim)) return fail("descriptor: op operand row out of range");
             rp::finalize(I);
+            return 0;
+        };
+        // optional: integrals <NI>, then per node  integral <var> <lo> <hi> <#slots> <#ops> <out row>  + its slot and op lines (pinn_hip.h)
+        std::vector<Slot> inner_slots;
+        {
+            const std::streampos pos = in.tellg();
+            std::string t2;
+            if ((in >> t2) && t2 == "integrals") {
+                int ni = 0;
+                if (!(in >> ni) || ni < 1 || ni > aux::INT_MAX_NODES)
+                    return fail("descriptor: integrals line (1.." + std::to_string(aux::INT_MAX_NODES) + " integral nodes per term)");
+                T.inodes.resize(ni);
+                for (int k = 0; k < ni; ++k) {
+                    IntNode& Nd = T.inodes[k];
+                    std::string lo, hi;
+                    int ins = 0, ino = 0;
+                    if (!expect("integral") || !(in >> Nd.var >> lo >> hi >> ins >> ino >> Nd.out_row))
+                        return fail("descriptor: integral line (integral <var> <lo> <hi> <#slots> <#ops> <out row>)");
+                    if (Nd.var < 0 || Nd.var >= T.d) return fail("descriptor: integral variable is not a coordinate of the term");
+                    auto bound = [&](const std::string& b, int& row, double& val) -> int {
+                        if (b.size() >= 2 && b[0] == 'x' && b.find_first_not_of("0123456789", 1) == std::string::npos) {
+                            row = std::atoi(b.c_str() + 1);
+                            return (row >= 0 && row < T.d) ? 0 : fail("descriptor: integral bound names a coordinate the term does not have");
+                        }
+                        char* end = nullptr;
+                        val = std::strtod(b.c_str(), &end);
+                        if (b.empty() || *end) return fail("descriptor: integral bound '" + b + "' is neither a number nor a coordinate x<i> (a bound that is a general expression is not supported)");
+                        if (!std::isfinite(val)) return fail("descriptor: infinite integral bounds are not supported (bounds must be finite)");
+                        return 0;
+                    };
+                    if (bound(lo, Nd.lo_row, Nd.lo) || bound(hi, Nd.hi_row, Nd.hi)) return 1;
+                    if (ins < 1 || ins > aux::EXPR_MAX_SLOTS) return fail("descriptor: an integral node needs 1.." + std::to_string(aux::EXPR_MAX_SLOTS) + " slots (the integrand must contain a dependent variable)");
+                    if (ino < 1) return fail("descriptor: an integral node needs at least one op");
+                    Nd.slot0 = (int)inner_slots.size();
+                    Nd.nslots = ins;
+                    for (int s = 0; s < ins; ++s) {
+                        Slot S;
+                        S.net = 0; S.order = 0; S.lap = 0;
+                        for (int a = 0; a < MAX_DERIV_ORDER; ++a) S.axes[a] = 0;
+                        if (parse_slot(S)) return 1;
+                        if (S.lap) return fail("descriptor: lap slots are not supported inside an integral node");
+                        inner_slots.push_back(S);
+                    }
+                    Nd.ops.resize(ino);
+                    for (int q = 0; q < ino; ++q) {
+                        double immd = 0.0;
+                        if (parse_op(Nd.ops[q], T.d + E.np + ins + q, immd)) return 1;
+                        if (Nd.ops[q].code == rp::OP_DATA) return fail("descriptor: DATA channels are not supported inside an integral node");
+                    }
+                    if (Nd.out_row < 0 || Nd.out_row >= T.d + E.np + ins + ino) return fail("descriptor: integral out row out of range");
+                }
+            } else {
+                in.clear();
+                in.seekg(pos);
+            }
+        }
+        const int ni = (int)T.inodes.size();
+        T.slots.resize(ns);
+        for (int s = 0; s < ns; ++s)
+            if (parse_slot(T.slots[s])) return 1;
+        T.n_outer = ns;
+        T.ops.resize(no);
+        T.imm64.clear();
+        for (int q = 0; q < no; ++q) {
+            rp::Instr& I = T.ops[q];
+            double immd = 0.0;
+            if (parse_op(I, T.d + E.np + ns + ni + q, immd)) return 1;
+            T.imm64.push_back(immd);
             if (I.code == rp::OP_DATA) {
                 if (I.imm < 0.f || I.imm > 15.f || I.imm != (float)(int)I.imm) return fail("descriptor: DATA channel index");
                 T.ndata = std::max(T.ndata, (int)I.imm + 1);
             }
         }
-        if (T.out_row < 0 || T.out_row >= T.d + E.np + ns + no) return fail("descriptor: out row out of range");
+        if (T.out_row < 0 || T.out_row >= T.d + E.np + ns + ni + no) return fail("descriptor: out row out of range");
+        if (ni > 0) {
+            // the tail kernel keeps ONE slot per jet channel and site class (seed written once): a repeated slot would lose an adjoint
+            auto same = [](const Slot& x, const Slot& y) {
+                bool eq = x.net == y.net && x.order == y.order && x.lap == y.lap;
+                for (int a = 0; eq && a < x.order; ++a) eq = x.axes[a] == y.axes[a];
+                return eq;
+            };
+            auto dup = [&](const Slot* b, int n) { for (int x = 0; x < n; ++x) for (int y = 0; y < x; ++y) if (same(b[x], b[y])) return true; return false; };
+            if (dup(T.slots.data(), ns)) return fail("descriptor: a term with integral nodes lists the same slot twice");
+            for (const IntNode& Nd : T.inodes)
+                if (dup(inner_slots.data() + Nd.slot0, Nd.nslots)) return fail("descriptor: an integral node lists the same slot twice");
+        }
+        for (IntNode& Nd : T.inodes) Nd.slot0 += ns;          // the nodes' slots follow the outer ones in T.slots
+        T.slots.insert(T.slots.end(), inner_slots.begin(), inner_slots.end());
         // optional: inmap <net> <n> <coordinate index of input 0> ... (one line per network whose inputs are not simply the
         // term's coordinates in order)
         for (;;) {
@@ -253,6 +328,8 @@ int apply_embeddings(pinn_engine& E) {
         bool touched = false;
         for (int n : nets) touched = touched || !E.nets[n].emb_idx.empty();
         if (!touched) continue;
+        if (!T.inodes.empty())
+            return fail("term " + std::to_string(ti) + ": integral terms over a network behind a periodic input embedding are not supported (the integrand would be integrated over an embedded coordinate)");
         const int d0 = T.d, np = E.np, S0 = (int)T.slots.size();
         // user-space input maps (explicit for every referenced network from here on: the row count of the term changes)
         for (int n : nets) {

@@ -44,13 +44,33 @@ namespace {
 // embedded terms (periodic input embedding): the installed point set lives in d_upts [n][d_user]; the device rows [n][d] = the
 // coordinates followed by their sin / cos rows are rebuilt from it whenever it changes (set_points, every sampler draw)
 inline float* user_pts(Term& T) { return T.emb_cols.empty() ? T.d_pts : T.d_upts; }
+void expand_sites(pinn_engine& E, Term& T);
 void embed_points(pinn_engine& E, Term& T) {
+    expand_sites(E, T);                                  // (integral terms: the site set follows every change of the point set)
     if (T.emb_cols.empty() || !T.d_upts || T.n <= 0) return;
     aux::EmbedArgs a;
     std::memset(&a, 0, sizeof a);
     a.upts = T.d_upts; a.pts = T.d_pts; a.n = (int)T.n; a.du = T.d_user; a.dx = T.d;
     for (size_t k = 0; k < T.emb_cols.size() && k < 4; ++k) { a.src[k] = T.emb_cols[k].src; a.is_cos[k] = T.emb_cols[k].is_cos; a.omega[k] = T.emb_cols[k].omega; }
     aux::launch_embed(a, E.stream);
+}
+// integral terms: device form of node k (shared by the site expansion and the tail kernel)
+aux::IntNodeDev int_node_dev(const Term& T, int k, int prog_off) {
+    const IntNode& Nd = T.inodes[(size_t)k];
+    aux::IntNodeDev d;
+    std::memset(&d, 0, sizeof d);
+    d.var = Nd.var; d.lo_row = Nd.lo_row; d.hi_row = Nd.hi_row; d.lo = (float)Nd.lo; d.hi = (float)Nd.hi; d.lo64 = Nd.lo; d.hi64 = Nd.hi;
+    d.slot0 = Nd.slot0; d.nslots = Nd.nslots; d.prog_off = prog_off; d.nops = (int)Nd.ops.size(); d.out_row = Nd.out_row;
+    return d;
+}
+// (re-)build blocks 1.. of an integral term's site set from block 0, the collocation points (set_points, every sampler draw)
+void expand_sites(pinn_engine& E, Term& T) {
+    if (T.inodes.empty() || !T.d_pts || T.n <= 0) return;
+    aux::IntSitesArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.sites = T.d_pts; a.N = (int)T.n; a.d = T.d; a.nnodes = (int)T.inodes.size(); a.Q = T.int_q; a.xi = E.d_int_xi;
+    for (int k = 0; k < a.nnodes; ++k) a.node[k] = int_node_dev(T, k, 0);
+    aux::launch_int_sites(a, E.stream);
 }
 void eval_sources(pinn_engine& E, Term& T) {
     if (T.src_root.empty() || T.coupled >= 0) return;
@@ -130,6 +150,69 @@ aux::ExprArgs expr_args(pinn_engine& E, Coupled& Cp, float scale, float* resid) 
     a.data = T.d_data;
     a.pw = (T.pw_n == T.n && T.pw_n > 0) ? T.d_pw : nullptr;
     return a;
+}
+
+// launch arguments of k_int_expr for an integral term (one network: Cp.d_jets[0] / d_ubar[0] are [C][sites x N])
+aux::IntExprArgs int_expr_args(pinn_engine& E, Coupled& Cp, float scale, float* resid) {
+    Term& T = E.terms[Cp.term];
+    aux::IntExprArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.sites = T.d_pts; a.N = (int)T.n; a.d = T.d; a.nparams = E.np; a.nparams_estim = E.ne; a.params = E.d_params;
+    a.jets = Cp.d_jets[0]; a.ubar = Cp.d_ubar[0]; a.C = E.groups[Cp.groups[0]].spec->C;
+    a.n_outer = T.n_outer; a.nnodes = (int)T.inodes.size(); a.Q = T.int_q;
+    for (size_t si = 0; si < T.slots.size(); ++si) a.chan[si] = T.chan_of_slot[si];
+    for (int c = 0; c < aux::INT_MAX_C; ++c) {
+        a.outer_slot_of_chan[c] = -1;
+        for (int k = 0; k < aux::INT_MAX_NODES; ++k) a.node_slot_of_chan[k][c] = -1;
+    }
+    for (int si = 0; si < T.n_outer; ++si) a.outer_slot_of_chan[T.chan_of_slot[(size_t)si]] = si;
+    int off = 0;
+    for (int k = 0; k < a.nnodes; ++k) {
+        a.node[k] = int_node_dev(T, k, off);
+        off += (int)T.inodes[(size_t)k].ops.size();
+        for (int si = a.node[k].slot0; si < a.node[k].slot0 + a.node[k].nslots; ++si) a.node_slot_of_chan[k][T.chan_of_slot[(size_t)si]] = si;
+    }
+    a.w = E.d_int_w;
+    a.prog = Cp.d_prog; a.iprog = T.d_int_prog; a.nops = (int)T.ops.size(); a.out_row = T.out_row; a.scale = scale;
+    a.losspart = Cp.d_losspart; a.pslab = Cp.d_pslab; a.K = (int)E.terms.size(); a.term_id = Cp.term; a.resid = resid;
+    a.data = T.d_data;
+    a.pw = (T.pw_n == T.n && T.pw_n > 0) ? T.d_pw : nullptr;
+    return a;
+}
+
+// Gauss-Legendre rule of q nodes on [-1, 1] in double (Newton on P_q from the Chebyshev guess), nodes increasing: what
+// numpy.polynomial.legendre.leggauss(q) returns to rounding.  Uploaded as the handle's rule for integral terms.
+int upload_int_rule(pinn_engine& E, int q) {
+    std::vector<double> xi((size_t)q), w((size_t)q);
+    const double PI = 3.14159265358979323846264338327950288;
+    for (int i = 0; i < q; ++i) {
+        double x = -std::cos(PI * (i + 0.75) / (q + 0.5)), dp = 1.0;
+        for (int it = 0; it < 100; ++it) {
+            double p0 = 1.0, p1 = x;
+            for (int n = 2; n <= q; ++n) { const double p2 = ((2.0 * n - 1.0) * x * p1 - (n - 1.0) * p0) / n; p0 = p1; p1 = p2; }
+            dp = q * (x * p1 - p0) / (x * x - 1.0);
+            const double dx = p1 / dp;
+            x -= dx;
+            if (std::fabs(dx) < 1e-16) break;
+        }
+        {
+            double p0 = 1.0, p1 = x;
+            for (int n = 2; n <= q; ++n) { const double p2 = ((2.0 * n - 1.0) * x * p1 - (n - 1.0) * p0) / n; p0 = p1; p1 = p2; }
+            dp = q * (x * p1 - p0) / (x * x - 1.0);
+        }
+        xi[(size_t)i] = x;
+        w[(size_t)i] = 2.0 / ((1.0 - x * x) * dp * dp);
+    }
+    std::vector<float> wf(w.begin(), w.end());
+    if (!E.d_int_xi) {
+        E.d_int_xi = (double*)plat_malloc(sizeof(double) * aux::INT_MAX_Q);
+        E.d_int_w = (float*)plat_malloc(sizeof(float) * aux::INT_MAX_Q);
+        if (!E.d_int_xi || !E.d_int_w) return fail("device allocation failed (quadrature rule)");
+    }
+    plat_h2d(E.d_int_xi, xi.data(), sizeof(double) * q, E.stream);
+    plat_h2d(E.d_int_w, wf.data(), sizeof(float) * q, E.stream);
+    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());      // (pageable temporaries)
+    return 0;
 }
 
 // one caller array of n elements of type T, seen as element type V at the precision boundary of a float / double entry point: the caller's
@@ -350,6 +433,12 @@ int pe::run_loss_grad(pinn_engine& E, const float* d_theta, float* d_out, const 
         }
         max_n1 = std::max(max_n1, nent / 4 + K);
         max_split = std::max(max_split, nsplit);
+        if (!E.terms[Cp.term].inodes.empty()) {          // integral term: the tail kernel over the site set's jets
+            aux::IntExprArgs ia = int_expr_args(E, Cp, scale_of(Cp.term), nullptr);
+            ia.loss_only = loss_only ? 1 : 0;
+            aux::launch_int_expr(ia, Cp.blocks, E.stream);
+            continue;
+        }
         aux::ExprArgs ea = expr_args(E, Cp, scale_of(Cp.term), nullptr);    // scale 0 => zero seeds
         ea.loss_only = loss_only ? 1 : 0;
         aux::launch_expr(ea, Cp.blocks, E.stream);
@@ -451,7 +540,9 @@ int pinn_create_on(const char* descriptor, int device, pinn_handle* out) {
     }
     E->hp_out = E->hp_theta + E->ntheta;
     E->hp_raw = (double*)(E->hp_theta + ((2 * E->ntheta + K + 1) / 2) * 2);
-    if (build_plan(*E)) {
+    bool any_int = false;
+    for (auto& T : E->terms) any_int = any_int || !T.inodes.empty();
+    if ((any_int && upload_int_rule(*E, E->int_q)) || build_plan(*E)) {
         const std::string msg = g_err;               // pinn_destroy must not lose the reason
         pinn_destroy(E.release());
         g_err = msg;
@@ -472,6 +563,7 @@ int pinn_destroy(pinn_handle h) {
     for (auto& T : E.terms) { plat_free(T.d_pts); plat_free(T.d_upts); plat_free(T.d_resid); plat_free(T.d_lb); plat_free(T.d_ub); plat_free(T.d_data); plat_free(T.d_pw); }
     plat_free(E.d_opt_theta); plat_free(E.d_opt_m); plat_free(E.d_opt_v); plat_free(E.d_opt_out); plat_free(E.d_w_over_n); plat_free(E.d_hist); plat_free(E.d_step); plat_free(E.d_draws); plat_free(E.d_sampled); plat_free(E.d_c12); plat_free(E.d_bar); plat_free(E.d_sums2); plat_free(E.d_own_r); plat_free(E.d_train_samp); plat_free(E.d_opt_bak); plat_host_free(E.h_flag);
     plat_free(E.d_theta); plat_free(E.d_params); plat_free(E.d_defaults); plat_free(E.d_lossraw);
+    plat_free(E.d_int_xi); plat_free(E.d_int_w);
     plat_free(E.d_out); plat_free(E.d_phi_pts); plat_free(E.d_phi_out); plat_free(E.d_phi_scr);
     plat_host_free(E.hp_theta);
     plat_event_destroy(E.ev0); plat_event_destroy(E.ev1); plat_event_destroy(E.ev2); plat_event_destroy(E.ev3);
@@ -495,13 +587,18 @@ static int set_points_impl(pinn_handle h, int term, const float* pts, int64_t n,
     if (!pts || n <= 0) return fail("pinn_set_points: empty point set (the reference's mean(abs2, .) over an empty set is NaN; refusing)");
     Term& T = E.terms[term];
     if (n * T.d >= (int64_t)1 << 31) return fail("pinn_set_points: point set too large for 32-bit indexing; shard it");
+    const int64_t S = T.sites();                         // integral terms: d_pts is the site set, the installed points are its block 0
+    if (S > 1 && n * S * std::max(T.d, aux::INT_MAX_C) >= (int64_t)1 << 31)
+        return fail("pinn_set_points: the site set of integral term " + std::to_string(term) + " (" + std::to_string(n) + " points x (1 + " +
+                    std::to_string(T.inodes.size()) + " integral node(s) x " + std::to_string(T.int_q) + " quadrature nodes) = " + std::to_string(n * S) +
+                    " sites) exceeds what one launch group takes (32-bit indexing of its jet channels); shard the point set or lower integral_nodes");
     if (n > T.pts_cap || !T.d_pts) {                     // grow only: a resampled set of another size reuses the buffer
         plat_sync(E.stream);                             // (an evaluation in flight may still read the old buffer)
         plat_free(T.d_pts);
         plat_free(T.d_upts);
         T.d_upts = nullptr;
         T.pts_cap = 0;
-        T.d_pts = (float*)plat_malloc(sizeof(float) * n * T.d);
+        T.d_pts = (float*)plat_malloc(sizeof(float) * n * S * T.d);
         if (!T.emb_cols.empty()) T.d_upts = (float*)plat_malloc(sizeof(float) * n * T.d_user);
         if (!T.d_pts || (!T.emb_cols.empty() && !T.d_upts)) return fail("device allocation failed (points)");
         T.pts_cap = n;
@@ -522,7 +619,7 @@ static int set_points_impl(pinn_handle h, int term, const float* pts, int64_t n,
 // a coupled equation
 static int term_installed(pinn_engine& E, int term) {
     Term& T = E.terms[term];
-    const int64_t n = T.n;
+    int64_t n = T.n;
     if (T.coupled < 0) {
         if (!T.src_root.empty()) {
             if (T.src_cap < n) {
@@ -539,6 +636,8 @@ static int term_installed(pinn_engine& E, int term) {
     }
     Coupled& Cp = E.coupled[T.coupled];
     const int K = (int)E.terms.size();
+    const int64_t npts = n;
+    n *= T.sites();                                      // (integral terms: the networks' jets / seeds cover the site set)
     if (Cp.cap < n) {
         for (size_t i = 0; i < Cp.d_jets.size(); ++i)
             if (Cp.tail < 0 || (int)i == Cp.tail) { plat_free(Cp.d_jets[i]); plat_free(Cp.d_ubar[i]); }
@@ -564,7 +663,7 @@ static int term_installed(pinn_engine& E, int term) {
     if (Cp.tail >= 0)                                    // rows packed with stride n (the kernels address channel c at c * N)
         for (size_t i = 0; i < Cp.nets.size(); ++i)
             if ((int)i != Cp.tail) { Cp.d_jets[i] = Cp.d_jets_all + (size_t)Cp.src_off[i] * n; Cp.d_ubar[i] = Cp.d_ubar_all + (size_t)Cp.src_off[i] * n; }
-    Cp.blocks = (int)((n + 255) / 256);
+    Cp.blocks = (int)((npts + 255) / 256);
     if (Cp.cap_blocks < Cp.blocks) {
         plat_free(Cp.d_losspart); plat_free(Cp.d_pslab);
         Cp.d_losspart = (double*)plat_malloc(sizeof(double) * (size_t)Cp.blocks * 4 * K);
@@ -779,7 +878,8 @@ static int residual_f32(pinn_engine& E, int term, const float* theta, float* r) 
             ga.ntiles = ga.terms[0].ntiles;
             G.spec->launch(ga, pk::MODE_FWD, std::max(1, std::min(E.ncu * G.spec->WG_FWD, G.spec->family == 1 ? (ga.ntiles + 3) / 4 : ga.ntiles)), E.stream);
         }
-        aux::launch_expr(expr_args(E, Cp, 0.f, T.d_resid), Cp.blocks, E.stream);
+        if (!T.inodes.empty()) aux::launch_int_expr(int_expr_args(E, Cp, 0.f, T.d_resid), Cp.blocks, E.stream);
+        else aux::launch_expr(expr_args(E, Cp, 0.f, T.d_resid), Cp.blocks, E.stream);
         if (plat_d2h(r, T.d_resid, sizeof(float) * T.n, E.stream)) return fail("D2H copy failed");
         if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
         { const std::string le = jit_take_launch_error(); if (!le.empty()) return fail("pinn_residual: " + le); }
@@ -1090,12 +1190,64 @@ int pinn_set_option(pinn_handle h, const char* name, const char* value) {
         if (v == "off" || v == "0") { E.persistent = false; return 0; }
         return fail("pinn_set_option: persistent must be \"on\" or \"off\"");
     }
+    if (k == "integral_nodes") {
+        // Gauss-Legendre nodes per integral node.  A live handle is RE-PLANNED: the installed point sets of its integral terms stay, their
+        // site sets are rebuilt for the new rule (buffers grow as needed); optimiser state, samplers and weights stay
+        char* end = nullptr;
+        const long q = std::strtol(v.c_str(), &end, 10);
+        if (v.empty() || *end || q < 2 || q > aux::INT_MAX_Q) return fail("pinn_set_option: integral_nodes must be an integer in 2.." + std::to_string(aux::INT_MAX_Q) + ", not \"" + v + "\"");
+        if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+        for (auto& T : E.terms)
+            if (!T.inodes.empty() && T.d_pts && T.n > 0 && T.n * (1 + (int64_t)T.inodes.size() * q) * std::max(T.d, aux::INT_MAX_C) >= (int64_t)1 << 31)
+                return fail("pinn_set_option: integral_nodes = " + std::to_string(q) + " makes a site set of " + std::to_string(T.n * (1 + (int64_t)T.inodes.size() * q)) +
+                            " sites, more than one launch group takes; the handle keeps " + std::to_string(E.int_q));
+        bool any = false;
+        for (auto& T : E.terms) any = any || !T.inodes.empty();
+        if (!any) { E.int_q = (int)q; return 0; }
+        // allocate first, commit after: a failed allocation of a site buffer leaves the handle exactly as it was
+        std::vector<float*> nbuf(E.terms.size(), nullptr);
+        for (size_t t = 0; t < E.terms.size(); ++t) {
+            Term& T = E.terms[t];
+            if (T.inodes.empty() || !T.d_pts || T.n <= 0) continue;
+            const int64_t new_sites = 1 + (int64_t)T.inodes.size() * q;
+            if (T.n * new_sites <= T.pts_cap * (int64_t)T.sites()) continue;      // the buffer (pts_cap points at the current rule) has room
+            nbuf[t] = (float*)plat_malloc(sizeof(float) * (size_t)T.n * new_sites * T.d);
+            if (!nbuf[t]) {
+                for (float* b : nbuf) plat_free(b);
+                return fail("pinn_set_option: device allocation failed (site set for integral_nodes = " + std::to_string(q) + "); the handle keeps " + std::to_string(E.int_q));
+            }
+        }
+        if (upload_int_rule(E, (int)q)) {
+            for (float* b : nbuf) plat_free(b);
+            if (E.d_int_xi) upload_int_rule(E, E.int_q);
+            return 1;
+        }
+        E.int_q = (int)q;
+        for (size_t t = 0; t < E.terms.size(); ++t) {
+            Term& T = E.terms[t];
+            if (T.inodes.empty()) continue;
+            const int64_t room = T.pts_cap * (int64_t)T.sites();          // sites the current buffer holds
+            T.int_q = E.int_q;
+            if (!T.d_pts || T.n <= 0) { T.pts_cap = 0; continue; }        // (no set installed: pinn_set_points sizes the buffer)
+            if (nbuf[t]) {
+                plat_d2d(nbuf[t], T.d_pts, sizeof(float) * (size_t)T.n * T.d, E.stream);      // block 0: the collocation points
+                plat_sync(E.stream);
+                plat_free(T.d_pts);
+                T.d_pts = nbuf[t];
+                T.pts_cap = T.n;
+            } else T.pts_cap = room / T.sites();                          // points the kept buffer holds at the new rule (>= n)
+            expand_sites(E, T);
+            if (term_installed(E, (int)t)) return 1;
+        }
+        if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+        return 0;
+    }
     if (k == "derivative") {
         if (v == "stencil") return f64_stencil_enable(E, true);
         if (v == "exact") return E.f64 ? f64_stencil_enable(E, false) : 0;
         return fail("pinn_set_option: derivative must be \"exact\" or \"stencil\"");
     }
-    return fail("pinn_set_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative)");
+    return fail("pinn_set_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes)");
 }
 
 int pinn_get_option(pinn_handle h, const char* name, char* buf, int64_t buflen) {
@@ -1106,6 +1258,7 @@ int pinn_get_option(pinn_handle h, const char* name, char* buf, int64_t buflen) 
     if (k == "gemm_delta") { std::snprintf(buf, (size_t)buflen, "%.9g", h->gemm_delta); return 0; }
     if (k == "precision") { std::snprintf(buf, (size_t)buflen, "%s", h->f64 ? "f64" : "f32"); return 0; }
     if (k == "persistent") { std::snprintf(buf, (size_t)buflen, "%s", h->persistent ? "on" : "off"); return 0; }
+    if (k == "integral_nodes") { std::snprintf(buf, (size_t)buflen, "%d", h->int_q); return 0; }
     if (k == "derivative") { std::snprintf(buf, (size_t)buflen, "%s", pe::f64_stencil_on(*h) ? "stencil" : "exact"); return 0; }
     if (k == "eval_path") { std::snprintf(buf, (size_t)buflen, "%s", h->eval_path == 2 ? "one launch" : (h->eval_path == 1 ? "stand-alone kernels" : "none")); return 0; }
     if (k == "f64_path") { std::snprintf(buf, (size_t)buflen, "%s", pe::f64_path(*h)); return 0; }
@@ -1113,7 +1266,7 @@ int pinn_get_option(pinn_handle h, const char* name, char* buf, int64_t buflen) 
     if (k == "f64_merged") { std::snprintf(buf, (size_t)buflen, "%d", pe::f64_merged(*h)); return 0; }          // merged launches of the last float64 evaluation
     if (k == "f64_chunks") { std::snprintf(buf, (size_t)buflen, "%d", pe::f64_chunks(*h)); return 0; }          // chunks of the largest point set in the last float64 call
     if (k == "adam_path") { std::snprintf(buf, (size_t)buflen, "%s", h->adam_path == 2 ? "persistent" : (h->adam_path == 1 ? "loop" : "none")); return 0; }
-    return fail("pinn_get_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, grad_health, gemm_delta, adam_path, eval_path, f64_path, f64_merged, f64_chunks, f64_affine)");
+    return fail("pinn_get_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, grad_health, gemm_delta, adam_path, eval_path, f64_path, f64_merged, f64_chunks, f64_affine)");
 }
 
 // fp32 optimiser state (float64 mode: f64.cpp keeps its own, in double)
@@ -1886,7 +2039,11 @@ int pinn_describe(pinn_handle h, char* buf, int64_t buflen) {
         const Group& G = h->groups[g];
         os << "group " << g << (G.kind == 1 ? (G.use_rec ? " [coupled fwd/gradin, records in HBM]" : " [coupled fwd/gradin]") :
                                 (G.kind == 2 ? " [coupled tail: forward + tape + reverse in one launch]" : "")) << " net=" << G.net << " kernel=" << spec_name(*G.spec) << (G.ga.act == pk::ACT_SWISH ? "+swish" : "") << " tiles=" << G.ga.ntiles << " blocks=" << G.blocks << " terms=";
-        for (int t : G.terms) os << t << ",";
+        for (int t : G.terms) {
+            os << t;
+            if (!h->terms[t].inodes.empty()) os << "+integral(" << h->terms[t].int_q << ")";       // its tiles are the term's site set
+            os << ",";
+        }
         if (G.chain_to >= 0) os << " slabs=" << (G.blocks <= h->groups[G.chain_to].blocks ? "chained onto group " : "own (more workgroups than group ") << G.chain_to << (G.blocks <= h->groups[G.chain_to].blocks ? "" : ")");
         if (G.merged >= 0 && h->merged[G.merged].tail == (int)g) os << " launch=merged into group " << h->merged[G.merged].head << "'s (one persistent kernel walks both tile lists)";
         os << "\n";

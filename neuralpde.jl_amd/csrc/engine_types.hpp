@@ -13,6 +13,7 @@
 
 #include "../../include/pinn_hip.h"
 #include "aux_limits.hpp"
+#include "int_limits.hpp"
 #include "plat.hpp"
 #include "spec_registry.hpp"
 
@@ -77,7 +78,27 @@ struct Net {
 };
 struct LinearForm { float k = 0.f; float a[pk::LIN_MAX_C] = {}; float b[pk::LIN_MAX_SRC] = {}; };
 struct EmbCol { int src; double omega; int is_cos; };      // device coordinate row = sin / cos (omega x coordinate `src`)
+// one integral node of a term (descriptor `integral` block): I(x) = int_lo^hi f(s) ds over coordinate `var`, f a tape of its own over
+// rows [coordinates (row `var` = the quadrature node) | params | its slots | ops]; its slots are Term::slots[slot0, slot0 + nslots)
+struct IntNode {
+    int var = 0;
+    int lo_row = -1, hi_row = -1;    // >= 0: the bound is that coordinate of the collocation point
+    double lo = 0.0, hi = 0.0;       // otherwise the constant
+    int slot0 = 0, nslots = 0;
+    std::vector<rp::Instr> ops;
+    int out_row = 0;
+};
 struct Term {
+    // integral terms: rows [d+np+n_outer, d+np+n_outer+inodes.size()) of the tape are the integral nodes; `slots` holds
+    // the outer slots first, then every node's.  The device point buffer d_pts is the term's SITE SET [sites()][n][d]: block 0 the
+    // collocation points as installed, block 1 + k Q + q the points with node k's variable moved to quadrature node q
+    // (aux::k_int_sites whenever the point set changes)
+    std::vector<IntNode> inodes;
+    int n_outer = 0;                 // outer slots (== slots.size() without integral nodes)
+    int int_q = 0;                   // Gauss-Legendre nodes per integral node (handle option "integral_nodes")
+    rp::Instr* d_int_prog = nullptr; // the nodes' tapes, node after node
+    int sites() const { return 1 + (int)inodes.size() * int_q; }      // evaluations of the network(s) per collocation point
+    int tape_row0(int np) const { return d + np + (inodes.empty() ? (int)slots.size() : n_outer + (int)inodes.size()); }      // first op row
     int d = 0;                       // coordinate rows of the device point set (embedded terms: d_user rows + emb_cols)
     int d_user = 0;                  // coordinates per point at the C ABI (pinn_set_points, samplers, pinn_get_points); == d without embeddings
     std::vector<EmbCol> emb_cols;    // rows d_user .. d-1, written by aux::k_embed whenever the point set changes (descriptor.cpp: apply_embeddings)
@@ -287,6 +308,9 @@ struct pinn_engine {
     int max_contrib = 0, max_inv_pos = 0;      // most slab entries / image positions of one theta element (plan.cpp)
     bool persistent = true;          // pinn_set_option "persistent": small problems run pinn_adam_steps inside one launch
     int eval_path = 0;               // what the last host-entry loss + gradient evaluation ran: 1 the stand-alone kernels, 2 one launch (eval_fused)
+    int int_q = 16;                  // pinn_set_option "integral_nodes": Gauss-Legendre nodes per integral node (2..64)
+    double* d_int_xi = nullptr;      // [int_q] nodes on [-1, 1] (double) and
+    float* d_int_w = nullptr;        // [int_q] weights of the rule, computed in double on the host
     int adam_path = 0;               // what the last pinn_adam_steps call ran: 0 nothing yet, 1 the stand-alone loop, 2 the persistent kernel
     // phi scratch
     float* d_phi_pts = nullptr;

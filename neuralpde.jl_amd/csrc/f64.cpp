@@ -311,6 +311,8 @@ int f64_enable(pinn_engine& E) {
         const Term& T = E.terms0[t];
         F64Term& F = S->terms[t];
         const std::string who = "precision f64: term " + std::to_string(t) + ": ";
+        if (!T.inodes.empty())
+            return fail(who + "integral terms run on the fp32 kernels only (the float64 evaluation mode does not cover them): use precision = \"f32\"");
         std::vector<int> nets;
         for (auto& sl : T.slots) if (std::find(nets.begin(), nets.end(), sl.net) == nets.end()) nets.push_back(sl.net);
         std::sort(nets.begin(), nets.end());

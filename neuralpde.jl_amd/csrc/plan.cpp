@@ -360,7 +360,7 @@ static int plan_assign_terms(pinn_engine& E) {
         bool coupled_ok = true, any_coupled = false;
         for (size_t t = 0; t < E.terms.size(); ++t) {
             fused[t] = E.terms[t];
-            did[t] = fuse_laplacian(fused[t], E.np);
+            did[t] = E.terms[t].inodes.empty() && fuse_laplacian(fused[t], E.np);      // (an integral term keeps its slots as parsed)
             std::vector<int> nets;
             for (auto& s : fused[t].slots) if (std::find(nets.begin(), nets.end(), s.net) == nets.end()) nets.push_back(s.net);
             if (nets.size() == 1) {
@@ -420,6 +420,17 @@ static int plan_assign_terms(pinn_engine& E) {
         }
         // a single-network residual too long for the fused kernel's 32-row tape takes the two-launch path (k_expr has 96 rows)
         two_launch[t] = term_nets[t].size() > 1;
+        if (!T.inodes.empty()) {
+            // integral terms always take the forward / tail kernel / reverse path, on their site set, with ONE network
+            if (term_nets[t].size() > 1)
+                return fail("term " + std::to_string(t) + ": an integral term must be an equation of one dependent variable (it references " +
+                            std::to_string(term_nets[t].size()) + " networks)");
+            if (E.nets[term_nets[t][0]].kind == 1)
+                return fail("term " + std::to_string(t) + ": integral terms over a DGM network are not supported (Dense chains only)");
+            if (E.int_q < 2 || E.int_q > aux::INT_MAX_Q) return fail("integral_nodes must be in 2.." + std::to_string(aux::INT_MAX_Q));
+            T.int_q = E.int_q;
+            two_launch[t] = 1;
+        }
         if (!two_launch[t]) {
             Term probe = T;
             analyse_static(probe, E.np);
@@ -494,8 +505,12 @@ static int plan_assign_terms(pinn_engine& E) {
             if (E.nets[net].kind == 1)
                 return fail("term " + std::to_string(t) + ": DGM networks are supported in single-network equations (one dependent variable per equation, "
                             "residual within the fused tape)");
-        if ((int)T.slots.size() > aux::EXPR_MAX_SLOTS || T.d + E.np + (int)T.slots.size() + (int)T.ops.size() > aux::EXPR_MAX_ROWS)
+        if ((int)T.slots.size() > aux::EXPR_MAX_SLOTS || T.tape_row0(E.np) + (int)T.ops.size() > aux::EXPR_MAX_ROWS)
             return fail("term " + std::to_string(t) + ": coupled residual expression too long");
+        for (const IntNode& Nd : T.inodes)
+            if (T.d + E.np + Nd.nslots + (int)Nd.ops.size() > aux::EXPR_MAX_ROWS)
+                return fail("term " + std::to_string(t) + ": integrand expression too long (" + std::to_string(T.d + E.np + Nd.nslots + (int)Nd.ops.size()) +
+                            " rows > " + std::to_string(aux::EXPR_MAX_ROWS) + ")");
         E.coupled.emplace_back();
         Coupled& Cp = E.coupled.back();
         T.coupled = (int)E.coupled.size() - 1;
@@ -515,6 +530,9 @@ static int plan_assign_terms(pinn_engine& E) {
                 if (needs_of(T, net, nf, npairs, nh) || spec_for(t, net, T.d, nf, npairs, nh, sps[i])) return 1;
             }
         }
+        if (!T.inodes.empty() && sps[0]->C > aux::INT_MAX_C)
+            return fail("term " + std::to_string(t) + ": the kernel of an integral term carries " + std::to_string(sps[0]->C) + " jet channels (> " +
+                        std::to_string(aux::INT_MAX_C) + ")");
         // TAIL launch: the family-2 kernel with the most channels evaluates the residual tape itself, the other networks' jets as source rows
         {
             const bool no_tail = std::getenv("PINN_NO_TAIL_FUSE") != nullptr;      // (read per plan: the tests switch it)
@@ -525,7 +543,7 @@ static int plan_assign_terms(pinn_engine& E) {
                 nsrc_all += sps[i]->C;
                 if (sps[i]->family == 2 && (best < 0 || sps[i]->C > sps[best]->C)) best = (int)i;
             }
-            if (best >= 0 && !no_tail && !data_ops && !coupled_union) {
+            if (best >= 0 && !no_tail && !data_ops && !coupled_union && T.inodes.empty()) {
                 const int nsrc = nsrc_all - sps[best]->C;
                 if (T.d + E.np + sps[best]->C + nsrc + (int)T.ops.size() <= rp::MAX_ROWS_FUSED) {
                     Cp.tail = best;
@@ -932,8 +950,21 @@ static int plan_coupled_programs(pinn_engine& E) {
     // ---- coupled equations: tape in descriptor row numbering (slots are direct inputs of k_expr) ----
     for (auto& Cp : E.coupled) {
         Term& T = E.terms[Cp.term];
-        const int lim0 = T.d + E.np + (int)T.slots.size();
+        const int lim0 = T.tape_row0(E.np);
         std::vector<rp::Instr> prog = T.ops;
+        if (!T.inodes.empty()) {                         // the nodes' tapes, node after node (aux::IntNodeDev::prog_off)
+            std::vector<rp::Instr> ip;
+            for (const IntNode& Nd : T.inodes) ip.insert(ip.end(), Nd.ops.begin(), Nd.ops.end());
+            for (rp::Instr& I : ip) {
+                if (rp::is_nullary(I.code)) I.a = 0;
+                if (!rp::is_binary(I.code)) I.b = 0;
+                rp::finalize(I);
+            }
+            T.d_int_prog = (rp::Instr*)plat_malloc(sizeof(rp::Instr) * ip.size());
+            if (!T.d_int_prog) return fail("device allocation failed (integrand programs)");
+            plat_h2d(T.d_int_prog, ip.data(), sizeof(rp::Instr) * ip.size(), E.stream);
+            plat_sync(E.stream);                         // (ip is a pageable temporary)
+        }
         for (size_t q = 0; q < prog.size(); ++q) {
             rp::Instr& I = prog[q];
             const int lim = lim0 + (int)q;
@@ -1075,6 +1106,7 @@ int build_plan(pinn_engine& E) {
 void free_plan(pinn_engine& E) {
     for (auto& T : E.terms) {
         plat_free(T.d_src_prog); T.d_src_prog = nullptr;
+        plat_free(T.d_int_prog); T.d_int_prog = nullptr;
         plat_free(T.d_src); T.d_src = nullptr; T.src_cap = 0;
         T.net = T.group = T.slot_in_group = T.coupled = -1;
     }
@@ -1107,10 +1139,11 @@ void retile(pinn_engine& E, int gi) {
     for (size_t j = 0; j < G.terms.size(); ++j) {
         Term& T = E.terms[G.terms[j]];
         pk::TermDev& td = G.ga.terms[j];
+        const int64_t nsites = T.n * T.sites();           // an integral term's network launches run on its site set
         td.pts = T.d_pts;
-        td.N = (int)T.n;
+        td.N = (int)nsites;
         td.tile0 = tile;
-        td.ntiles = (int)((T.n + s.TP - 1) / s.TP);
+        td.ntiles = (int)((nsites + s.TP - 1) / s.TP);
         td.prog_off = G.prog_off[j];
         td.nops = G.prog_n[j];
         td.out_row = G.out_row[j];
@@ -1118,7 +1151,7 @@ void retile(pinn_engine& E, int gi) {
         td.scale = 0.f;
         td.out = nullptr;
         td.in = nullptr;
-        td.pw = (T.pw_n == T.n && T.pw_n > 0) ? T.d_pw : nullptr;
+        td.pw = (T.pw_n == T.n && T.pw_n > 0 && T.inodes.empty()) ? T.d_pw : nullptr;      // (integral terms: the point factors enter in k_int_expr)
         td.src = (G.kind == 0) ? T.d_src : nullptr;
         td.nsrc = (G.kind == 0) ? (int)T.src_root.size() : 0;
         td.src_bar = nullptr;

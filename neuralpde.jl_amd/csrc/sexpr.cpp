@@ -112,7 +112,7 @@ bool as_number(const Node& n, double& v) {
 }
 bool is_pi(const Node& n) { return n.atom && (n.text == "pi" || n.text == "π"); }
 
-struct Ref { char kind; int idx; };      // 'x' coordinate, 'p' parameter, 's' slot, 'o' op
+struct Ref { char kind; int idx; };      // 'x' coordinate, 'p' parameter, 's' slot, 'i' integral node, 'o' op
 
 struct Lowering {
     const SexprContext& C;
@@ -122,6 +122,11 @@ struct Lowering {
     std::vector<RawOp> ops;
     std::map<std::string, Ref> memo;
     std::string err;
+    // integral nodes (integral <var> <lo> <hi> <body>): the body is lowered by a Lowering of its own (`inner`) into a tape over
+    // [coordinates | parameters | its slots | its ops]; the node is a row of this tape like a jet slot (include/pinn_hip.h)
+    struct RawNode { int var; int lo_row, hi_row; double lo, hi; std::vector<Slot> slots; std::vector<RawOp> ops; Ref out; };
+    std::vector<RawNode> nodes;
+    bool inner = false;
 
     Lowering(const SexprContext& c, const std::vector<std::string>& iv) : C(c), indvars(iv) {}
 
@@ -186,6 +191,45 @@ struct Lowering {
             for (int k = 0; k < pr.second; ++k) axes.push_back(ax);
         }
         return slot_ref(net, axes, out);
+    }
+
+    // a bound of an integral: a finite number, or one of the term's independent variables
+    bool bound(const Node& b, const char* what, int& row, double& val) {
+        row = -1;
+        val = 0.0;
+        if (b.atom) {
+            for (size_t i = 0; i < indvars.size(); ++i)
+                if (indvars[i] == b.text) { row = (int)i; return true; }
+            if (as_number(b, val)) return true;
+            std::string t = b.text;
+            if (!t.empty() && (t[0] == '-' || t[0] == '+')) t = t.substr(1);
+            if (t == "Inf" || t == "inf" || t == "oo" || t == "∞" || t == "Inf32" || t == "Inf64")
+                return fail_(std::string("integral with an infinite ") + what + " bound: the reference's change of variables for infinite domains "
+                             "(transform_inf_integral.jl) is not supported by the HIP engine; bounds must be finite");
+        }
+        return fail_(std::string("integral ") + what + " bound `" + b.key() + "` is a general expression: a bound must be a finite number or an independent variable of the term");
+    }
+    bool integral(const Node& n, Ref& out) {
+        if (inner) return fail_("nested integrals are not supported by the HIP engine (one integration variable per integral term)");
+        if (n.args.size() != 4) return fail_("malformed (integral <variable> <lo> <hi> <body>): multi-variable integrals (ProductDomain) are not supported, an integral term runs over ONE independent variable");
+        if (!n.args[0].atom) return fail_("multi-variable integrals (ProductDomain) are not supported by the HIP engine: an integral term runs over ONE independent variable");
+        RawNode nd;
+        nd.var = -1;
+        for (size_t i = 0; i < indvars.size(); ++i)
+            if (indvars[i] == n.args[0].text) nd.var = (int)i;
+        if (nd.var < 0) return fail_("integration variable " + n.args[0].text + " is not an independent variable of this term");
+        if (!bound(n.args[1], "lower", nd.lo_row, nd.lo) || !bound(n.args[2], "upper", nd.hi_row, nd.hi)) return false;
+        if ((int)nodes.size() >= aux::INT_MAX_NODES) return fail_("more than " + std::to_string(aux::INT_MAX_NODES) + " integral nodes in one term");
+        Lowering B(C, indvars);
+        B.inner = true;
+        Ref r;
+        if (!B.lower(n.args[3], r)) return fail_(B.err);
+        if (B.slots.empty()) return fail_("the integrand of " + n.key() + " does not contain a dependent variable: integrate it symbolically");
+        if (r.kind != 'o') r = B.unary(rp::OP_ADDC, r, 0.0);
+        nd.slots = B.slots; nd.ops = B.ops; nd.out = r;
+        nodes.push_back(nd);
+        out = Ref{'i', (int)nodes.size() - 1};
+        return true;
     }
 
     bool lower(const Node& n, Ref& out) {
@@ -369,6 +413,7 @@ struct Lowering {
             out = unary(f->second, r);
             return true;
         }
+        if (h == "integral") return integral(n, out);
         return fail_("function '" + h + "' with " + std::to_string(na) + " argument(s) is outside the engine's closed op set (SURVEY.md App. B)");
     }
 };
@@ -392,7 +437,7 @@ int lower_sexpr_term(const SexprContext& C, const std::vector<std::string>& indv
     res.args = {nl, nr};
     Ref out;
     if (!L.lower(res, out)) return fail("residual lowering: " + L.err);
-    if (L.slots.empty()) {
+    if (L.slots.empty() && L.nodes.empty()) {
         // the residual does not depend on any dependent variable after folding; bind the term to the first one named in the equation
         int net = -1;
         std::vector<const Node*> st{&nl, &nr};
@@ -409,27 +454,45 @@ int lower_sexpr_term(const SexprContext& C, const std::vector<std::string>& indv
         L.slot_ref(net, {}, dummy);
     }
     if (out.kind != 'o') out = L.unary(rp::OP_ADDC, out, 0.0);             // residual is a bare input row: materialise it
-    const int d = (int)indvars.size(), S = (int)L.slots.size();
-    auto row = [&](const Ref& r) -> int {
+    const int d = (int)indvars.size(), S = (int)L.slots.size(), NI = (int)L.nodes.size();
+    // rows [coordinates | parameters | S slots | NI integral nodes | ops]; a node's own tape has its slots in place of (S, NI)
+    auto row_of = [&](const Ref& r, int ns, int ni) -> int {
         switch (r.kind) {
             case 'x': return r.idx;
             case 'p': return d + r.idx;
             case 's': return d + np + r.idx;
-            default: return d + np + S + r.idx;
+            case 'i': return d + np + ns + r.idx;
+            default: return d + np + ns + ni + r.idx;
         }
     };
+    auto instr = [&](const Lowering::RawOp& o, int ns, int ni) {
+        rp::Instr I;
+        I.code = o.code;
+        I.a = o.has_a ? row_of(o.a, ns, ni) : 0;
+        I.b = (o.has_b && rp::is_binary(o.code)) ? row_of(o.b, ns, ni) : 0;
+        I.imm = o.imm;
+        rp::finalize(I);
+        return I;
+    };
+    auto row = [&](const Ref& r) { return row_of(r, S, NI); };
     T.d = d;
     T.slots = L.slots;
+    T.n_outer = S;
+    T.inodes.clear();
+    for (auto& nd : L.nodes) {                           // the nodes' slots follow the outer ones (engine_types.hpp: Term::slots)
+        IntNode Nd;
+        Nd.var = nd.var; Nd.lo_row = nd.lo_row; Nd.hi_row = nd.hi_row; Nd.lo = nd.lo; Nd.hi = nd.hi;
+        Nd.slot0 = (int)T.slots.size(); Nd.nslots = (int)nd.slots.size();
+        if (Nd.nslots > aux::EXPR_MAX_SLOTS) return fail("an integral node has more than " + std::to_string(aux::EXPR_MAX_SLOTS) + " slots");
+        for (auto& o : nd.ops) Nd.ops.push_back(instr(o, Nd.nslots, 0));
+        Nd.out_row = row_of(nd.out, Nd.nslots, 0);
+        T.slots.insert(T.slots.end(), nd.slots.begin(), nd.slots.end());
+        T.inodes.push_back(Nd);
+    }
     T.ops.clear();
     T.imm64.clear();
     for (auto& o : L.ops) {
-        rp::Instr I;
-        I.code = o.code;
-        I.a = o.has_a ? row(o.a) : 0;
-        I.b = (o.has_b && rp::is_binary(o.code)) ? row(o.b) : 0;
-        I.imm = o.imm;
-        rp::finalize(I);
-        T.ops.push_back(I);
+        T.ops.push_back(instr(o, S, NI));
         T.imm64.push_back(o.imm64);
     }
     T.out_row = row(out);
@@ -450,7 +513,7 @@ int lower_sexpr_term(const SexprContext& C, const std::vector<std::string>& indv
         for (size_t i = 0; ident && i < m.size(); ++i) ident = m[i] == (int)i;
         if (!ident) T.inmap[s.net] = m;
     }
-    if (d + np + S + (int)T.ops.size() > rp::MAX_ROWS) return fail("residual expression too long");
+    if (d + np + S + NI + (int)T.ops.size() > rp::MAX_ROWS) return fail("residual expression too long");
     return 0;
 }
 

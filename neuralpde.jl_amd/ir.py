@@ -9,7 +9,10 @@ Row numbering inside a term (descriptor side):
     [0, d)                 coordinates, in the positional order of `this_eq_indvars` (discretize.jl:126-131)
     [d, d+NP)              PDE parameters (theta.p when param_estim, else default_p; discretize.jl:83-109)
     [d+NP, d+NP+S)         jet slots
-    [d+NP+S, ...)          ops
+    [d+NP+S, d+NP+S+NI)    integral nodes (terms with `Integral` operators only; src/discretize.jl:355-396)
+    [d+NP+S+NI, ...)       ops
+An integral node carries a tape of its own — the integrand — numbered the same way over its own slots, with the integration
+variable's coordinate row holding the quadrature node.
 """
 from __future__ import annotations
 
@@ -41,6 +44,29 @@ class Instr:
 
 
 @dataclass
+class IntegralIR:
+    """One `Integral(s in lo..hi)(f)` of a term: I(x) = int_lo^hi f(s; x, u, du, p) ds over coordinate `var` of the term."""
+    var: int                            # index of the integration variable among the term's coordinates
+    lo: object                          # float, or ("x", i): coordinate i of the collocation point
+    hi: object
+    slots: List[Slot]                   # the integrand's u(...) / derivative(...) call sites, evaluated at the substituted point
+    ops: List[Instr]                    # the integrand's tape: rows [coordinates | parameters | these slots | ops]
+    out_row: int
+
+    @staticmethod
+    def _bound(b) -> str:
+        return f"x{int(b[1])}" if isinstance(b, tuple) else repr(float(b))
+
+    def lines(self) -> list:
+        out = [f"integral {self.var} {self._bound(self.lo)} {self._bound(self.hi)} {len(self.slots)} {len(self.ops)} {self.out_row}"]
+        for s in self.slots:
+            out.append(f"slot {s.net} {s.order} " + " ".join(str(a) for a in s.axes))
+        for q in self.ops:
+            out.append(f"op {q.op} {q.a} {q.b} {float(q.imm)!r}")
+        return out
+
+
+@dataclass
 class TermIR:
     dim: int
     slots: List[Slot]
@@ -56,6 +82,7 @@ class TermIR:
     # exist only as tapes (DataLoss)
     lhs_sexpr: str = None
     rhs_sexpr: str = None
+    integrals: List[IntegralIR] = field(default_factory=list)      # integral nodes, rows [d+NP+S, d+NP+S+NI) of the tape
 
 
 @dataclass
@@ -115,6 +142,10 @@ class ProblemIR:
 
     def _term_lines(self, i, t):
         out = [f"term {i} {t.dim} {len(t.slots)} {len(t.ops)} {t.out_row}"]
+        if t.integrals:                 # `integrals <NI>` + one block per node, in front of the term's own slot lines
+            out.append(f"integrals {len(t.integrals)}")
+            for node in t.integrals:
+                out += node.lines()
         for s in t.slots:
             out.append(f"slot {s.net} {s.order} " + " ".join(str(a) for a in s.axes))
         for q in t.ops:

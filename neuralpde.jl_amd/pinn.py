@@ -193,7 +193,7 @@ class PhysicsInformedNN:
     def __init__(self, chain, strategy: AbstractTrainingStrategy, *, init_params=None, phi=None, derivative=None,
                  param_estim: bool = False, additional_loss: Optional[Callable] = None, adaptive_loss=None,
                  logger=None, log_options: LogOptions = LogOptions(), iteration=None, data_loss: Sequence[DataLoss] = (),
-                 precision: str = "auto", **kwargs):
+                 precision: str = "auto", integral_nodes: int = 16, **kwargs):
         if phi is not None or derivative is not None:
             raise ValueError("custom `phi` / `derivative` closures are per-call Julia hooks (src/pinn_types.jl:166-167) "
                              "and cannot be fused into the HIP kernels; they are not supported by this backend")
@@ -212,6 +212,11 @@ class PhysicsInformedNN:
         #           results are converted at the boundary;
         #   "f64":  the float64 mode whatever eltype(theta).
         self.precision = precision
+        # Gauss-Legendre nodes per `Integral` term (the engine's fixed rule in place of the reference's adaptive cubature,
+        # src/discretize.jl:355-396); handle option "integral_nodes"
+        if int(integral_nodes) != integral_nodes or not 2 <= int(integral_nodes) <= 64:
+            raise ValueError(f"integral_nodes must be an integer in 2..64, not {integral_nodes!r}")
+        self.integral_nodes = int(integral_nodes)
         self.strategy = strategy
         self.init_params = init_params
         self.param_estim = param_estim
@@ -578,6 +583,9 @@ def symbolic_discretize(pde_system: PDESystem, discretization: PhysicsInformedNN
     n_pde, n_bc = len(eqs), len(bcs)
     hints = [s.shape[1] for s in list(pde_sets) + list(bc_sets)] + [np.asarray(dl.values).size for dl in discretization.data_loss]
     engine = _lib.Engine(ir.to_descriptor2(hints) if _os.environ.get("PINN_DESCRIPTOR") == "2" else ir.to_descriptor(hints))
+
+    if any(t.integrals for t in terms):
+        engine.set_option("integral_nodes", str(getattr(discretization, "integral_nodes", 16)))
 
     def install(pde_sets, bc_sets):
         for k, s in enumerate(list(pde_sets) + list(bc_sets)):

@@ -4,7 +4,8 @@ The Julia glue (julia/NeuralPDEHIP.jl: `sexpr`) prints the Expr trees the refere
 and `toexpr(expand_derivatives(eq.rhs))` (src/symbolic_utilities.jl:360-370); this module prints the same shape from sympy trees, so
 that the Python mirror exercises the ONE lowering implementation both hosts share (the C++ restatement of `_transform_expression`,
 src/symbolic_utilities.jl:132-331).  Shape: `(head arg ...)` with heads `+ - * / ^`, function names, dependent-variable names
-(`(u x y)`, `(u 0 y)`) and `(D <variable> <order> <expr>)` for Differentials (nested for mixed derivatives, as Symbolics nests them)."""
+(`(u x y)`, `(u 0 y)`), `(D <variable> <order> <expr>)` for Differentials (nested for mixed derivatives, as Symbolics nests them) and
+`(integral <variable> <lo> <hi> <expr>)` for Integrals over one variable."""
 from __future__ import annotations
 
 import sympy as sp
@@ -32,6 +33,12 @@ def sexpr(e) -> str:
         return _num(e)
     if e.is_Symbol:
         return str(e)
+    if isinstance(e, sp.Integral):                         # (integral <variable> <lo> <hi> <integrand>), one variable
+        if len(e.limits) != 1 or len(e.limits[0]) != 3:
+            raise SexprError(f"cannot print {e}: an integral term runs over one variable with both bounds")
+        var, lo, hi = e.limits[0]
+        bound = lambda b: ("-Inf" if b == -sp.oo else "Inf") if b in (sp.oo, -sp.oo) else sexpr(b)
+        return f"(integral {var} {bound(lo)} {bound(hi)} {sexpr(e.function)})"
     if isinstance(e, sp.Derivative):
         inner = e.expr
         if not isinstance(inner, sp.core.function.AppliedUndef):

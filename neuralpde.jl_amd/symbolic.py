@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import sympy as sp
 
-from .ir import BINARY, Instr, Slot, TermIR
+from .ir import BINARY, Instr, IntegralIR, Slot, TermIR
 
 
 # ------------------------------------------------------------------------------------------------
@@ -51,6 +51,38 @@ class Differential:
 
     def __call__(self, expr):
         return sp.Derivative(expr, (self.var, self.order))
+
+
+@dataclass
+class ProductDomain:
+    """`ProductDomain(ClosedInterval(..), ClosedInterval(..))` — [3P] DomainSets: the domain of the reference's multi-variable integrals."""
+    intervals: Sequence
+
+    def __init__(self, *intervals):
+        self.intervals = tuple(intervals)
+
+
+class Integral:
+    """`Integral(s in ClosedInterval(lo, hi))` — [3P] Symbolics; the reference's integro-differential terms (src/discretize.jl:355-396).
+    `Integral(In(t, Interval(0.0, t)))(i(t))` is the integral of the expression over ONE independent variable; each bound is a finite
+    number or an independent variable (the integration variable itself included, as in the reference's `0..t`).  The engine evaluates it
+    with a fixed Gauss-Legendre rule of `integral_nodes` nodes (PhysicsInformedNN(..., integral_nodes=Q)), not with adaptive cubature."""
+
+    def __init__(self, domain):
+        if not isinstance(domain, VarDomain):
+            raise LoweringError("Integral takes `In(variable, Interval(lo, hi))`")
+        if isinstance(domain.domain, ProductDomain) or isinstance(domain.variable, (tuple, list)):
+            raise LoweringError("multi-variable integrals (ProductDomain) are not supported by the HIP engine: an integral term runs over ONE independent variable")
+        if not isinstance(domain.variable, sp.Symbol):
+            raise LoweringError("Integral: the integration variable must be an independent variable")
+        self.var = domain.variable
+        self.lo, self.hi = sp.sympify(domain.domain.lo), sp.sympify(domain.domain.hi)
+
+    def __call__(self, expr):
+        expr = sp.sympify(expr)
+        if expr.has(sp.Integral):
+            raise LoweringError("nested integrals are not supported by the HIP engine (one integration variable per integral term)")
+        return sp.Integral(expr, (self.var, self.lo, self.hi))
 
 
 @dataclass
@@ -209,8 +241,10 @@ class _Builder:
         self.slots: List[Slot] = []
         self.ops: List[Instr] = []
         self.memo: Dict[object, Tuple[str, int]] = {}
+        self.integrals: List[IntegralIR] = []
+        self.inner = False                      # this builder lowers an integrand
 
-    # references are ('x', i) coordinate, ('p', i) parameter, ('s', i) slot, ('o', i) op
+    # references are ('x', i) coordinate, ('p', i) parameter, ('s', i) slot, ('i', i) integral node, ('o', i) op
     def slot(self, s: Slot):
         if s not in self.slots:
             self.slots.append(s)
@@ -245,6 +279,45 @@ class _Builder:
         # of order >= 3, orders 5-6: the reference's recursion takes them all, src/pinn_types.jl:454-460) gets a generated jet set
         return self.slot(Slot(net, tuple(sorted(axes))))
 
+    def _bound(self, b, what):
+        """A bound of an integral: a finite number, or one of the term's independent variables."""
+        b = sp.sympify(b)
+        if b.is_Symbol and str(b) in self.indvars:
+            return ("x", self.indvars.index(str(b)))
+        if b.is_Number or b.is_NumberSymbol:
+            if not b.is_finite:
+                raise LoweringError(f"integral with an infinite {what} bound: the reference's change of variables for infinite domains "
+                                    "(transform_inf_integral.jl) is not supported by the HIP engine; bounds must be finite")
+            return float(b)
+        raise LoweringError(f"integral {what} bound `{b}` is a general expression: a bound must be a finite number or an independent variable of the term")
+
+    def _integral(self, e):
+        """One integral node: bounds, and the integrand as a tape of its own over [coordinates with s substituted | parameters | its slots]."""
+        if self.inner or e.function.has(sp.Integral):
+            raise LoweringError("nested integrals are not supported by the HIP engine (one integration variable per integral term)")
+        if len(e.limits) != 1:
+            raise LoweringError("multi-variable integrals (ProductDomain) are not supported by the HIP engine: an integral term runs over ONE independent variable")
+        lim = e.limits[0]
+        if len(lim) != 3:
+            raise LoweringError(f"integral without both bounds: {e}")
+        var, lo, hi = lim
+        if str(var) not in self.indvars:
+            raise LoweringError(f"integration variable {var} is not an independent variable of this term {self.indvars}")
+        B = _Builder(self.vi, self.indvars, self.params)
+        B.inner = True
+        out = B.lower(e.function)
+        if not B.slots:
+            raise LoweringError(f"the integrand of {e} does not contain a dependent variable: integrate it symbolically")
+        if out[0] != "o":
+            out = B.emit("ADDC", out, imm=0.0)
+        d, NP, S = len(self.indvars), len(self.params), len(B.slots)
+        row = lambda ref: {"x": ref[1], "p": d + ref[1], "s": d + NP + ref[1], "o": d + NP + S + ref[1]}[ref[0]]
+        ops = [Instr(op, row(a) if a is not None else 0, row(b) if (b is not None and op in BINARY) else 0, imm) for (op, a, b, imm) in B.ops]
+        node = IntegralIR(var=self.indvars.index(str(var)), lo=self._bound(lo, "lower"), hi=self._bound(hi, "upper"),
+                          slots=list(B.slots), ops=ops, out_row=row(out))
+        self.integrals.append(node)
+        return ("i", len(self.integrals) - 1)
+
     def _lower(self, e):
         if e.is_Number or e.is_NumberSymbol:
             return self.const(float(e))
@@ -255,10 +328,14 @@ class _Builder:
             if n in self.params:
                 return ("p", self.params.index(n))
             raise LoweringError(f"symbol {n} is neither an independent variable of this term {self.indvars} nor a parameter")
+        if isinstance(e, sp.Integral):
+            return self._integral(e)
         if isinstance(e, sp.Derivative):
             inner = e.expr
             if isinstance(inner, sp.core.function.AppliedUndef) and str(inner.func) in self.vi.dict_depvars:
                 return self._depvar_slot(inner, e.variable_count)
+            if inner.has(sp.Integral):
+                raise LoweringError(f"derivative of an integral term is not supported by the HIP engine: {e}")
             d = e.doit()
             if isinstance(d, sp.Derivative) and d == e:
                 raise LoweringError(f"cannot expand derivative {e}")
@@ -354,14 +431,14 @@ def lower_equation(eq: Equation, vi: VarInfo, params: Sequence, kind: str) -> Te
         raise LoweringError("equation does not contain a dependent variable")
     # an identically-zero residual (e.g. `u(0.0) ~ u(0.0)`, test/Forward/forward__ode.jl:12) is legal
     out = B.lower(sp.sympify(expr))
-    if not B.slots:     # residual simplified to a constant: still bind the term to its network
+    if not B.slots and not B.integrals:     # residual simplified to a constant: still bind the term to its network
         first = _depvar_calls(sp.Add(eq.lhs, -eq.rhs, evaluate=False), vi)[0]
         B.slot(Slot(vi.dict_depvars[str(first.func)] - 1, ()))
-    d, NP, S = len(indvars), len(pnames), len(B.slots)
+    d, NP, S, NI = len(indvars), len(pnames), len(B.slots), len(B.integrals)
 
-    def row(ref):
+    def row(ref):       # an integral node is a row of the outer tape like a jet slot: rows [d+NP+S, d+NP+S+NI)
         k, i = ref
-        return {"x": i, "p": d + i, "s": d + NP + i, "o": d + NP + S + i}[k]
+        return {"x": i, "p": d + i, "s": d + NP + i, "i": d + NP + S + i, "o": d + NP + S + NI + i}[k]
 
     if out[0] != "o":        # residual is a bare input row: materialise it
         out = B.emit("ADDC", out, imm=0.0)
@@ -371,7 +448,7 @@ def lower_equation(eq: Equation, vi: VarInfo, params: Sequence, kind: str) -> Te
     # every dependent variable gets its own rows of `cord` (src/discretize.jl:111-131): inputs of net k = the term's
     # coordinates named by dict_depvar_input[depvar k]
     inmaps = {}
-    for sl in B.slots:
+    for sl in list(B.slots) + [sl for node in B.integrals for sl in node.slots]:
         if sl.net in inmaps:
             continue
         name = vi.depvars[sl.net]
@@ -384,4 +461,4 @@ def lower_equation(eq: Equation, vi: VarInfo, params: Sequence, kind: str) -> Te
     except SexprError:
         ls = rs = None
     return TermIR(dim=d, slots=list(B.slots), ops=ops, out_row=row(out), indvars=tuple(indvars), kind=kind,
-                  source=str(expr), inmaps=inmaps, lhs_sexpr=ls, rhs_sexpr=rs)
+                  source=str(expr), inmaps=inmaps, lhs_sexpr=ls, rhs_sexpr=rs, integrals=list(B.integrals))
