@@ -279,6 +279,46 @@ int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int histor
                int* iters_done);
 
 /*
+ * RESIDENT HMC: the transition loop of the BPINN sampler (`ahmc_bayesian_pinn_pde` with Kernel = HMC(eps, n_leapfrog),
+ * ext/bpinn/PDE_BPINN.jl:371-640) on the device.  theta, momentum, the diagonal inverse metric, the log-posterior gradient and the energies stay in
+ * HBM in double; pinn_hmc_draws runs `ndraws` complete transitions — momentum draw, n_leapfrog leapfrog steps, Metropolis accept / reject — without
+ * a host synchronisation and downloads everything once at its end.  A leapfrog step is the handle's own resident evaluation (the double kernels in
+ * float64 mode; the fp32 kernels at (float)theta otherwise, their K sums of squares in double) plus one fused update launch.  Opt-in: nothing else in
+ * the library uses it.  The state has buffers of its own — evaluations and pinn_adam_* between two calls leave the chain alone and vice versa.
+ *   log-posterior  logp(theta) = loglik(theta)                                         exactly pinn_loglik_grad's number for stds[0..k)
+ *                               + sum_{i < P - n_prior} logpdf(Normal(nn_mu, nn_sigma), theta_i)          the network weights
+ *                               + sum_{j < n_prior} logpdf(prior_j, theta_{P - n_prior + j})             the trailing PDE parameters;
+ *                  prior_kind[j] = 0: Normal(prior_mu[j], prior_sigma[j]); 1: LogNormal(prior_mu[j], prior_sigma[j]) — its log-density at x <= 0 is
+ *                  -inf (gradient 0), so a proposal that carries the parameter there is rejected.
+ *   transition     r = z / sqrt(minv), z ~ N(0, I);  H = -logp + 1/2 sum_i minv_i r_i^2;
+ *                  r += eps/2 grad logp;  then n_leapfrog times { theta += eps minv r;  evaluate;  r += eps grad logp (eps/2 the last time) };
+ *                  a = exp(min(0, H_old - H_new)), a = 0 when H_new is not finite;  accept iff u < a, u ~ U[0, 1).
+ *   pinn_hmc_init        uploads theta (p doubles), checks and stores stds (k == pinn_num_terms) and the priors, evaluates logp and its gradient
+ *                        at theta once, sets the unit metric and the draw counter 0.  A second call replaces the state.
+ *   pinn_hmc_set_metric  p positive entries of the diagonal inverse mass matrix; NULL: ones.
+ *   pinn_hmc_draws       momenta: ndraws x p doubles, row i = the momentum r of draw i (used as given), or NULL; uniforms: ndraws doubles or NULL;
+ *                        samples (nullable): ndraws x p, row i = the state AFTER draw i; accept_prob[i] = a of draw i; logp[i] = logp of that state.
+ *   pinn_hmc_get         the current state: theta (p doubles), *logp (nullable), grad = d logp / d theta (p doubles, nullable).
+ * GENERATOR (momenta / uniforms == NULL), counter-based, all arithmetic in uint32 (wrapping) and double:
+ *     mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16                  (csrc/sample_rules.hpp)
+ *     key     = mix32( mix32(seed_lo + 0x9E3779B9 * seed_hi) ^ (c * 0x85EBCA6B + 0xC2B2AE35) )              c = draw counter, seed = seed_hi : seed_lo
+ *     word(e, j) = mix32( key ^ mix32((2 e + j) * 0x9E3779B9 + 0x165667B1) )
+ *     z_e     = sqrt(-2 ln((word(e, 0) + 1) / 2^32)) * cos(6.283185307179586 * (word(e, 1) / 2^32))         Box-Muller, element e of theta
+ *     u       = word(P, 0) / 2^32
+ *   The draw counter lives in the handle, starts at 0 in pinn_hmc_init and advances by one per completed draw (also when momenta and uniforms are
+ *   supplied): 2 + 3 draws in two calls are bit-equal to 5 draws in one.
+ * Refused, with the handle left as it was: any call before pinn_hmc_init; a handle whose precision mode changed since (init again); a term with a
+ * device sampler (the target must be fixed, as for pinn_lbfgs); a handle on a communicator; p != ntheta, k != the number of terms; stds, prior
+ * sigmas or metric entries that are not positive; eps <= 0, n_leapfrog < 1, ndraws < 1.
+ */
+int pinn_hmc_init(pinn_handle h, const double* theta, int64_t p, const double* stds, int k, double nn_mu, double nn_sigma,
+                  int n_prior, const int* prior_kind, const double* prior_mu, const double* prior_sigma);
+int pinn_hmc_set_metric(pinn_handle h, const double* inv_metric, int64_t p);
+int pinn_hmc_draws(pinn_handle h, int ndraws, int n_leapfrog, double eps, uint64_t seed, const double* momenta, const double* uniforms,
+                   double* samples, int64_t p, double* accept_prob, double* logp);
+int pinn_hmc_get(pinn_handle h, double* theta, int64_t p, double* logp, double* grad);
+
+/*
  * Run-time options of a handle.  "gemm" = arithmetic of the hidden-layer GEMMs of the 64- / 128-wide (neuron-split) kernels:
  *   "split" (default) — every fp32 product rebuilt from three bf16 pieces per operand on the bf16 matrix pipe (6 MFMAs, fp32 accumulation):
  *                       2-4 x the rounding error of an fp32 fmaf chain, ~1.35 x faster (error budget: DESIGN.md section 6);

@@ -315,6 +315,49 @@ function loglik_grad(e::HIPEngine, θ::AbstractVector{<:Real}, stds::AbstractVec
     return ll[], g, gs
 end
 
+"""
+    hmc_init(e, θ, stds; nn_prior = (0.0, 2.0), param_priors = ())
+    hmc_set_metric(e, inv_metric)            # `nothing`: unit metric
+    hmc_draws(e, ndraws, n_leapfrog, ϵ; seed = 0, momenta = nothing, uniforms = nothing) -> (samples P × ndraws, accept_prob, logp)
+    hmc_get(e) -> (θ, logp, ∇logp)
+
+The resident HMC transition loop (`pinn_hmc_*`, DESIGN.md §4.7): `Kernel = HMC(ϵ, n_leapfrog)` of `ahmc_bayesian_pinn_pde`
+(ext/bpinn/PDE_BPINN.jl:371-640) with θ, momentum, metric, gradient and energies on the device; `ndraws` transitions per call, one download.
+`param_priors`: one `(kind, μ, σ)` per trailing PDE parameter, kind 0 = Normal, 1 = LogNormal.
+"""
+function hmc_init(e::HIPEngine, θ::AbstractVector{<:Real}, stds::AbstractVector{<:Real}; nn_prior = (0.0, 2.0), param_priors = ())
+    θ64 = Vector{Float64}(θ); sd = Vector{Float64}(stds)
+    kd = Int32[Int32(q[1]) for q in param_priors]; mu = Float64[q[2] for q in param_priors]; sg = Float64[q[3] for q in param_priors]
+    GC.@preserve θ64 sd kd mu sg check(ccall(sym(:pinn_hmc_init), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Cint, Cdouble, Cdouble, Cint, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+        e.h, θ64, e.P, sd, length(sd), Float64(nn_prior[1]), Float64(nn_prior[2]), length(kd), kd, mu, sg), "pinn_hmc_init")
+    return nothing
+end
+
+function hmc_set_metric(e::HIPEngine, inv_metric)
+    m = inv_metric === nothing ? Float64[] : Vector{Float64}(inv_metric)
+    GC.@preserve m check(ccall(sym(:pinn_hmc_set_metric), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64),
+        e.h, inv_metric === nothing ? Ptr{Float64}(C_NULL) : pointer(m), e.P), "pinn_hmc_set_metric")
+    return nothing
+end
+
+function hmc_draws(e::HIPEngine, ndraws::Integer, n_leapfrog::Integer, ϵ::Real; seed::Integer = 0, momenta = nothing, uniforms = nothing)
+    mom = momenta === nothing ? Float64[] : Vector{Float64}(vec(momenta)); uni = uniforms === nothing ? Float64[] : Vector{Float64}(uniforms)
+    samples = zeros(Float64, e.P, ndraws); acc = zeros(Float64, ndraws); lp = zeros(Float64, ndraws)
+    GC.@preserve mom uni samples acc lp check(ccall(sym(:pinn_hmc_draws), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cdouble, UInt64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+        e.h, ndraws, n_leapfrog, Float64(ϵ), UInt64(seed), momenta === nothing ? Ptr{Float64}(C_NULL) : pointer(mom),
+        uniforms === nothing ? Ptr{Float64}(C_NULL) : pointer(uni), samples, e.P, acc, lp), "pinn_hmc_draws")
+    return samples, acc, lp
+end
+
+function hmc_get(e::HIPEngine)
+    θ = zeros(Float64, e.P); g = zeros(Float64, e.P); lp = Ref{Float64}(0.0)
+    GC.@preserve θ g check(ccall(sym(:pinn_hmc_get), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}, Ptr{Float64}),
+        e.h, θ, e.P, lp, g), "pinn_hmc_get")
+    return θ, lp[], g
+end
+
 # ------------------------------------------------------------------------------------------------
 # 1. s-expression printer of the Julia Expr trees `toexpr` returns
 # ------------------------------------------------------------------------------------------------

@@ -38,6 +38,7 @@ SYMBOLS = [
     "pinn_adam_init_f64", "pinn_adam_get_f64", "pinn_set_point_data_f64", "pinn_loss_grad_device_f64",
     "pinn_residual_f64", "pinn_phi_f64", "pinn_derivative_f64", "pinn_term_grads_f64", "pinn_loglik_grad_f64",
     "pinn_loss_grad_sharded_device_f64", "pinn_loss_grad_sharded_f64",
+    "pinn_hmc_init", "pinn_hmc_set_metric", "pinn_hmc_draws", "pinn_hmc_get",
 ]
 
 
@@ -109,6 +110,13 @@ class Library:
             L.pinn_loglik_grad_f64.argtypes = [vp, dp, C.c_int64, dp, dp, dp, dp]
             L.pinn_loss_grad_sharded_device_f64.argtypes = [vp, vp, fp, vp, vp]
             L.pinn_loss_grad_sharded_f64.argtypes = [C.POINTER(vp), C.c_int, dp, C.c_int64, dp, dp, dp]
+        except AttributeError:
+            pass
+        try:                                     # (resident HMC: variant libraries built before it still load)
+            L.pinn_hmc_init.argtypes = [vp, dp, C.c_int64, dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), dp, dp]
+            L.pinn_hmc_set_metric.argtypes = [vp, dp, C.c_int64]
+            L.pinn_hmc_draws.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint64, dp, dp, dp, C.c_int64, dp, dp]
+            L.pinn_hmc_get.argtypes = [vp, dp, C.c_int64, dp, dp]
         except AttributeError:
             pass
         L.pinn_lbfgs.argtypes = [vp, C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_double, fp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -521,6 +529,49 @@ class Engine:
                                            w.ctypes.data_as(C.POINTER(C.c_float)) if w is not None else None,
                                            hist.ctypes.data_as(C.POINTER(C.c_double)), C.byref(done)), "pinn_lbfgs")
         return th, hist[:done.value]
+
+    # ---- resident HMC (include/pinn_hip.h: pinn_hmc_*) ----
+    def hmc_init(self, theta, stds, nn_prior=(0.0, 2.0), param_priors=()):
+        """`pinn_hmc_init`: put a chain at theta.  stds: one per loss term; nn_prior = (mu, sigma) of the Normal prior on the network weights;
+        param_priors: one (kind, mu, sigma) per trailing PDE parameter, kind 0 / "normal" or 1 / "lognormal"."""
+        th, sd = _f64(theta), _f64(stds).reshape(-1)
+        kinds = {"normal": 0, "lognormal": 1}
+        kd = np.ascontiguousarray([kinds.get(str(q[0]).lower(), q[0]) for q in param_priors], dtype=np.int32)
+        mu, sg = _f64([q[1] for q in param_priors]), _f64([q[2] for q in param_priors])
+        dp = C.POINTER(C.c_double)
+        self.L.check(self.L.lib.pinn_hmc_init(self.h, th.ctypes.data_as(dp), th.size, sd.ctypes.data_as(dp), sd.size, float(nn_prior[0]), float(nn_prior[1]),
+                                              kd.size, kd.ctypes.data_as(C.POINTER(C.c_int)) if kd.size else None,
+                                              mu.ctypes.data_as(dp) if kd.size else None, sg.ctypes.data_as(dp) if kd.size else None), "pinn_hmc_init")
+
+    def hmc_set_metric(self, inv_metric=None):
+        """`pinn_hmc_set_metric`: the diagonal inverse mass matrix (None: ones)"""
+        m = None if inv_metric is None else _f64(inv_metric).reshape(-1)
+        self.L.check(self.L.lib.pinn_hmc_set_metric(self.h, m.ctypes.data_as(C.POINTER(C.c_double)) if m is not None else None,
+                                                    m.size if m is not None else self.P), "pinn_hmc_set_metric")
+
+    def hmc_draws(self, ndraws: int, n_leapfrog: int, eps: float, seed: int = 0, momenta=None, uniforms=None, want_samples: bool = True):
+        """`pinn_hmc_draws`: `ndraws` transitions on the device, one download.  Returns (samples [ndraws x P] or None, accept_prob, logp).
+        momenta ([ndraws x P]) / uniforms ([ndraws]) replace the device generator's draws when given."""
+        nd, dp = max(int(ndraws), 0), C.POINTER(C.c_double)
+        mom = None if momenta is None else _f64(momenta).reshape(-1)
+        uni = None if uniforms is None else _f64(uniforms).reshape(-1)
+        if (mom is not None and mom.size != nd * self.P) or (uni is not None and uni.size != nd):
+            raise ValueError("momenta: ndraws x P values, uniforms: ndraws values")
+        smp = np.zeros((nd, self.P), dtype=np.float64) if want_samples else None
+        acc, lp = np.zeros(nd, dtype=np.float64), np.zeros(nd, dtype=np.float64)
+        self.L.check(self.L.lib.pinn_hmc_draws(self.h, int(ndraws), int(n_leapfrog), float(eps), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                               mom.ctypes.data_as(dp) if mom is not None else None, uni.ctypes.data_as(dp) if uni is not None else None,
+                                               smp.ctypes.data_as(dp) if smp is not None else None, self.P, acc.ctypes.data_as(dp), lp.ctypes.data_as(dp)),
+                     "pinn_hmc_draws")
+        return smp, acc, lp
+
+    def hmc_get(self, want_grad: bool = True):
+        """`pinn_hmc_get`: (theta, logp, d logp / d theta) of the chain's current state"""
+        th = np.zeros(self.P, dtype=np.float64)
+        g = np.zeros(self.P, dtype=np.float64) if want_grad else None
+        lp, dp = C.c_double(), C.POINTER(C.c_double)
+        self.L.check(self.L.lib.pinn_hmc_get(self.h, th.ctypes.data_as(dp), th.size, C.byref(lp), g.ctypes.data_as(dp) if g is not None else None), "pinn_hmc_get")
+        return th, lp.value, g
 
     def adam_init_f64(self, theta):
         th = _f64(theta)

@@ -11,8 +11,10 @@ i.e. an affine function of the per-term sums of squares the engine already retur
     grad_theta sum_k l_k = - grad_theta sum_k w_k L_k        with  w_k = N_k / (2 sigma_k^2),
 
 which is one `pinn_loss_grad` call with those term weights (reverse mode over all P parameters, where the reference
-uses forward-mode ForwardDiff over every parameter of the network).  Priors, the data likelihood (`L2LossData`) and the
-HMC/NUTS sampler itself stay on the host as in the reference.
+uses forward-mode ForwardDiff over every parameter of the network).  By default the priors and the HMC sampler itself stay on the
+host as in the reference (`sampler="host"`: one device evaluation and one host round trip per leapfrog step).  `sampler="device"` runs the
+transitions on the device (`pinn_hmc_*`): theta, momentum, metric, gradient and energies stay resident, a call
+makes many draws and downloads once; the step-size search, dual averaging and the windowed metric stay here in Python.
 """
 from __future__ import annotations
 
@@ -125,6 +127,71 @@ def _hmc(logp_grad, theta0, draw_samples, n_leapfrog, eps0, target, rng, n_adapt
     return np.asarray(samples), {"acceptance": np.asarray(accs), "step_size": eps, "inv_metric": minv, "n_adapts": n_adapts}
 
 
+def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, eps0, target, rng, seed, n_adapts=None, chunk=256):
+    """`_hmc` with the transitions on the device (Engine.hmc_*): the same initial step-size search on the host evaluation path (at most 42
+    evaluations), the same dual averaging and windowed metric in Python around `hmc_draws(1, ...)` during adaptation (a new metric goes down
+    through `hmc_set_metric`), then the remaining draws in chunks of `chunk`.  Momenta and uniforms come from the device generator (`seed`)."""
+    n = theta0.size
+    n_adapts = min(draw_samples // 10, 1000) if n_adapts is None else n_adapts
+    th = theta0.astype(np.float64).copy()
+    lp, g = logp_grad(th)
+    minv = np.ones(n)
+
+    def one_step(r, eps):
+        r = r + 0.5 * eps * g
+        t1 = th + eps * minv * r
+        lp1, g1 = logp_grad(t1)
+        r = r + 0.5 * eps * g1
+        return -lp1 + 0.5 * np.sum(minv * r * r)
+
+    eps = eps0
+    r0 = rng.standard_normal(n) / np.sqrt(minv)
+    h0 = -lp + 0.5 * np.sum(minv * r0 * r0)
+    d = h0 - one_step(r0, eps)
+    direction = 1.0 if (np.isfinite(d) and d > np.log(0.8)) else -1.0
+    for _ in range(40):
+        eps *= 2.0 ** direction
+        d = h0 - one_step(r0, eps)
+        if not np.isfinite(d):
+            d = -np.inf
+        if (direction > 0) == (d <= np.log(0.8)):
+            break
+    init_chain(th)
+    mu, hbar, log_eps_bar, t0, gamma, kappa = np.log(10 * eps), 0.0, 0.0, 10.0, 0.05, 0.75
+    w0, w1 = int(0.15 * n_adapts), int(0.9 * n_adapts)
+    win, samples, accs = [], [], []
+    m_count = 0
+    for it in range(min(n_adapts, draw_samples)):
+        smp, acc, _ = eng.hmc_draws(1, n_leapfrog, eps, seed)
+        th, a = smp[0], float(acc[0])
+        samples.append(th)
+        accs.append(a)
+        m_count += 1
+        hbar = (1 - 1 / (m_count + t0)) * hbar + (target - a) / (m_count + t0)
+        log_eps = mu - np.sqrt(m_count) / gamma * hbar
+        eta = m_count ** (-kappa)
+        log_eps_bar = eta * log_eps + (1 - eta) * log_eps_bar
+        eps = float(np.exp(log_eps))
+        if w0 <= it < w1:
+            win.append(th)
+        if it == w1 - 1 and len(win) >= 8 and n_adapts >= 100:
+            var = np.var(np.asarray(win), axis=0)
+            k = len(win)
+            minv = (k / (k + 5.0)) * var + 1e-3 * (5.0 / (k + 5.0))
+            eng.hmc_set_metric(minv)
+            mu, hbar, log_eps_bar, m_count = np.log(10 * eps), 0.0, 0.0, 0
+        if it == n_adapts - 1:
+            eps = float(np.exp(log_eps_bar)) if m_count > 0 else eps
+    done = len(samples)
+    while done < draw_samples:
+        nd = min(int(chunk), draw_samples - done)
+        smp, acc, _ = eng.hmc_draws(nd, n_leapfrog, eps, seed)
+        samples.extend(smp)
+        accs.extend(acc)
+        done += nd
+    return np.asarray(samples), {"acceptance": np.asarray(accs), "step_size": eps, "inv_metric": minv, "n_adapts": n_adapts}
+
+
 class LogNormal:
     """[3P] Distributions.LogNormal(mu, sigma) as a parameter prior (`param = [LogNormal(6.0, 0.5)]`, test/PDEBPINN/bpinn_pde__bpinn_pde_inv_i_*.jl:58)."""
 
@@ -156,7 +223,8 @@ class Normal:
 
 
 def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, bcstd=(0.01,), l2std=(0.05,), phystd=(0.05,), priorsNNw=(0.0, 2.0),
-                           param=(), n_leapfrog=30, step_size=0.1, targetacceptancerate=0.8, saveats=(0.1,), numensemble=None, rng=None):
+                           param=(), n_leapfrog=30, step_size=0.1, targetacceptancerate=0.8, saveats=(0.1,), numensemble=None, rng=None,
+                           sampler="host", seed=0):
     """`ahmc_bayesian_pinn_pde(pde_system, discretization; draw_samples, bcstd, phystd, priorsNNw, Kernel = HMC(0.1, 30), saveats,
     numensemble)` — the forward-problem form of ext/bpinn/PDE_BPINN.jl:371-640: the posterior over the network parameters is
     prior N(priorsNNw[1], priorsNNw[2]^2 I) x physics likelihood (`pinn_loglik_grad`: every leapfrog step is ONE fused device evaluation,
@@ -164,8 +232,13 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
     the ensemble statistics run on the host, as in the reference.  `discretization`: a PhysicsInformedNN with fixed point sets (the
     reference's BayesianPINN takes GridTraining).  Inverse problems: `param = [prior of every PDE parameter]` (the chain starts at the
     priors' first parameter, as in the reference), the discretization built with `param_estim = True` and the observations as `data_loss`
-    terms (the reference's `dataset`), whose standard deviations are `l2std` — the L2 data term then sits in the same fused device call."""
-    rng = np.random.default_rng() if rng is None else rng
+    terms (the reference's `dataset`), whose standard deviations are `l2std` — the L2 data term then sits in the same fused device call.
+    `sampler = "device"` runs the transitions resident on the device (`pinn_hmc_*`; momenta and uniforms from its counter-based generator
+    keyed by `seed`, the host `rng` — default_rng(seed) unless given — only feeds the initial step-size search); `stats["sampler"]` says which ran."""
+    if sampler not in ("host", "device"):
+        raise ValueError(f"sampler must be \"host\" or \"device\", not {sampler!r}")
+    if rng is None:
+        rng = np.random.default_rng() if sampler == "host" else np.random.default_rng(seed)
     rep = npde.symbolic_discretize(pde_system, discretization)
     eng = rep.engine
     n_pde, n_bc = len(rep.eqs), len(rep.bcs)
@@ -198,7 +271,17 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
     theta0 = np.asarray(rep.flat_init_params, dtype=np.float64).copy()
     for j, pr in enumerate(param):
         theta0[nn + j] = pr.params()[0]
-    samples, stats = _hmc(logp_grad, theta0, int(draw_samples), int(n_leapfrog), float(step_size), float(targetacceptancerate), rng)
+    if sampler == "device":
+        kinds = []
+        for pr in param:
+            if not isinstance(pr, (Normal, LogNormal)):
+                raise ValueError("sampler=\"device\": parameter priors must be Normal or LogNormal")
+            kinds.append((1 if isinstance(pr, LogNormal) else 0,) + tuple(pr.params()))
+        samples, stats = _hmc_device(eng, logp_grad, theta0, lambda th: eng.hmc_init(th, stds, (mu0, sd0), kinds), int(draw_samples), int(n_leapfrog),
+                                     float(step_size), float(targetacceptancerate), rng, int(seed))
+    else:
+        samples, stats = _hmc(logp_grad, theta0, int(draw_samples), int(n_leapfrog), float(step_size), float(targetacceptancerate), rng)
+    stats["sampler"] = sampler
     numensemble = int(draw_samples // 3) if numensemble is None else int(numensemble)
     # inference: the last `numensemble` draws on the saveats grid (one spacing per independent variable), per dependent variable
     doms = {str(d.variable): (float(d.domain.lo), float(d.domain.hi)) for d in pde_system.domain}

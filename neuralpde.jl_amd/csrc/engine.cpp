@@ -5,6 +5,7 @@
 // and what it does per optimiser iteration (src/discretize.jl:567-598).
 #include "engine_types.hpp"
 #include "aux_kernels.hpp"
+#include "hmc_kernels.hpp"
 
 #include <type_traits>
 
@@ -490,6 +491,8 @@ int pe::upload_theta(pinn_engine& E, const float* theta, int64_t p) {
 // =================================================================================================
 // C ABI
 // =================================================================================================
+static void hmc_free(pinn_engine& E);
+
 extern "C" {
 
 const char* pinn_backend(void) { return plat_name(); }
@@ -558,6 +561,7 @@ int pinn_destroy(pinn_handle h) {
     DeviceScope scope(E.device);
     pinn_comm_destroy(h);
     plat_sync(E.stream);
+    hmc_free(E);
     f64_destroy(E);
     free_plan(E);
     for (auto& T : E.terms) { plat_free(T.d_pts); plat_free(T.d_upts); plat_free(T.d_resid); plat_free(T.d_lb); plat_free(T.d_ub); plat_free(T.d_data); plat_free(T.d_pw); }
@@ -2213,6 +2217,238 @@ int pinn_adam_init(pinn_handle h, const float* theta, int64_t p) { return adam_i
 int pinn_adam_init_f64(pinn_handle h, const double* theta, int64_t p) { return adam_init_twin(__func__, h, theta, p); }
 int pinn_adam_get(pinn_handle h, float* theta, int64_t p) { return adam_get_twin(__func__, h, theta, p); }
 int pinn_adam_get_f64(pinn_handle h, double* theta, int64_t p) { return adam_get_twin(__func__, h, theta, p); }
+
+}  // extern "C"
+
+// =================================================================================================
+// Resident HMC (pinn_hmc_*): the transition loop of neuralpde.jl_amd/bpinn.py `_hmc` with the chain on the device.
+// A leapfrog step = the handle's resident evaluation (float64 mode: f64_eval_resident; otherwise run_loss_grad at the narrowed copy of theta,
+// with the K sums in double) + ONE update launch (hmc_kernels.hpp); nothing is read back before the single download that ends pinn_hmc_draws.
+// The state has buffers of its own: evaluations and optimiser runs between two calls do not touch the chain, and the chain does not touch them.
+// =================================================================================================
+namespace {
+
+struct HmcState {
+    bool f64 = false;                    // the precision mode the state was initialised in
+    hmc::Args a;
+    std::vector<double> w64;             // term weights N_k / (2 s_k^2) of the evaluation, as pinn_loglik_grad forms them
+    std::vector<float> w32;
+    double* d_state = nullptr;           // [6 P + SC_COUNT]: th_cur | th_prop | r | g_cur | g_prop | minv | scalars
+    double* d_tab = nullptr;             // [3 n_prior + 3 K]: prior mu | prior sigma | lik_c | lik_d | lik_n (+ kinds as ints in d_kind)
+    int* d_kind = nullptr;
+    double* d_ev64 = nullptr;            // float64 mode: [P + K] gradient | raw sums of the running evaluation
+    float* d_ev32 = nullptr;             // fp32 mode: [P + K] floats, the K sums again as doubles in d_raw, the narrowed theta in d_th32
+    double* d_raw = nullptr;
+    float* d_th32 = nullptr;
+    double* d_samples = nullptr; double* d_stat = nullptr; double* d_mom = nullptr; double* d_uni = nullptr;
+    size_t samples_cap = 0, stat_cap = 0, mom_cap = 0, uni_cap = 0;
+    unsigned long long draws = 0;        // draw counter of the generator (advanced per completed draw, whatever supplies momenta and uniforms)
+};
+
+void hmc_release(HmcState* H) {
+    if (!H) return;
+    plat_free(H->d_state); plat_free(H->d_tab); plat_free(H->d_kind); plat_free(H->d_ev64); plat_free(H->d_ev32); plat_free(H->d_raw); plat_free(H->d_th32);
+    plat_free(H->d_samples); plat_free(H->d_stat); plat_free(H->d_mom); plat_free(H->d_uni);
+    delete H;
+}
+
+bool hmc_grow(double*& p, size_t& cap, size_t need, plat_stream st) {
+    if (cap >= need) return true;
+    plat_sync(st);
+    plat_free(p);
+    p = (double*)plat_malloc(sizeof(double) * need);
+    cap = p ? need : 0;
+    return p != nullptr;
+}
+
+// what every pinn_hmc_* call after init checks first; leaves the handle as it is
+int hmc_ready(pinn_engine& E, const char* who) {
+    if (!E.hmc) return fail(std::string(who) + ": no sampler state (call pinn_hmc_init first)");
+    if (((HmcState*)E.hmc)->f64 != (E.f64 != nullptr))
+        return fail(std::string(who) + ": the handle's precision changed since pinn_hmc_init (call pinn_hmc_init again)");
+    return 0;
+}
+int hmc_refuse_target(pinn_engine& E, const char* who) {
+    if (E.comm) return fail(std::string(who) + ": the handle belongs to a communicator; the resident sampler runs single-device chains only");
+    for (auto& T : E.terms)
+        if (T.sampler != 0) return fail(std::string(who) + ": a term redraws its points on the device; HMC needs a fixed target (fixed point sets)");
+    return 0;
+}
+
+// one evaluation at the proposal (already in the buffer the evaluation reads): [gradient | sums] into the sampler's vector
+int hmc_eval(pinn_engine& E, HmcState& H) {
+    if (H.f64) return f64_eval_resident(E, H.w64.data(), H.d_ev64);
+    return run_loss_grad(E, H.d_th32, H.d_ev32, H.w32.data(), -1, false, H.d_raw);
+}
+void hmc_leap(pinn_engine& E, HmcState& H, bool from_eval, double kick, double eps, int drift) {
+    if (H.f64) hmc::launch_leap<double>(H.a, from_eval ? H.d_ev64 : nullptr, kick, eps, drift, E.stream);
+    else hmc::launch_leap<float>(H.a, from_eval ? H.d_ev32 : nullptr, kick, eps, drift, E.stream);
+}
+const double* hmc_sse(const HmcState& H) { return H.f64 ? H.d_ev64 + H.a.P : H.d_raw; }
+
+}  // namespace
+
+static void hmc_free(pinn_engine& E) {
+    hmc_release((HmcState*)E.hmc);
+    E.hmc = nullptr;
+}
+
+extern "C" {
+
+int pinn_hmc_init(pinn_handle h, const double* theta, int64_t p, const double* stds, int k, double nn_mu, double nn_sigma,
+                  int n_prior, const int* prior_kind, const double* prior_mu, const double* prior_sigma) {
+    const char* who = "pinn_hmc_init";
+    if (!h || !theta || !stds) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (check_theta(E, who, p)) return 1;
+    const int K = (int)E.terms.size();
+    if (k != K) return fail(std::string(who) + ": " + std::to_string(k) + " standard deviations for " + std::to_string(K) + " loss terms");
+    for (int j = 0; j < K; ++j)
+        if (!(stds[j] > 0.0) || !std::isfinite(stds[j])) return fail(std::string(who) + ": standard deviations must be positive");
+    if (!(nn_sigma > 0.0) || !std::isfinite(nn_sigma) || !std::isfinite(nn_mu)) return fail(std::string(who) + ": the weight prior needs a finite mean and a positive standard deviation");
+    if (n_prior < 0 || n_prior > p) return fail(std::string(who) + ": n_prior must be in 0..P");
+    if (n_prior > 0 && (!prior_kind || !prior_mu || !prior_sigma)) return fail(std::string(who) + ": null prior table");
+    for (int j = 0; j < n_prior; ++j) {
+        if (prior_kind[j] != hmc::PRIOR_NORMAL && prior_kind[j] != hmc::PRIOR_LOGNORMAL) return fail(std::string(who) + ": prior kind must be 0 (Normal) or 1 (LogNormal)");
+        if (!(prior_sigma[j] > 0.0) || !std::isfinite(prior_sigma[j]) || !std::isfinite(prior_mu[j])) return fail(std::string(who) + ": a parameter prior needs a finite mu and a positive sigma");
+    }
+    if (hmc_refuse_target(E, who)) return 1;
+    DeviceScope scope(E.device);
+    if (!E.f64 && ensure_points(E)) return 1;
+    const size_t P = (size_t)p;
+    std::unique_ptr<HmcState, void (*)(HmcState*)> H(new HmcState, hmc_release);
+    H->f64 = E.f64 != nullptr;
+    H->d_state = (double*)plat_malloc(sizeof(double) * (6 * P + hmc::SC_COUNT));
+    H->d_tab = (double*)plat_malloc(sizeof(double) * (size_t)(2 * n_prior + 3 * K));
+    H->d_kind = (int*)plat_malloc(sizeof(int) * (size_t)std::max(n_prior, 1));
+    if (H->f64) H->d_ev64 = (double*)plat_malloc(sizeof(double) * (P + K));
+    else {
+        H->d_ev32 = (float*)plat_malloc(sizeof(float) * (P + K));
+        H->d_raw = (double*)plat_malloc(sizeof(double) * (size_t)K);
+        H->d_th32 = (float*)plat_malloc(sizeof(float) * P);
+    }
+    if (!H->d_state || !H->d_tab || !H->d_kind || (H->f64 ? !H->d_ev64 : (!H->d_ev32 || !H->d_raw || !H->d_th32))) return fail(std::string(who) + ": device allocation failed");
+    hmc::Args& a = H->a;
+    std::memset(&a, 0, sizeof a);
+    a.P = (int)p; a.K = K; a.n_prior = n_prior; a.nn = (int)p - n_prior;
+    a.sse_roundtrip = H->f64 ? 1 : 0;
+    a.th_cur = H->d_state; a.th_prop = a.th_cur + P; a.r = a.th_prop + P; a.g_cur = a.r + P; a.g_prop = a.g_cur + P;
+    double* minv = a.g_prop + P;
+    a.minv = minv; a.sc = minv + P;
+    a.nn_mu = nn_mu; a.nn_sigma = nn_sigma; a.nn_var = nn_sigma * nn_sigma;
+    a.nn_const = (double)a.nn * (std::log(nn_sigma) + 0.5 * std::log(2.0 * 3.14159265358979323846));
+    double* tab = H->d_tab;
+    a.pr_mu = tab; a.pr_sigma = tab + n_prior; a.lik_c = tab + 2 * n_prior; a.lik_d = a.lik_c + K; a.lik_n = a.lik_d + K;
+    a.pr_kind = H->d_kind;
+    a.th_eval64 = H->f64 ? f64_theta_buffer(E) : nullptr;
+    a.th_eval32 = H->f64 ? nullptr : H->d_th32;
+    // host images: state (theta twice, zero momentum and gradients, unit metric), tables
+    std::vector<double> st(6 * P + hmc::SC_COUNT, 0.0), tb((size_t)(2 * n_prior + 3 * K));
+    std::copy(theta, theta + P, st.begin());
+    std::copy(theta, theta + P, st.begin() + P);
+    std::fill(st.begin() + 5 * P, st.begin() + 6 * P, 1.0);
+    for (int j = 0; j < n_prior; ++j) { tb[j] = prior_mu[j]; tb[n_prior + j] = prior_sigma[j]; }
+    H->w64.resize(K); H->w32.resize(K);
+    for (int j = 0; j < K; ++j) {
+        const double N = (double)E.terms[j].n, Nn = (double)E.terms[j].n_norm, sd = stds[j];
+        H->w64[j] = Nn / (2.0 * sd * sd);
+        H->w32[j] = (float)H->w64[j];
+        tb[2 * n_prior + j] = -0.5 * N * std::log(2.0 * 3.14159265358979323846) - N * std::log(sd);      // (loglik_from_sse's constants, same order of operations)
+        tb[2 * n_prior + K + j] = 2.0 * sd * sd;
+        tb[2 * n_prior + 2 * K + j] = Nn;
+    }
+    std::vector<int> kinds(prior_kind, prior_kind + n_prior);
+    if (plat_h2d(H->d_state, st.data(), sizeof(double) * st.size(), E.stream) || plat_h2d(H->d_tab, tb.data(), sizeof(double) * tb.size(), E.stream) ||
+        (n_prior > 0 && plat_h2d(H->d_kind, kinds.data(), sizeof(int) * kinds.size(), E.stream)))
+        return fail(std::string(who) + ": H2D copy failed");
+    if (H->f64) {
+        if (plat_h2d(a.th_eval64, theta, sizeof(double) * P, E.stream)) return fail(std::string(who) + ": H2D copy failed");
+    } else {
+        std::vector<float> t32(P);
+        for (size_t i = 0; i < P; ++i) t32[i] = (float)theta[i];
+        if (plat_h2d(H->d_th32, t32.data(), sizeof(float) * P, E.stream) || plat_sync(E.stream)) return fail(std::string(who) + ": H2D copy failed");
+    }
+    // logp and its gradient at theta: one evaluation, the update kernel with a zero kick (gradient only), the energy kernel at zero momentum
+    if (hmc_eval(E, *H)) return 1;
+    hmc_leap(E, *H, true, 0.0, 0.0, 0);
+    hmc::launch_energy(a, 1, hmc_sse(*H), E.stream);
+    plat_d2d(a.g_cur, a.g_prop, sizeof(double) * P, E.stream);
+    plat_d2d(a.sc + hmc::SC_LP_CUR, a.sc + hmc::SC_LP_PROP, sizeof(double), E.stream);
+    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    hmc_free(E);
+    E.hmc = H.release();
+    return 0;
+}
+
+int pinn_hmc_set_metric(pinn_handle h, const double* inv_metric, int64_t p) {
+    const char* who = "pinn_hmc_set_metric";
+    if (!h) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (hmc_ready(E, who) || check_theta(E, who, p)) return 1;
+    HmcState& H = *(HmcState*)E.hmc;
+    std::vector<double> m((size_t)p, 1.0);
+    for (int64_t i = 0; inv_metric && i < p; ++i) {
+        if (!(inv_metric[i] > 0.0) || !std::isfinite(inv_metric[i])) return fail(std::string(who) + ": the inverse metric must be positive and finite");
+        m[(size_t)i] = inv_metric[i];
+    }
+    DeviceScope scope(E.device);
+    if (plat_h2d((double*)H.a.minv, m.data(), sizeof(double) * (size_t)p, E.stream) || plat_sync(E.stream)) return fail(std::string(who) + ": H2D copy failed");
+    return 0;
+}
+
+int pinn_hmc_draws(pinn_handle h, int ndraws, int n_leapfrog, double eps, uint64_t seed, const double* momenta, const double* uniforms,
+                   double* samples, int64_t p, double* accept_prob, double* logp) {
+    const char* who = "pinn_hmc_draws";
+    if (!h || !accept_prob || !logp) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who)) return 1;
+    if (ndraws < 1) return fail(std::string(who) + ": ndraws must be at least 1");
+    if (n_leapfrog < 1) return fail(std::string(who) + ": n_leapfrog must be at least 1");
+    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(std::string(who) + ": the step size eps must be positive and finite");
+    HmcState& H = *(HmcState*)E.hmc;
+    DeviceScope scope(E.device);
+    if (H.f64) H.a.th_eval64 = f64_theta_buffer(E);      // (the mode may have been left and entered again since init)
+    const size_t P = (size_t)p, nd = (size_t)ndraws;
+    if ((samples && !hmc_grow(H.d_samples, H.samples_cap, nd * P, E.stream)) || !hmc_grow(H.d_stat, H.stat_cap, 2 * nd, E.stream) ||
+        (momenta && !hmc_grow(H.d_mom, H.mom_cap, nd * P, E.stream)) || (uniforms && !hmc_grow(H.d_uni, H.uni_cap, nd, E.stream)))
+        return fail(std::string(who) + ": device allocation failed");
+    if ((momenta && plat_h2d(H.d_mom, momenta, sizeof(double) * nd * P, E.stream)) || (uniforms && plat_h2d(H.d_uni, uniforms, sizeof(double) * nd, E.stream)))
+        return fail(std::string(who) + ": H2D copy failed");
+    double* d_acc = H.d_stat;
+    double* d_lp = H.d_stat + nd;
+    for (int d = 0; d < ndraws; ++d) {
+        const unsigned ctr = (unsigned)H.draws;
+        hmc::launch_momentum(H.a, momenta ? H.d_mom + (size_t)d * P : nullptr, seed, ctr, E.stream);
+        hmc::launch_energy(H.a, 0, nullptr, E.stream);
+        hmc_leap(E, H, false, 0.5 * eps, eps, 1);
+        for (int s = 0; s < n_leapfrog; ++s) {
+            if (hmc_eval(E, H)) return 1;                // (the current state only changes in the accept launch: a failed call leaves the chain at its last completed draw)
+            const bool last = s == n_leapfrog - 1;
+            hmc_leap(E, H, true, last ? 0.5 * eps : eps, eps, last ? 0 : 1);
+        }
+        hmc::launch_energy(H.a, 1, hmc_sse(H), E.stream);
+        hmc::launch_accept(H.a, d, uniforms ? H.d_uni : nullptr, seed, ctr, samples ? H.d_samples : nullptr, d_acc, d_lp, E.stream);
+        ++H.draws;
+    }
+    if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * P, E.stream)) || plat_d2h(accept_prob, d_acc, sizeof(double) * nd, E.stream) ||
+        plat_d2h(logp, d_lp, sizeof(double) * nd, E.stream))
+        return fail(std::string(who) + ": D2H copy failed");
+    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    return 0;
+}
+
+int pinn_hmc_get(pinn_handle h, double* theta, int64_t p, double* logp, double* grad) {
+    const char* who = "pinn_hmc_get";
+    if (!h || !theta) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (hmc_ready(E, who) || check_theta(E, who, p)) return 1;
+    HmcState& H = *(HmcState*)E.hmc;
+    DeviceScope scope(E.device);
+    if (plat_d2h(theta, H.a.th_cur, sizeof(double) * (size_t)p, E.stream) || (logp && plat_d2h(logp, H.a.sc + hmc::SC_LP_CUR, sizeof(double), E.stream)) ||
+        (grad && plat_d2h(grad, H.a.g_cur, sizeof(double) * (size_t)p, E.stream)) || plat_sync(E.stream))
+        return fail(std::string(who) + ": D2H copy failed");
+    return 0;
+}
 
 }  // extern "C"
 

@@ -319,6 +319,7 @@ struct pinn_engine {
     size_t phi_scr_cap = 0;
     int64_t phi_cap = 0;
     int phi_chan = 0;                // jet channels d_phi_out holds per point
+    void* hmc = nullptr;             // resident HMC sampler state (engine.cpp: HmcState; pinn_hmc_init), nullptr = none
 };
 
 namespace pe {
@@ -376,6 +377,8 @@ int f64_adam_steps(pinn_engine& E, int nsteps, double lr, double beta1, double b
 int f64_points_from_device(pinn_engine& E, int term);
 int f64_eval_from_device_f32(pinn_engine& E, const float* d_theta, const float* term_w, float* d_out, bool want_grad);
 int f64_eval_from_device_f64(pinn_engine& E, const double* d_theta, const float* term_w, double* d_out);
+double* f64_theta_buffer(pinn_engine& E);          // the device buffer [P, padded] every float64 evaluation of the handle reads its parameters from
+int f64_eval_resident(pinn_engine& E, const double* term_w, double* d_out);      // evaluate at the parameters in that buffer: d_out = [gradient | raw sums] (P + K doubles, device)
 int f64_eval_sharded_local(pinn_engine& E, const double* theta, const double* term_w, double** d_out);      // host theta -> this device's [gradient | sums] (P + K doubles, device)
 int f64_adam_steps_comm(pinn_engine** es, int ndev, int nsteps, double lr, double beta1, double beta2, double eps, const float* term_w, double* loss_history,
                         void (*redraw)(pinn_engine&, pe::Term&));

@@ -1300,6 +1300,14 @@ int f64_eval_from_device_f64(pinn_engine& E, const double* d_theta, const float*
     return f64_eval_device(E, d_theta, d_out, d_out + P, w.data());
 }
 
+// the resident HMC loop (engine.cpp: pinn_hmc_*) in float64 mode: its update kernel writes the proposal into the evaluation's own parameter buffer
+// (padded as the matrix-pipe kernels need) and every leapfrog step evaluates there, [gradient | raw sums] into the sampler's own vector (P + K doubles)
+double* f64_theta_buffer(pinn_engine& E) { return ((F64State*)E.f64)->d_theta; }
+int f64_eval_resident(pinn_engine& E, const double* term_w, double* d_out) {
+    F64State& S = *(F64State*)E.f64;
+    return f64_eval_device(E, S.d_theta, d_out, d_out + E.ntheta, term_w);
+}
+
 // " f64_channels=5,1,1,1,1 f64_kernels=mfma:HT4xPG1,mfma:HT4xPG4,..." for pinn_describe
 std::string f64_describe(const pinn_engine& E) {
     if (!E.f64) return "";
