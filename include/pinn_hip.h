@@ -319,6 +319,37 @@ int pinn_hmc_draws(pinn_handle h, int ndraws, int n_leapfrog, double eps, uint64
 int pinn_hmc_get(pinn_handle h, double* theta, int64_t p, double* logp, double* grad);
 
 /*
+ * RESIDENT L-BFGS: pinn_lbfgs's iteration with the iterate x, its gradient, the trial point, the direction, the curvature
+ * pairs (rings of `history` vectors) and the line search's bookkeeping in HBM in double.  Opt-in: pinn_lbfgs is unchanged.  The host queues SLOTS —
+ * one state-machine launch (judge the evaluation just finished: Armijo test, accept with the curvature-pair update or halve the step; propose the
+ * next point: two-loop recursion and first step, or the next trial of the running line search) followed by one full evaluation of the handle's resident
+ * path (the double kernels in float64 mode; the fp32 kernels at (float)x otherwise, their K sums in double) — in chunks of "lbfgs_chunk" slots
+ * (pinn_set_option, 1..64, default 8; 1 = one synchronisation per evaluation) and reads the control block, nothing else, after each chunk.
+ * Same algorithm and constants as pinn_lbfgs (Armijo c1 = 1e-4, halving, 30 trials, pair kept iff s.y > 1e-10 |s| |y|, gamma = s.y / y.y, restart
+ * from -g when g.d >= 0, first step min(1, 1 / |g|_2)), same order of operations; dot products are summed in a fixed parallel order, so the
+ * iterates agree with pinn_lbfgs's to rounding and are bit-reproducible from run to run.  ONE difference: a rejected trial costs a full evaluation
+ * here (pinn_lbfgs evaluates rejected trials loss-only and the accepted point once more with its gradient); an accepted trial is never re-evaluated.
+ *   pinn_lbfgs_init   uploads theta (p doubles), fixes the term weights (NULL: ones — they cannot change later: the curvature pairs belong to one
+ *                     objective), evaluates f and g once, clears the rings and the counters.  A second call replaces the state.
+ *   pinn_lbfgs_steps  continues from the stored state for at most `maxiters` further iterations and at most `max_evals` further trial evaluations
+ *                     (2 iterations followed by 3 are bit-equal to 5 in one call; a call that ends inside a line search is resumed there).
+ *                     loss_history (nullable): objective after every iteration of this call, `maxiters` entries, padded with the last objective;
+ *                     *iters_done / *evals_done: iterations / trial evaluations of this call; *status: 0 RUN or 1 RETRY (max_evals ended the call
+ *                     between / inside line searches), 2 CONVERGED (max |g_i| <= gtol), 3 STALLED (30 trials without decrease: the evaluation's
+ *                     noise floor), 4 MAXITER.  A terminal status ends the call, not the optimisation: the next call tests again.  Slots queued behind
+ *                     a terminal one do nothing (at most lbfgs_chunk - 1 evaluations are spent on them).  At STALLED a handle in "split" GEMM mode
+ *                     switches itself to "fp32" once per call, re-evaluates at x, clears the rings and goes on, and is switched back before the
+ *                     call returns, as in pinn_lbfgs ($PINN_LBFGS_KEEP_GEMM=1 disables that).
+ *   pinn_lbfgs_get    the current iterate: theta (p doubles), *f (nullable), grad (p doubles, nullable).
+ * The state has buffers of its own: evaluations, pinn_adam_* and pinn_hmc_* between two calls leave it alone and vice versa.
+ * Refused, with the handle left as it was: pinn_lbfgs_steps / _get before pinn_lbfgs_init; a handle whose precision mode changed since (init again);
+ * a term with a device sampler; a handle on a communicator; p != ntheta; history outside 1..64; maxiters < 1; max_evals < 1.
+ */
+int pinn_lbfgs_init(pinn_handle h, const double* theta, int64_t p, int history, const float* term_w);
+int pinn_lbfgs_steps(pinn_handle h, int maxiters, int max_evals, double gtol, double* loss_history, int* iters_done, int* evals_done, int* status);
+int pinn_lbfgs_get(pinn_handle h, double* theta, int64_t p, double* f, double* grad);
+
+/*
  * Run-time options of a handle.  "gemm" = arithmetic of the hidden-layer GEMMs of the 64- / 128-wide (neuron-split) kernels:
  *   "split" (default) — every fp32 product rebuilt from three bf16 pieces per operand on the bf16 matrix pipe (6 MFMAs, fp32 accumulation):
  *                       2-4 x the rounding error of an fp32 fmaf chain, ~1.35 x faster (error budget: DESIGN.md section 6);

@@ -358,6 +358,44 @@ function hmc_get(e::HIPEngine)
     return θ, lp[], g
 end
 
+"""
+    lbfgs_init(e, θ; history = 10, weights = nothing)
+    lbfgs_steps(e, maxiters; max_evals = 31 * maxiters, gtol = 1e-8) -> (loss_history, evals, status)
+    lbfgs_get(e) -> (θ, f, ∇f)
+    lbfgs_resident!(e, θ; maxiters, history = 10, gtol = 1e-8, weights = nothing) -> (θ, loss_history)
+
+The resident L-BFGS finisher (`pinn_lbfgs_init / _steps / _get`, DESIGN.md §4.8): `solve(prob, LBFGS(); maxiters)` with the iterate, the
+curvature pairs and the line search on the device.  `status`: 0 RUN, 1 RETRY, 2 CONVERGED, 3 STALLED, 4 MAXITER.  The term weights are fixed
+at `lbfgs_init`.  `lbfgs_resident!` is the one-call form (the library's host routine `pinn_lbfgs` is not called by this glue).
+"""
+function lbfgs_init(e::HIPEngine, θ::AbstractVector{<:Real}; history::Integer = 10, weights = nothing)
+    θ64 = Vector{Float64}(θ); w = weights === nothing ? Float32[] : Vector{Float32}(weights)
+    GC.@preserve θ64 w check(ccall(sym(:pinn_lbfgs_init), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Cint, Ptr{Float32}),
+        e.h, θ64, e.P, history, weights === nothing ? Ptr{Float32}(C_NULL) : pointer(w)), "pinn_lbfgs_init")
+    return nothing
+end
+
+function lbfgs_steps(e::HIPEngine, maxiters::Integer; max_evals::Integer = 31 * maxiters, gtol::Real = 1e-8)
+    hist = zeros(Float64, maxiters); it = Ref{Cint}(0); ev = Ref{Cint}(0); st = Ref{Cint}(0)
+    GC.@preserve hist check(ccall(sym(:pinn_lbfgs_steps), Cint, (Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Float64}, Ref{Cint}, Ref{Cint}, Ref{Cint}),
+        e.h, maxiters, max_evals, Float64(gtol), hist, it, ev, st), "pinn_lbfgs_steps")
+    return hist[1:it[]], Int(ev[]), Int(st[])
+end
+
+function lbfgs_get(e::HIPEngine)
+    θ = zeros(Float64, e.P); g = zeros(Float64, e.P); f = Ref{Float64}(0.0)
+    GC.@preserve θ g check(ccall(sym(:pinn_lbfgs_get), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}, Ptr{Float64}),
+        e.h, θ, e.P, f, g), "pinn_lbfgs_get")
+    return θ, f[], g
+end
+
+function lbfgs_resident!(e::HIPEngine, θ::AbstractVector{<:Real}; maxiters::Integer, history::Integer = 10, gtol::Real = 1e-8, weights = nothing)
+    lbfgs_init(e, θ; history = history, weights = weights)
+    hist, _, _ = lbfgs_steps(e, maxiters; gtol = gtol)
+    θ .= lbfgs_get(e)[1]
+    return θ, hist
+end
+
 # ------------------------------------------------------------------------------------------------
 # 1. s-expression printer of the Julia Expr trees `toexpr` returns
 # ------------------------------------------------------------------------------------------------

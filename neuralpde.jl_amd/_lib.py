@@ -39,6 +39,7 @@ SYMBOLS = [
     "pinn_residual_f64", "pinn_phi_f64", "pinn_derivative_f64", "pinn_term_grads_f64", "pinn_loglik_grad_f64",
     "pinn_loss_grad_sharded_device_f64", "pinn_loss_grad_sharded_f64",
     "pinn_hmc_init", "pinn_hmc_set_metric", "pinn_hmc_draws", "pinn_hmc_get",
+    "pinn_lbfgs_init", "pinn_lbfgs_steps", "pinn_lbfgs_get",
 ]
 
 
@@ -117,6 +118,12 @@ class Library:
             L.pinn_hmc_set_metric.argtypes = [vp, dp, C.c_int64]
             L.pinn_hmc_draws.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint64, dp, dp, dp, C.c_int64, dp, dp]
             L.pinn_hmc_get.argtypes = [vp, dp, C.c_int64, dp, dp]
+        except AttributeError:
+            pass
+        try:                                     # (resident L-BFGS: variant libraries built before it still load)
+            L.pinn_lbfgs_init.argtypes = [vp, dp, C.c_int64, C.c_int, fp]
+            L.pinn_lbfgs_steps.argtypes = [vp, C.c_int, C.c_int, C.c_double, dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.pinn_lbfgs_get.argtypes = [vp, dp, C.c_int64, dp, dp]
         except AttributeError:
             pass
         L.pinn_lbfgs.argtypes = [vp, C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_double, fp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -529,6 +536,34 @@ class Engine:
                                            w.ctypes.data_as(C.POINTER(C.c_float)) if w is not None else None,
                                            hist.ctypes.data_as(C.POINTER(C.c_double)), C.byref(done)), "pinn_lbfgs")
         return th, hist[:done.value]
+
+    # ---- resident L-BFGS (include/pinn_hip.h: pinn_lbfgs_init / _steps / _get) ----
+    LBFGS_STATUS = ("RUN", "RETRY", "CONVERGED", "STALLED", "MAXITER")
+
+    def lbfgs_init(self, theta, weights=None, history: int = 10):
+        """`pinn_lbfgs_init`: put the device-resident L-BFGS state at theta; the term weights are fixed here."""
+        th = _f64(theta)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32)) if weights is not None else None
+        self.L.check(self.L.lib.pinn_lbfgs_init(self.h, th.ctypes.data_as(C.POINTER(C.c_double)), th.size, int(history),
+                                                w.ctypes.data_as(C.POINTER(C.c_float)) if w is not None else None), "pinn_lbfgs_init")
+
+    def lbfgs_steps(self, maxiters: int, max_evals: int = None, gtol: float = 1e-8):
+        """`pinn_lbfgs_steps`: at most `maxiters` further iterations / `max_evals` further trial evaluations (default: 31 per iteration, which
+        never binds) from the stored state.  Returns (objective after every performed iteration, evaluations, status name)."""
+        hist = np.zeros(max(int(maxiters), 1), dtype=np.float64)
+        it, ev, st = C.c_int(0), C.c_int(0), C.c_int(0)
+        me = 31 * max(int(maxiters), 1) if max_evals is None else int(max_evals)
+        self.L.check(self.L.lib.pinn_lbfgs_steps(self.h, int(maxiters), me, float(gtol), hist.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 C.byref(it), C.byref(ev), C.byref(st)), "pinn_lbfgs_steps")
+        return hist[:it.value], ev.value, self.LBFGS_STATUS[st.value]
+
+    def lbfgs_get(self, want_grad: bool = True):
+        """`pinn_lbfgs_get`: (theta, objective, gradient) of the current iterate"""
+        th = np.zeros(self.P, dtype=np.float64)
+        g = np.zeros(self.P, dtype=np.float64) if want_grad else None
+        f, dp = C.c_double(), C.POINTER(C.c_double)
+        self.L.check(self.L.lib.pinn_lbfgs_get(self.h, th.ctypes.data_as(dp), th.size, C.byref(f), g.ctypes.data_as(dp) if g is not None else None), "pinn_lbfgs_get")
+        return th, f.value, g
 
     # ---- resident HMC (include/pinn_hip.h: pinn_hmc_*) ----
     def hmc_init(self, theta, stds, nn_prior=(0.0, 2.0), param_priors=()):

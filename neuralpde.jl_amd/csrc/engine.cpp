@@ -6,6 +6,7 @@
 #include "engine_types.hpp"
 #include "aux_kernels.hpp"
 #include "hmc_kernels.hpp"
+#include "lbfgs_kernels.hpp"
 
 #include <type_traits>
 
@@ -492,6 +493,7 @@ int pe::upload_theta(pinn_engine& E, const float* theta, int64_t p) {
 // C ABI
 // =================================================================================================
 static void hmc_free(pinn_engine& E);
+static void lbfgs_free(pinn_engine& E);
 
 extern "C" {
 
@@ -562,6 +564,7 @@ int pinn_destroy(pinn_handle h) {
     pinn_comm_destroy(h);
     plat_sync(E.stream);
     hmc_free(E);
+    lbfgs_free(E);
     f64_destroy(E);
     free_plan(E);
     for (auto& T : E.terms) { plat_free(T.d_pts); plat_free(T.d_upts); plat_free(T.d_resid); plat_free(T.d_lb); plat_free(T.d_ub); plat_free(T.d_data); plat_free(T.d_pw); }
@@ -1251,7 +1254,14 @@ int pinn_set_option(pinn_handle h, const char* name, const char* value) {
         if (v == "exact") return E.f64 ? f64_stencil_enable(E, false) : 0;
         return fail("pinn_set_option: derivative must be \"exact\" or \"stencil\"");
     }
-    return fail("pinn_set_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes)");
+    if (k == "lbfgs_chunk") {
+        char* end = nullptr;
+        const long q = std::strtol(v.c_str(), &end, 10);
+        if (v.empty() || *end || q < 1 || q > 64) return fail("pinn_set_option: lbfgs_chunk must be an integer in 1..64, not \"" + v + "\"");
+        E.lbfgs_chunk = (int)q;
+        return 0;
+    }
+    return fail("pinn_set_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, lbfgs_chunk)");
 }
 
 int pinn_get_option(pinn_handle h, const char* name, char* buf, int64_t buflen) {
@@ -1270,7 +1280,8 @@ int pinn_get_option(pinn_handle h, const char* name, char* buf, int64_t buflen) 
     if (k == "f64_merged") { std::snprintf(buf, (size_t)buflen, "%d", pe::f64_merged(*h)); return 0; }          // merged launches of the last float64 evaluation
     if (k == "f64_chunks") { std::snprintf(buf, (size_t)buflen, "%d", pe::f64_chunks(*h)); return 0; }          // chunks of the largest point set in the last float64 call
     if (k == "adam_path") { std::snprintf(buf, (size_t)buflen, "%s", h->adam_path == 2 ? "persistent" : (h->adam_path == 1 ? "loop" : "none")); return 0; }
-    return fail("pinn_get_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, grad_health, gemm_delta, adam_path, eval_path, f64_path, f64_merged, f64_chunks, f64_affine)");
+    if (k == "lbfgs_chunk") { std::snprintf(buf, (size_t)buflen, "%d", h->lbfgs_chunk); return 0; }
+    return fail("pinn_get_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, lbfgs_chunk, grad_health, gemm_delta, adam_path, eval_path, f64_path, f64_merged, f64_chunks, f64_affine)");
 }
 
 // fp32 optimiser state (float64 mode: f64.cpp keeps its own, in double)
@@ -1833,6 +1844,35 @@ int pinn_adam_apply(pinn_handle h, const float* grad_and_sums, int64_t n, float 
     return 0;
 }
 
+// The noise-floor switch of the L-BFGS routines (pinn_lbfgs, pinn_lbfgs_steps).  A line search that cannot decrease the objective along a descent
+// direction has reached the evaluation's noise floor; the split-operand GEMMs' floor is 2-4 x that of the fp32 MFMA kernels:
+// a handle in "split" mode is switched to them once per call and goes on from the same iterate.  The switch only changes arithmetic where a launch
+// group runs a family-2 kernel that exists as a split / fp32 twin; $PINN_LBFGS_KEEP_GEMM disables it; every exit path hands the handle back in the
+// mode it came in.
+struct GemmFloorSwitch {
+    pinn_engine& E;
+    bool switched = false, armed = false, has_twin = false;
+    explicit GemmFloorSwitch(pinn_engine& e) : E(e) {
+        for (const NetPlan& NP : E.netplans) has_twin = has_twin || (NP.spec && NP.spec->family == 2 && NP.spec->twin);
+    }
+    ~GemmFloorSwitch() { if (armed && E.gemm != pk::GEMM_SPLIT) { const std::string keep = g_err; replan_gemm(E, pk::GEMM_SPLIT); if (!keep.empty()) g_err = keep; } }
+    bool eligible() const { return !E.f64 && E.gemm == pk::GEMM_SPLIT && !switched && has_twin && std::getenv("PINN_LBFGS_KEEP_GEMM") == nullptr; }
+    // 0: done, `switched` says whether the handle now runs the fp32 kernels; 1: error; 2: the switch failed (the fp32 twin of a run-time specialised
+    // shape did not compile) and left the handle in split mode — replan_gemm restored the plan: the iterate reached so far is the answer, not an
+    // error
+    int engage() {
+        if (replan_gemm(E, pk::GEMM_FP32)) { if (E.gemm != pk::GEMM_SPLIT || E.groups.empty()) return 1; g_err.clear(); return 2; }
+        switched = E.gemm == pk::GEMM_FP32;
+        armed = switched;
+        return 0;
+    }
+    int finish() {                                       // the regular end of a call
+        if (!switched) return 0;
+        armed = false;
+        return replan_gemm(E, pk::GEMM_SPLIT) ? 1 : 0;
+    }
+};
+
 int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int history, double gtol, const float* term_w, double* loss_history,
                int* iters_done) {
     if (!h || !theta) return fail("pinn_lbfgs: null argument");
@@ -1877,14 +1917,7 @@ int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int histor
     if (eval(x, &g, f)) return 1;
     std::deque<std::vector<double>> S, Y;
     std::deque<double> RHO;
-    bool switched = false;
-    // the noise-floor switch below only changes arithmetic where a launch group runs a family-2 kernel that exists as a split / fp32 twin
-    bool has_twin = false;
-    for (const NetPlan& NP : E.netplans) has_twin = has_twin || (NP.spec && NP.spec->family == 2 && NP.spec->twin);
-    struct Restore {                                     // every exit path hands the handle back in the mode it came in
-        pinn_engine& E; bool armed = false;
-        ~Restore() { if (armed && E.gemm != pk::GEMM_SPLIT) { const std::string keep = g_err; replan_gemm(E, pk::GEMM_SPLIT); if (!keep.empty()) g_err = keep; } }
-    } restore{E};
+    GemmFloorSwitch floor_switch(E);
     int it = 0;
     for (; it < maxiters; ++it) {
         double gmax = 0.0;
@@ -1928,15 +1961,12 @@ int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int histor
             t *= 0.5;
         }
         if (!ok) {
-            // no decrease along a descent direction: the evaluation's noise floor.  The split-operand GEMMs' floor is 2-4 x that of the
-            // fp32 MFMA kernels: switch the handle to them once and go on from the same iterate
-            if (!E.f64 && E.gemm == pk::GEMM_SPLIT && !switched && has_twin && std::getenv("PINN_LBFGS_KEEP_GEMM") == nullptr) {
-                // a failed switch (the fp32 twin of a run-time specialised shape did not compile) leaves the handle in split mode — replan_gemm
-                // restored the plan: the iterate reached so far is the answer, not an error
-                if (replan_gemm(E, pk::GEMM_FP32)) { if (E.gemm != pk::GEMM_SPLIT || E.groups.empty()) return 1; g_err.clear(); break; }
-                switched = E.gemm == pk::GEMM_FP32;
-                restore.armed = switched;
-                if (switched) {
+            // no decrease along a descent direction: the evaluation's noise floor (GemmFloorSwitch)
+            if (floor_switch.eligible()) {
+                const int sw = floor_switch.engage();
+                if (sw == 1) return 1;
+                if (sw == 2) break;
+                if (floor_switch.switched) {
                     if (eval(x, &g, f)) return 1;
                     S.clear(); Y.clear(); RHO.clear();   // curvature pairs carry the other arithmetic's gradient noise
                     --it;
@@ -1958,8 +1988,7 @@ int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int histor
     if (loss_history) for (int i = it; i < maxiters; ++i) loss_history[i] = f;
     if (iters_done) *iters_done = it;
     for (size_t i = 0; i < P; ++i) theta[i] = x[i];
-    if (switched) { restore.armed = false; if (replan_gemm(E, pk::GEMM_SPLIT)) return 1; }
-    return 0;
+    return floor_switch.finish();
 }
 
 static int adam_get_f32(pinn_engine& E, float* theta) {
@@ -2034,7 +2063,8 @@ int pinn_describe(pinn_handle h, char* buf, int64_t buflen) {
     if (!h || !buf || buflen <= 0) return fail("pinn_describe: bad argument");
     std::ostringstream os;
     os << "backend=" << plat_name() << " cus=" << h->ncu << " ntheta=" << h->ntheta << " terms=" << h->terms.size()
-       << (h->f64 ? " precision=f64 (pinn_loss_grad*, pinn_lbfgs evaluate in double — matrix-pipe tile kernels where instantiated, one lane per point elsewhere; the plan below serves the fp32 entry points)" + pe::f64_describe(*h) : std::string()) << "\n";
+       << (h->f64 ? " precision=f64 (pinn_loss_grad*, pinn_lbfgs evaluate in double — matrix-pipe tile kernels where instantiated, one lane per point elsewhere; the plan below serves the fp32 entry points)" + pe::f64_describe(*h) : std::string())
+       << (h->lbfgs ? " lbfgs=resident(history=" + std::to_string(h->lbfgs_history) + ",chunk=" + std::to_string(h->lbfgs_chunk) + ")" : std::string()) << "\n";
     for (size_t n = 0; n < h->netplans.size(); ++n)
         if (h->netplans[n].spec && h->netplans[n].spec->family != 3)
             os << "net " << n << " weights=packed image (k_pack per evaluation)"
@@ -2447,6 +2477,204 @@ int pinn_hmc_get(pinn_handle h, double* theta, int64_t p, double* logp, double* 
     if (plat_d2h(theta, H.a.th_cur, sizeof(double) * (size_t)p, E.stream) || (logp && plat_d2h(logp, H.a.sc + hmc::SC_LP_CUR, sizeof(double), E.stream)) ||
         (grad && plat_d2h(grad, H.a.g_cur, sizeof(double) * (size_t)p, E.stream)) || plat_sync(E.stream))
         return fail(std::string(who) + ": D2H copy failed");
+    return 0;
+}
+
+}  // extern "C"
+
+// =================================================================================================
+// Resident L-BFGS (pinn_lbfgs_init / _steps / _get): pinn_lbfgs's iteration with the iterate, the curvature rings and the
+// line search on the device.  A SLOT = one lbfgs::k_lbfgs_step launch (judge the evaluation just finished, propose the next point) + one full
+// resident evaluation (float64 mode: f64_eval_resident; otherwise run_loss_grad at the narrowed copy of the trial point, the K sums in double).
+// Slots are queued in chunks of "lbfgs_chunk"; the host reads the control block after a chunk and nothing else before the call's end.
+// The state has buffers of its own: evaluations, optimiser runs and HMC draws between two calls do not touch it, and it does not touch them.
+// =================================================================================================
+namespace {
+
+struct LbfgsState {
+    bool f64 = false;                    // the precision mode the state was initialised in
+    lbfgs::Args a;
+    lbfgs::Ctl ctl;                      // host mirror of the control block as of the last download
+    std::vector<double> w64;             // the term weights, fixed at init (the curvature pairs belong to one objective)
+    std::vector<float> w32;
+    double* d_state = nullptr;           // [4 P + 2 m P + m]: x | g | xn | d | S | Y | rho
+    lbfgs::Ctl* d_ctl = nullptr;
+    double* d_tab = nullptr;             // [2 K]: weights | n_norm
+    double* d_ev64 = nullptr;            // float64 mode: [P + K] gradient | raw sums of the running evaluation
+    float* d_ev32 = nullptr;             // fp32 mode: [P + K] floats, the K sums again as doubles in d_raw, the narrowed trial point in d_th32
+    double* d_raw = nullptr;
+    float* d_th32 = nullptr;
+    double* d_hist = nullptr;
+    size_t hist_cap = 0;
+};
+
+void lbfgs_release(LbfgsState* H) {
+    if (!H) return;
+    plat_free(H->d_state); plat_free(H->d_ctl); plat_free(H->d_tab); plat_free(H->d_ev64); plat_free(H->d_ev32); plat_free(H->d_raw); plat_free(H->d_th32);
+    plat_free(H->d_hist);
+    delete H;
+}
+
+// what pinn_lbfgs_steps / _get check first; leaves the handle as it is
+int lbfgs_ready(pinn_engine& E, const char* who) {
+    if (!E.lbfgs) return fail(std::string(who) + ": no optimiser state (call pinn_lbfgs_init first)");
+    if (((LbfgsState*)E.lbfgs)->f64 != (E.f64 != nullptr))
+        return fail(std::string(who) + ": the handle's precision changed since pinn_lbfgs_init (call pinn_lbfgs_init again)");
+    return 0;
+}
+int lbfgs_refuse_target(pinn_engine& E, const char* who) {
+    if (E.comm) return fail(std::string(who) + ": the handle belongs to a communicator; the resident L-BFGS loop runs on a single device only");
+    for (auto& T : E.terms)
+        if (T.sampler != 0) return fail(std::string(who) + ": a term redraws its points on the device; L-BFGS needs a fixed objective (fixed point sets)");
+    return 0;
+}
+int lbfgs_eval(pinn_engine& E, LbfgsState& H) {
+    if (H.f64) return f64_eval_resident(E, H.w64.data(), H.d_ev64);
+    return run_loss_grad(E, H.d_th32, H.d_ev32, H.w32.data(), -1, false, H.d_raw);
+}
+void lbfgs_step(pinn_engine& E, LbfgsState& H, int mode, int it0, int it_end, double gtol) {
+    if (H.f64) lbfgs::launch_step<double>(H.a, H.d_ev64, mode, it0, it_end, gtol, E.stream);
+    else lbfgs::launch_step<float>(H.a, H.d_ev32, mode, it0, it_end, gtol, E.stream);
+}
+// (f, g) at x from one evaluation; rings cleared, nothing pending (init, and after the noise-floor switch); downloads the control block
+int lbfgs_adopt(pinn_engine& E, LbfgsState& H) {
+    lbfgs_step(E, H, lbfgs::MODE_LOAD, 0, 0, 0.0);
+    if (lbfgs_eval(E, H)) return 1;
+    lbfgs_step(E, H, lbfgs::MODE_ADOPT, 0, 0, 0.0);
+    if (plat_d2h(&H.ctl, H.d_ctl, sizeof(lbfgs::Ctl), E.stream)) return fail("D2H copy failed");
+    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    return 0;
+}
+
+}  // namespace
+
+static void lbfgs_free(pinn_engine& E) {
+    lbfgs_release((LbfgsState*)E.lbfgs);
+    E.lbfgs = nullptr;
+    E.lbfgs_history = 0;
+}
+
+extern "C" {
+
+int pinn_lbfgs_init(pinn_handle h, const double* theta, int64_t p, int history, const float* term_w) {
+    const char* who = "pinn_lbfgs_init";
+    if (!h || !theta) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (check_theta(E, who, p)) return 1;
+    if (history < 1 || history > lbfgs::MAX_HISTORY) return fail(std::string(who) + ": history must be in 1.." + std::to_string(lbfgs::MAX_HISTORY));
+    if (lbfgs_refuse_target(E, who)) return 1;
+    DeviceScope scope(E.device);
+    if (!E.f64 && ensure_points(E)) return 1;
+    const size_t P = (size_t)p, m = (size_t)history;
+    const int K = (int)E.terms.size();
+    std::unique_ptr<LbfgsState, void (*)(LbfgsState*)> H(new LbfgsState, lbfgs_release);
+    H->f64 = E.f64 != nullptr;
+    const size_t nstate = 4 * P + 2 * m * P + m;
+    H->d_state = (double*)plat_malloc(sizeof(double) * nstate);
+    H->d_ctl = (lbfgs::Ctl*)plat_malloc(sizeof(lbfgs::Ctl));
+    H->d_tab = (double*)plat_malloc(sizeof(double) * (size_t)(2 * K));
+    if (H->f64) H->d_ev64 = (double*)plat_malloc(sizeof(double) * (P + K));
+    else {
+        H->d_ev32 = (float*)plat_malloc(sizeof(float) * (P + K));
+        H->d_raw = (double*)plat_malloc(sizeof(double) * (size_t)K);
+        H->d_th32 = (float*)plat_malloc(sizeof(float) * P);
+    }
+    if (!H->d_state || !H->d_ctl || !H->d_tab || (H->f64 ? !H->d_ev64 : (!H->d_ev32 || !H->d_raw || !H->d_th32))) return fail(std::string(who) + ": device allocation failed");
+    lbfgs::Args& a = H->a;
+    std::memset(&a, 0, sizeof a);
+    a.P = (int)p; a.K = K; a.m = history; a.f64form = H->f64 ? 1 : 0;
+    a.x = H->d_state; a.g = a.x + P; a.xn = a.g + P; a.d = a.xn + P; a.S = a.d + P; a.Y = a.S + m * P; a.rho = a.Y + m * P;
+    a.ctl = H->d_ctl;
+    a.w = H->d_tab; a.nrm = H->d_tab + K;
+    a.sums = H->f64 ? H->d_ev64 + P : H->d_raw;
+    a.th_eval64 = H->f64 ? f64_theta_buffer(E) : nullptr;
+    a.th_eval32 = H->f64 ? nullptr : H->d_th32;
+    H->w64.resize(K); H->w32.resize(K);
+    std::vector<double> tb((size_t)(2 * K));
+    for (int k = 0; k < K; ++k) {
+        H->w32[k] = term_w ? term_w[k] : 1.0f;
+        H->w64[k] = (double)H->w32[k];
+        tb[k] = H->w64[k];
+        tb[K + k] = (double)E.terms[k].n_norm;
+    }
+    std::memset(&H->ctl, 0, sizeof H->ctl);
+    plat_memset(H->d_state, 0, sizeof(double) * nstate, E.stream);
+    if (plat_h2d(a.x, theta, sizeof(double) * P, E.stream) || plat_h2d(H->d_tab, tb.data(), sizeof(double) * tb.size(), E.stream) ||
+        plat_h2d(H->d_ctl, &H->ctl, sizeof(lbfgs::Ctl), E.stream) || plat_sync(E.stream))
+        return fail(std::string(who) + ": H2D copy failed");
+    if (lbfgs_adopt(E, *H)) return 1;
+    lbfgs_free(E);
+    E.lbfgs = H.release();
+    E.lbfgs_history = history;
+    return 0;
+}
+
+int pinn_lbfgs_steps(pinn_handle h, int maxiters, int max_evals, double gtol, double* loss_history, int* iters_done, int* evals_done, int* status) {
+    const char* who = "pinn_lbfgs_steps";
+    if (!h) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (lbfgs_ready(E, who) || lbfgs_refuse_target(E, who)) return 1;
+    if (maxiters < 1) return fail(std::string(who) + ": maxiters must be at least 1");
+    if (max_evals < 1) return fail(std::string(who) + ": max_evals must be at least 1");
+    LbfgsState& H = *(LbfgsState*)E.lbfgs;
+    DeviceScope scope(E.device);
+    if (H.f64) H.a.th_eval64 = f64_theta_buffer(E);      // (the mode may have been left and entered again since init)
+    if (H.hist_cap < (size_t)maxiters) {
+        plat_sync(E.stream);
+        plat_free(H.d_hist);
+        H.d_hist = (double*)plat_malloc(sizeof(double) * (size_t)maxiters);
+        H.hist_cap = H.d_hist ? (size_t)maxiters : 0;
+        if (!H.d_hist) return fail(std::string(who) + ": device allocation failed");
+    }
+    H.a.loss_hist = H.d_hist;
+    if (H.ctl.status >= lbfgs::ST_CONVERGED) {           // a terminal state ends a call, not the optimisation: the next call tests again
+        H.ctl.status = lbfgs::ST_RUN;
+        if (plat_h2d(H.d_ctl, &H.ctl, sizeof(lbfgs::Ctl), E.stream) || plat_sync(E.stream)) return fail(std::string(who) + ": H2D copy failed");
+    }
+    const int it0 = H.ctl.it, it_end = it0 + maxiters, ev0 = H.ctl.evals;
+    GemmFloorSwitch floor_switch(E);
+    for (;;) {
+        const int left = max_evals - (H.ctl.evals - ev0);
+        if (left <= 0) break;
+        const int n = std::min(E.lbfgs_chunk, left);     // (a slot proposes at most one trial point)
+        for (int s = 0; s < n; ++s) {
+            lbfgs_step(E, H, lbfgs::MODE_SLOT, it0, it_end, gtol);
+            if (lbfgs_eval(E, H)) return 1;
+        }
+        if (plat_d2h(&H.ctl, H.d_ctl, sizeof(lbfgs::Ctl), E.stream)) return fail(std::string(who) + ": D2H copy failed");
+        if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+        if (H.ctl.status < lbfgs::ST_CONVERGED) continue;
+        if (H.ctl.status == lbfgs::ST_STALLED && floor_switch.eligible()) {
+            const int sw = floor_switch.engage();
+            if (sw == 1) return 1;
+            if (sw == 0 && floor_switch.switched) {      // go on from the same iterate; curvature pairs carry the other arithmetic's gradient noise
+                if (lbfgs_adopt(E, H)) return 1;
+                continue;
+            }
+        }
+        break;
+    }
+    const int done = H.ctl.it - it0;
+    if (loss_history) {
+        if (done > 0 && (plat_d2h(loss_history, H.d_hist, sizeof(double) * (size_t)done, E.stream) || plat_sync(E.stream))) return fail(std::string(who) + ": D2H copy failed");
+        for (int i = done; i < maxiters; ++i) loss_history[i] = H.ctl.f;
+    }
+    if (iters_done) *iters_done = done;
+    if (evals_done) *evals_done = H.ctl.evals - ev0;
+    if (status) *status = H.ctl.status;
+    return floor_switch.finish();
+}
+
+int pinn_lbfgs_get(pinn_handle h, double* theta, int64_t p, double* f, double* grad) {
+    const char* who = "pinn_lbfgs_get";
+    if (!h || !theta) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (lbfgs_ready(E, who) || check_theta(E, who, p)) return 1;
+    LbfgsState& H = *(LbfgsState*)E.lbfgs;
+    DeviceScope scope(E.device);
+    if (plat_d2h(theta, H.a.x, sizeof(double) * (size_t)p, E.stream) || (grad && plat_d2h(grad, H.a.g, sizeof(double) * (size_t)p, E.stream)) || plat_sync(E.stream))
+        return fail(std::string(who) + ": D2H copy failed");
+    if (f) *f = H.ctl.f;
     return 0;
 }
 

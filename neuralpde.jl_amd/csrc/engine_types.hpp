@@ -320,6 +320,9 @@ struct pinn_engine {
     int64_t phi_cap = 0;
     int phi_chan = 0;                // jet channels d_phi_out holds per point
     void* hmc = nullptr;             // resident HMC sampler state (engine.cpp: HmcState; pinn_hmc_init), nullptr = none
+    void* lbfgs = nullptr;           // resident L-BFGS state (engine.cpp: LbfgsState; pinn_lbfgs_init), nullptr = none
+    int lbfgs_history = 0;           // its history length (pinn_describe)
+    int lbfgs_chunk = 8;             // option "lbfgs_chunk": slots pinn_lbfgs_steps queues between two downloads of the control block, 1..64
 };
 
 namespace pe {

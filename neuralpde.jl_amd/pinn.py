@@ -352,9 +352,11 @@ class BFGS:
 
 @dataclass
 class LBFGS:
-    """[3P] OptimizationOptimJL.LBFGS(): scipy's L-BFGS-B on the host, see BFGS."""
+    """[3P] OptimizationOptimJL.LBFGS(): scipy's L-BFGS-B on the host, see BFGS.  `resident=True` (opt-in) runs the library's device-resident
+    loop (pinn_lbfgs_init / pinn_lbfgs_steps) where the library's own L-BFGS would run: no callback, no additional_loss, fixed weights."""
     m: int = 10
     gtol: float = 1e-8
+    resident: bool = False
 
 
 @dataclass
@@ -446,8 +448,14 @@ def _host_quasi_newton(prob: OptimizationProblem, alg, maxiters: int, callback) 
         raise ValueError("BFGS / LBFGS need a fixed objective: use GridTraining, QuadratureTraining or QuasiRandomTraining(...; resampling = false, "
                          "minibatch = 1) (the reference's tests say the same, e.g. test/NNPDE1/nnpde__pde_vi_pde_with_mixed_derivative.jl:76)")
     if isinstance(alg, LBFGS) and callback is None and rep.additional_loss is None and rep.adaloss.reweight_every <= 0:
-        # the library's own L-BFGS (pinn_lbfgs): same recursion, no Python in the loop
-        theta, hist = rep.engine.lbfgs(prob.u0, int(maxiters), rep._weights_now(), history=alg.m, gtol=alg.gtol)
+        # the library's own L-BFGS (pinn_lbfgs): same recursion, no Python in the loop; resident = True: the same iteration with the iterate,
+        # the curvature pairs and the line search on the device (pinn_lbfgs_init / pinn_lbfgs_steps)
+        if alg.resident:
+            rep.engine.lbfgs_init(prob.u0, rep._weights_now(), history=alg.m)
+            hist = rep.engine.lbfgs_steps(int(maxiters), gtol=alg.gtol)[0]
+            theta = rep.engine.lbfgs_get(want_grad=False)[0]
+        else:
+            theta, hist = rep.engine.lbfgs(prob.u0, int(maxiters), rep._weights_now(), history=alg.m, gtol=alg.gtol)
         rep.iteration[0] += len(hist)
         final = float(hist[-1]) if len(hist) else float(prob.f.value_and_grad(np.asarray(prob.u0, dtype=np.float64))[0])
         return OptimizationSolution(theta.astype(prob.u0.dtype), final, hist if len(hist) else np.array([final]))
