@@ -350,6 +350,26 @@ int pinn_lbfgs_steps(pinn_handle h, int maxiters, int max_evals, double gtol, do
 int pinn_lbfgs_get(pinn_handle h, double* theta, int64_t p, double* f, double* grad);
 
 /*
+ * ENSEMBLE PREDICTION: the trial function of network `net` at `nsamples` parameter vectors and n points, and the mean and
+ * standard deviation over the samples at every point, in one call — the prediction stage of a Bayesian PINN (ext/bpinn/PDE_BPINN.jl:254-302),
+ * deep-ensemble or checkpoint prediction.  Opt-in: pinn_phi / pinn_phi_f64 are unchanged.
+ *   thetas  [nsamples][p] FULL parameter vectors (p == ntheta; the engine takes the network's own slice, as pinn_phi does)
+ *   pts     [n][d] point-major, d = the network's inputs (as pinn_phi_f64)
+ *   mean[i] = (sum_s phi(x_i; theta_s)) / nsamples,  std[i] = sqrt(sum_s (phi(x_i; theta_s) - mean[i])^2 / (nsamples - ddof)),  ddof = 0 | 1:
+ *           both sums in double in the fixed order s = 0 .. nsamples-1 (numpy.mean / numpy.std(ddof)); bit-reproducible
+ *   preds   nullable: [nsamples][n], every prediction
+ * The compute type follows the handle: double on a handle in float64 mode; otherwise the float kernel at (float)theta, (float)x, its
+ * predictions widened — the statistics are in double either way.  One upload of thetas, one of pts, one launch per (samples x point blocks)
+ * + one for the statistics with no synchronisation in between, one download.  Predictions beyond a device-memory budget ($PINN_ENS_GB,
+ * default 4; $PINN_ENS_CHUNK = points per pass overrides it) are produced in passes over POINTS; the results do not depend on the passes.
+ * Refused, with the handle left as it was: net out of range; p != ntheta; nsamples < 1; ddof not 0 or 1; nsamples - ddof < 1; n < 1; a DGM
+ * network; a network behind a periodic input embedding; more than 16 Dense layers; a layer so wide that two activation images of 64 points
+ * exceed the 160 KB of LDS (wider than 160 neurons in float64 mode, 320 otherwise) — the message names the sizes.
+ */
+int pinn_phi_ensemble(pinn_handle h, int net, const double* thetas, int64_t nsamples, int64_t p, const double* pts, int64_t n, int ddof,
+                      double* mean, double* std, double* preds);
+
+/*
  * Run-time options of a handle.  "gemm" = arithmetic of the hidden-layer GEMMs of the 64- / 128-wide (neuron-split) kernels:
  *   "split" (default) — every fp32 product rebuilt from three bf16 pieces per operand on the bf16 matrix pipe (6 MFMAs, fp32 accumulation):
  *                       2-4 x the rounding error of an fp32 fmaf chain, ~1.35 x faster (error budget: DESIGN.md section 6);

@@ -281,6 +281,23 @@ function phi(e::HIPEngine, net::Integer, θ::AbstractVector{<:Real}, x::Abstract
 end
 
 """
+    phi_ensemble(e, net, Θ, x; ddof = 0, return_preds = false) -> (mean, std[, preds])
+
+`phi` of network `net` (1-based) at every COLUMN of `Θ` (P × S: full parameter vectors, e.g. the retained draws of a BPINN chain) and the
+columns of `x` (d × N), with the mean and the standard deviation over the S predictions formed on the device (`pinn_phi_ensemble`, DESIGN.md
+§4.9; the ensemble curves of `ahmc_bayesian_pinn_pde`, ext/bpinn/PDE_BPINN.jl:254-302).  `ddof = 1`: the corrected standard deviation
+(`Statistics.std`'s default); `preds` is N × S.
+"""
+function phi_ensemble(e::HIPEngine, net::Integer, Θ::AbstractMatrix{<:Real}, x::AbstractMatrix; ddof::Integer = 0, return_preds::Bool = false)
+    Θ64 = Matrix{Float64}(Θ); x64 = Matrix{Float64}(x); n = size(x64, 2); S = size(Θ64, 2)
+    μ = zeros(Float64, n); σ = zeros(Float64, n); preds = return_preds ? zeros(Float64, n, S) : zeros(Float64, 0, 0)
+    GC.@preserve Θ64 x64 μ σ preds check(ccall(sym(:pinn_phi_ensemble), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        e.h, net - 1, Θ64, S, size(Θ64, 1), x64, n, ddof, μ, σ, return_preds ? pointer(preds) : Ptr{Float64}(C_NULL)), "pinn_phi_ensemble")
+    return return_preds ? (μ, σ, preds) : (μ, σ)
+end
+
+"""
     derivative(e, net, θ, x, axes) -> 1 × N
 
 `numeric_derivative(phi, u, x, εs, order, θ)` of the reference (src/pinn_types.jl:445-482) through the engine: the EXACT derivative of the trial

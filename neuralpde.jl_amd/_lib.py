@@ -40,6 +40,7 @@ SYMBOLS = [
     "pinn_loss_grad_sharded_device_f64", "pinn_loss_grad_sharded_f64",
     "pinn_hmc_init", "pinn_hmc_set_metric", "pinn_hmc_draws", "pinn_hmc_get",
     "pinn_lbfgs_init", "pinn_lbfgs_steps", "pinn_lbfgs_get",
+    "pinn_phi_ensemble",
 ]
 
 
@@ -124,6 +125,10 @@ class Library:
             L.pinn_lbfgs_init.argtypes = [vp, dp, C.c_int64, C.c_int, fp]
             L.pinn_lbfgs_steps.argtypes = [vp, C.c_int, C.c_int, C.c_double, dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
             L.pinn_lbfgs_get.argtypes = [vp, dp, C.c_int64, dp, dp]
+        except AttributeError:
+            pass
+        try:                                     # (ensemble prediction: variant libraries built before it still load)
+            L.pinn_phi_ensemble.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int, dp, dp, dp]
         except AttributeError:
             pass
         L.pinn_lbfgs.argtypes = [vp, C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_double, fp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -433,6 +438,23 @@ class Engine:
                                                         flat.ctypes.data_as(C.POINTER(C.c_double)), pts.shape[1], len(axes), ax,
                                                         out.ctypes.data_as(C.POINTER(C.c_double))), "pinn_derivative_f64")
         return out
+
+    def phi_ensemble(self, net: int, thetas, pts, ddof: int = 0, return_preds: bool = False):
+        """`pinn_phi_ensemble`: the trial function of network `net` at every row of thetas (S x P full parameter vectors) and the columns of
+        pts (d x N; a single point may be given as (d,)), reduced over the rows on the device: -> (mean, std[, preds (S x N)]), `std` with
+        numpy's `ddof`.  The compute type follows the handle (double in float64 mode, the float kernel otherwise); the statistics are in double."""
+        th = np.atleast_2d(_f64(thetas))
+        pts = np.asarray(pts, dtype=np.float64)
+        if pts.ndim == 1:
+            pts = pts.reshape(-1, 1)
+        flat = np.ascontiguousarray(pts.T).reshape(-1)
+        n, dp = pts.shape[1], C.POINTER(C.c_double)
+        mean, std = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        preds = np.zeros((th.shape[0], n), dtype=np.float64) if return_preds else None
+        self.L.check(self.L.lib.pinn_phi_ensemble(self.h, int(net), th.ctypes.data_as(dp), th.shape[0], th.shape[1], flat.ctypes.data_as(dp), n, int(ddof),
+                                                  mean.ctypes.data_as(dp), std.ctypes.data_as(dp), preds.ctypes.data_as(dp) if return_preds else None),
+                     "pinn_phi_ensemble")
+        return (mean, std, preds) if return_preds else (mean, std)
 
     def phi(self, net: int, theta, pts) -> np.ndarray:
         th = _f32(theta)

@@ -224,7 +224,7 @@ class Normal:
 
 def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, bcstd=(0.01,), l2std=(0.05,), phystd=(0.05,), priorsNNw=(0.0, 2.0),
                            param=(), n_leapfrog=30, step_size=0.1, targetacceptancerate=0.8, saveats=(0.1,), numensemble=None, rng=None,
-                           sampler="host", seed=0):
+                           sampler="host", seed=0, ensemble="host"):
     """`ahmc_bayesian_pinn_pde(pde_system, discretization; draw_samples, bcstd, phystd, priorsNNw, Kernel = HMC(0.1, 30), saveats,
     numensemble)` — the forward-problem form of ext/bpinn/PDE_BPINN.jl:371-640: the posterior over the network parameters is
     prior N(priorsNNw[1], priorsNNw[2]^2 I) x physics likelihood (`pinn_loglik_grad`: every leapfrog step is ONE fused device evaluation,
@@ -234,9 +234,13 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
     priors' first parameter, as in the reference), the discretization built with `param_estim = True` and the observations as `data_loss`
     terms (the reference's `dataset`), whose standard deviations are `l2std` — the L2 data term then sits in the same fused device call.
     `sampler = "device"` runs the transitions resident on the device (`pinn_hmc_*`; momenta and uniforms from its counter-based generator
-    keyed by `seed`, the host `rng` — default_rng(seed) unless given — only feeds the initial step-size search); `stats["sampler"]` says which ran."""
+    keyed by `seed`, the host `rng` — default_rng(seed) unless given — only feeds the initial step-size search); `stats["sampler"]` says which ran.
+    `ensemble = "device"` (independent of `sampler`) forms the ensemble curves in ONE `pinn_phi_ensemble` call per dependent variable — every
+    retained draw's prediction and the mean / std over them on the device — instead of one trial-function call per draw; `stats["ensemble"]`."""
     if sampler not in ("host", "device"):
         raise ValueError(f"sampler must be \"host\" or \"device\", not {sampler!r}")
+    if ensemble not in ("host", "device"):
+        raise ValueError(f"ensemble must be \"host\" or \"device\", not {ensemble!r}")
     if rng is None:
         rng = np.random.default_rng() if sampler == "host" else np.random.default_rng(seed)
     rep = npde.symbolic_discretize(pde_system, discretization)
@@ -282,6 +286,7 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
     else:
         samples, stats = _hmc(logp_grad, theta0, int(draw_samples), int(n_leapfrog), float(step_size), float(targetacceptancerate), rng)
     stats["sampler"] = sampler
+    stats["ensemble"] = ensemble
     numensemble = int(draw_samples // 3) if numensemble is None else int(numensemble)
     # inference: the last `numensemble` draws on the saveats grid (one spacing per independent variable), per dependent variable
     doms = {str(d.variable): (float(d.domain.lo), float(d.domain.hi)) for d in pde_system.domain}
@@ -301,6 +306,11 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
             axes.append(np.arange(lo, hi + 0.5 * step, step))
         mesh = np.meshgrid(*axes, indexing="ij")
         pts = np.stack([m.ravel() for m in mesh])
+        if ensemble == "device":                 # the full sample vectors and the variable's network index: the engine slices
+            net = (rep.phi[i] if isinstance(rep.phi, (list, tuple)) else rep.phi).net
+            mean, std = eng.phi_ensemble(net, ens_samples[:numensemble], pts)
+            ens.append(mean); ens_std.append(std); tps.append(pts)
+            continue
         preds = np.stack([rep.phi[i](pts, npde.depvar_params(rep, th, name))[0] if isinstance(rep.phi, (list, tuple)) else rep.phi(pts, th)[0]
                           for th in ens_samples[:numensemble]])     # the reference predicts with the FIRST numensemble of its slice (:302)
         ens.append(preds.mean(axis=0)); ens_std.append(preds.std(axis=0)); tps.append(pts)

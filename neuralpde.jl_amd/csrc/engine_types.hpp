@@ -323,6 +323,7 @@ struct pinn_engine {
     void* lbfgs = nullptr;           // resident L-BFGS state (engine.cpp: LbfgsState; pinn_lbfgs_init), nullptr = none
     int lbfgs_history = 0;           // its history length (pinn_describe)
     int lbfgs_chunk = 8;             // option "lbfgs_chunk": slots pinn_lbfgs_steps queues between two downloads of the control block, 1..64
+    void* ens = nullptr;             // buffers of pinn_phi_ensemble (engine.cpp: EnsState), nullptr = none yet
 };
 
 namespace pe {
