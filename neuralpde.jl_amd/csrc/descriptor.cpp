@@ -25,9 +25,15 @@ int parse_descriptor(const char* text, pinn_engine& E) {
     if (!expect("params") || !(in >> E.np >> E.ne >> E.p_theta_off)) return fail("descriptor: params");
     if (E.np < 0 || E.np > pk::MAX_PARAMS || E.ne > E.np) return fail("descriptor: at most 4 PDE parameters are supported");
     if (!expect("defaults")) return fail("descriptor: defaults");
-    E.p_defaults.assign(pk::MAX_PARAMS, 0.f);
-    for (int i = 0; i < E.np; ++i)
-        if (!(in >> E.p_defaults[i])) return fail("descriptor: defaults values");
+    // each value is read twice from its own token: as double (what the float64 mode evaluates) and as float exactly as the fp32 kernels
+    // always got it (the decimal rounded once to float, not through the double)
+    E.p_defaults.assign(pk::MAX_PARAMS, 0.0);
+    E.p_defaults32.assign(pk::MAX_PARAMS, 0.f);
+    for (int i = 0; i < E.np; ++i) {
+        if (!(in >> tok)) return fail("descriptor: defaults values");
+        std::istringstream t64(tok), t32(tok);
+        if (!(t64 >> E.p_defaults[i]) || !(t32 >> E.p_defaults32[i])) return fail("descriptor: defaults values");
+    }
     if (ver == 2) {                            // pnames <np names>
         if (!expect("pnames")) return fail("descriptor: pnames");
         ctx.params.resize(E.np);

@@ -538,7 +538,7 @@ int pinn_create_on(const char* descriptor, int device, pinn_handle* out) {
         pinn_destroy(E.release());                   // releases whatever was allocated
         return fail("device allocation failed");
     }
-    plat_h2d(E->d_defaults, E->p_defaults.data(), sizeof(float) * pk::MAX_PARAMS, E->stream);
+    plat_h2d(E->d_defaults, E->p_defaults32.data(), sizeof(float) * pk::MAX_PARAMS, E->stream);
     // one pinned block for the host entry points; the reduction writes its results straight into it
     E->hp_theta = (float*)plat_host_alloc(sizeof(float) * (2 * E->ntheta + K + 2) + sizeof(double) * K);
     if (!E->hp_theta) {

@@ -232,7 +232,8 @@ using pe::Coupled; using pe::Group; using pe::MergedUnit; using pe::Net; using p
 struct pinn_engine {
     int64_t ntheta = 0;
     int np = 0, ne = 0, p_theta_off = 0;
-    std::vector<float> p_defaults;
+    std::vector<double> p_defaults;  // values of the PDE parameters that are not estimated, as the descriptor states them (the float64 mode reads these)
+    std::vector<float> p_defaults32; // the same decimals rounded to float: what d_defaults uploads for the fp32 kernels
     std::vector<Net> nets;
     std::vector<Term> terms;
     std::vector<Term> terms0;        // the terms as parsed, before the planner's rewrites (Laplacian fusion, source hoisting): what the float64 mode evaluates

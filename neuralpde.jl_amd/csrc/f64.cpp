@@ -163,7 +163,7 @@ static void f64_affine(const pinn_engine& E, const Term& T, F64Term& F) {
     std::vector<Form> row((size_t)R0 + T.ops.size());
     for (auto& f : row) f.a.assign((size_t)ns, 0.0);
     for (int i = 0; i < dt; ++i) row[i].t.push_back({1.0, i});
-    for (int k = 0; k < np; ++k) { if (k < E.ne) row[dt + k].ok = false; else row[dt + k].k = k < (int)E.p_defaults.size() ? (double)E.p_defaults[k] : 0.0; }
+    for (int k = 0; k < np; ++k) { if (k < E.ne) row[dt + k].ok = false; else row[dt + k].k = k < (int)E.p_defaults.size() ? E.p_defaults[k] : 0.0; }
     for (int q = 0; q < ns; ++q) row[dt + np + q].a[q] = 1.0;
     auto has_u = [&](const Form& f) { for (double x : f.a) if (x != 0.0) return true; return false; };
     auto is_const = [&](const Form& f) { return f.ok && !has_u(f) && f.t.empty(); };
@@ -236,7 +236,7 @@ static int f64_lin_install(pinn_engine& E, F64Term& F, const Term& T0) {
     pk::F64LinSrcArgs a;
     std::memset(&a, 0, sizeof a);
     a.pts = F.d_pts; a.N = (int)F.n; a.dt = T0.d; a.np = E.np; a.nslots = ns; a.nops = F.nops;
-    for (int j = 0; j < pk::MAX_PARAMS; ++j) a.pdef[j] = j < (int)E.p_defaults.size() ? (double)E.p_defaults[j] : 0.0;
+    for (int j = 0; j < pk::MAX_PARAMS; ++j) a.pdef[j] = j < (int)E.p_defaults.size() ? E.p_defaults[j] : 0.0;
     a.prog = F.d_prog; a.imm = F.d_imm;
     a.nterms = (int)F.lin_terms.size();
     for (int j = 0; j < a.nterms; ++j) { a.coef[j] = F.lin_terms[j].first; a.row[j] = F.lin_terms[j].second; }
@@ -482,7 +482,7 @@ static int f64_build(pinn_engine& E, const F64Term& F, int dt, const std::map<in
     a.r_pbar = rows; rows += std::max(E.ne, 1);
     a.r_sq = rows; rows += 1;
     a.np = E.np; a.ne = E.ne; a.p_off = E.p_theta_off;
-    for (int j = 0; j < pk::MAX_PARAMS; ++j) a.pdef[j] = j < (int)E.p_defaults.size() ? (double)E.p_defaults[j] : 0.0;
+    for (int j = 0; j < pk::MAX_PARAMS; ++j) a.pdef[j] = j < (int)E.p_defaults.size() ? E.p_defaults[j] : 0.0;
     a.prog = F.d_prog; a.imm = F.d_imm; a.nops = F.nops; a.out_row = F.out_row; a.nslots = F.nslots;
     for (int s = 0; s < F.nslots; ++s) { a.slot_chan[s] = F.slot_chan[s]; a.slot_net[s] = F.slot_net[s]; }
     a.nrows = rows;
@@ -735,7 +735,7 @@ static int f64_stencil_term(pinn_engine& E, int t, const double* theta, double* 
     std::memset(&ta, 0, sizeof ta);
     ta.pts = F0.d_pts; ta.dt = T0.d; ta.n = (int)n; ta.theta = theta;
     ta.np = E.np; ta.ne = E.ne; ta.p_off = E.p_theta_off;
-    for (int j = 0; j < pk::MAX_PARAMS; ++j) ta.pdef[j] = j < (int)E.p_defaults.size() ? (double)E.p_defaults[j] : 0.0;
+    for (int j = 0; j < pk::MAX_PARAMS; ++j) ta.pdef[j] = j < (int)E.p_defaults.size() ? E.p_defaults[j] : 0.0;
     ta.pw = (T.pw_n == T.n && T.pw_n > 0) ? T.d_pw : nullptr;
     ta.data = F0.ndata > 0 ? F0.d_data : nullptr;
     ta.uv = S.d_uv; ta.nv = nv;

@@ -1056,3 +1056,65 @@ def test_f64_affine_residual_fast_path(npde, use_emu):
     eng.set_sampler(0, [0.0, 0.0], [1.0, 1.0], 64, seed=3, kind=1)
     eng.adam_f64(np.asarray(rep.flat_init_params, dtype=np.float64), 2, 1e-3)
     assert int(eng.get_option("f64_affine")) == 4
+
+
+@pytest.mark.parametrize("toggles", ["", "PINN_F64_NO_LIN", "PINN_F64_NO_MFMA", "PINN_F64_NO_MERGE", "PINN_F64_NO_LIN,PINN_F64_NO_MFMA,PINN_F64_NO_MERGE"])
+def test_f64_mode_reads_fixed_parameters_in_double(npde, use_emu, toggles):
+    """PDE parameters that are not estimated keep their descriptor value in double: a = 0.7 and b = -1.3 (neither is a float32 number, so a
+    float copy would show at 1e-8) in a nonlinear interior term (the tape interpreter) and in an affine Robin term (coefficient and data of the
+    affine fast path) — losses, gradient, residuals, per-term gradients, the BPINN log-likelihood and one resident Adam step against the
+    exact-mode oracle, on the matrix-pipe and lane-per-point kernels, with and without the affine path and merged launches"""
+    import os
+    x, y = npde.parameters("x y")
+    a, b = npde.parameters("a b")
+    (u,) = npde.variables("u")
+    U = u(x, y)
+    Dx, Dy = npde.Differential(x), npde.Differential(y)
+    eqs = [npde.Eq(a * ((Dx ** 2)(U) + (Dy ** 2)(U)) + b * U * Dx(U) + Dy(U), sp.sin(sp.pi * x) * y)]
+    bcs = [npde.Eq(u(0, y) + b * Dx(u(0, y)), a * sp.cos(y)), npde.Eq(u(x, 1), a * x)]
+    dom = [npde.In(x, npde.Interval(0.0, 1.0)), npde.In(y, npde.Interval(0.0, 1.0))]
+    sysm = npde.PDESystem(eqs, bcs, dom, [x, y], [U], ps=[a, b], defaults={a: 0.7, b: -1.3})
+    chain = npde.Chain(npde.Dense(2, 16, "tanh"), npde.Dense(16, 16, "tanh"), npde.Dense(16, 1))
+    strat = npde.QuasiRandomTraining(37, bcs_points=19, sampling_alg=npde.SobolSample(seed=3), resampling=False, minibatch=1)
+    prob = helpers.oracle_problem(npde, sysm, [chain])
+    names = [t for t in toggles.split(",") if t]
+    for t in names:
+        os.environ[t] = "1"
+    try:
+        rep = npde.symbolic_discretize(sysm, npde.PhysicsInformedNN(chain, strat, init_params=tp.theta_for(chain, 23), precision="f64"))
+        eng = rep.engine
+        sets = rep.pde_train_sets + rep.bcs_train_sets
+        th = np.asarray(rep.flat_init_params, dtype=np.float64)
+        assert th.size == chain.nparams                                              # (nothing estimated)
+        w = np.linspace(1.0, 2.0, eng.K)
+        l, g = eng.loss_grad_f64(th, w)
+        assert eng.get_option("f64_path") == ("lanes" if "PINN_F64_NO_MFMA" in names else "mfma")
+        assert int(eng.get_option("f64_affine")) == (0 if "PINN_F64_NO_LIN" in names else 2)
+        res = [eng.residual_f64(k, th, s.shape[1]) for k, s in enumerate(sets)]
+        L, tg = eng.term_grads_f64(th)
+        stds = np.linspace(0.05, 0.2, eng.K)
+        ll, gl, gs = eng.loglik_grad_f64(th, stds)
+        th1, hist = eng.adam_f64(th, 1, 3e-3, w, eps=1.0)
+    finally:
+        for t in names:
+            os.environ.pop(t, None)
+    ref = po.loss_and_grad(prob, th, sets, weights=w, mode="exact", per_term_grads=True)
+    le, g2, gi = helpers.rel_errors(l, g, ref)
+    print("fixed parameters in float64 mode:", toggles, le.max(), g2, gi)
+    assert le.max() < EXACT and g2 < EXACT and gi < EXACT, (le, g2, gi)
+    for k, s in enumerate(sets):
+        rr = po.residual_values(prob, th, k, s, mode="exact").reshape(-1)
+        assert np.max(np.abs(res[k] - rr)) < 1e-12 * max(1.0, np.max(np.abs(rr))), k
+        assert abs(L[k] - ref.term_losses[k]) < EXACT * abs(ref.term_losses[k])
+        assert np.linalg.norm(tg[k] - ref.term_grads[k]) < EXACT * np.linalg.norm(ref.term_grads[k]), k
+    N = np.array([s.shape[1] for s in sets], dtype=np.float64)
+    refl = po.loss_and_grad(prob, th, sets, weights=N / (2.0 * stds ** 2), mode="exact")
+    sse = refl.term_losses * N
+    ll_ref = float(np.sum(-0.5 * N * np.log(2 * np.pi) - N * np.log(stds) - sse / (2 * stds ** 2)))
+    assert abs(ll - ll_ref) < EXACT * abs(ll_ref)
+    assert np.linalg.norm(gl + refl.grad) < EXACT * np.linalg.norm(refl.grad)
+    np.testing.assert_allclose(gs, -N / stds + sse / stds ** 3, rtol=EXACT)
+    # one resident Adam step with eps = 1 (the first step of Adam with a small eps is lr * sign(g): blind to a gradient that is a little off)
+    th_host = _host_adam(th, [lambda t_: ref.grad], 3e-3, eps=1.0)
+    assert abs(hist[0] - ref.loss) < EXACT * abs(ref.loss)
+    assert np.linalg.norm(th1 - th_host) < EXACT * np.linalg.norm(th_host - th)
