@@ -261,7 +261,12 @@ int pinn_adam_get(pinn_handle h, float* theta, int64_t p);
  * device — parameters, moments, the redrawn point sets (the fp32 samplers' points widened on the device: StochasticTraining /
  * QuasiRandomTraining(resampling = true) with the reference's default Float64 parameters, src/discretize.jl:432-449,
  * src/training_strategies.jl:271-282, 365-389), residual + gradient kernels, Adam — and pinn_adam_init / pinn_adam_get convert at the
- * boundary; in float32 mode these two narrow / widen at the boundary. */
+ * boundary; in float32 mode these two narrow / widen at the boundary.
+ * Each precision mode keeps an optimiser state of its own: pinn_adam_steps continues the state of the mode the handle is in.  The double state goes
+ * with the mode ("precision" = "f32" frees it: after a return to "f64" pinn_adam_steps / pinn_adam_get are refused until pinn_adam_init is called
+ * again), the fp32 state survives a visit to "f64".  Evaluations, pinn_phi / pinn_derivative / pinn_phi_ensemble, pinn_lbfgs, the resident L-BFGS and
+ * HMC, pinn_set_timing, "persistent" on / off and an option or a point set taken to another value and back between two pinn_adam_steps calls leave
+ * the iterate, the moments and the step counter alone: k1 + k2 steps in two calls are bit-equal to k1 + k2 in one (tests/test_handle_history.py). */
 int pinn_adam_init_f64(pinn_handle h, const double* theta, int64_t p);
 int pinn_adam_get_f64(pinn_handle h, double* theta, int64_t p);
 /*
@@ -307,6 +312,8 @@ int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int histor
  *     u       = word(P, 0) / 2^32
  *   The draw counter lives in the handle, starts at 0 in pinn_hmc_init and advances by one per completed draw (also when momenta and uniforms are
  *   supplied): 2 + 3 draws in two calls are bit-equal to 5 draws in one.
+ * The precision mode taken to the other value AND BACK between two calls is not a change: the chain continues, and its evaluations read the point
+ * sets as the mode holds them after the return (double copies converted from the float buffers).
  * Refused, with the handle left as it was: any call before pinn_hmc_init; a handle whose precision mode changed since (init again); a term with a
  * device sampler (the target must be fixed, as for pinn_lbfgs); a handle on a communicator; p != ntheta, k != the number of terms; stds, prior
  * sigmas or metric entries that are not positive; eps <= 0, n_leapfrog < 1, ndraws < 1.
@@ -342,6 +349,8 @@ int pinn_hmc_get(pinn_handle h, double* theta, int64_t p, double* logp, double* 
  *                     call returns, as in pinn_lbfgs ($PINN_LBFGS_KEEP_GEMM=1 disables that).
  *   pinn_lbfgs_get    the current iterate: theta (p doubles), *f (nullable), grad (p doubles, nullable).
  * The state has buffers of its own: evaluations, pinn_adam_* and pinn_hmc_* between two calls leave it alone and vice versa.
+ * The precision mode taken to the other value AND BACK between two calls is not a change: the iteration continues, on the point sets as the mode
+ * holds them after the return (double copies converted from the float buffers).
  * Refused, with the handle left as it was: pinn_lbfgs_steps / _get before pinn_lbfgs_init; a handle whose precision mode changed since (init again);
  * a term with a device sampler; a handle on a communicator; p != ntheta; history outside 1..64; maxiters < 1; max_evals < 1.
  */
