@@ -3,13 +3,8 @@
 // Mirrors what the reference does once per `discretize` call on the host
 // (src/discretize.jl:413-767: build loss functions, merge with the strategy, build full_loss_function)
 // and what it does per optimiser iteration (src/discretize.jl:567-598).
-#include "engine_types.hpp"
+#include "resident.hpp"
 #include "aux_kernels.hpp"
-#include "hmc_kernels.hpp"
-#include "lbfgs_kernels.hpp"
-#include "ens_kernels.hpp"
-
-#include <type_traits>
 
 #ifdef PINN_EMU
 namespace wv {
@@ -88,7 +83,9 @@ void eval_sources(pinn_engine& E, Term& T) {
     aux::launch_src(a, E.stream);
 }
 
-int ensure_points(pinn_engine& E) {
+}  // namespace
+
+int pe::ensure_points(pinn_engine& E) {
     for (size_t t = 0; t < E.terms.size(); ++t) {
         if (!E.terms[t].d_pts || E.terms[t].n <= 0)
             return fail("term " + std::to_string(t) + " has no collocation points (call pinn_set_points first)");
@@ -97,6 +94,8 @@ int ensure_points(pinn_engine& E) {
     }
     return 0;
 }
+
+namespace {
 
 // the weights every network's kernels read in this evaluation: the packed image rebuilt by k_pack (DGM kernels read theta itself)
 void pack_all(pinn_engine& E, const float* d_theta = nullptr, bool packed_fresh = false) {
@@ -216,35 +215,6 @@ int upload_int_rule(pinn_engine& E, int q) {
     plat_h2d(E.d_int_w, wf.data(), sizeof(float) * q, E.stream);
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());      // (pageable temporaries)
     return 0;
-}
-
-// one caller array of n elements of type T, seen as element type V at the precision boundary of a float / double entry point: the caller's
-// own array when T is V; otherwise a converted copy — of the caller's values for an input (T const), or one that put() converts back into
-// the caller's array for an output.  A null array stays null.
-template <class V, class T> class As {
-    static constexpr bool same = std::is_same_v<V, std::remove_const_t<T>>;
-    T* x_;
-    std::vector<V> copy_;
-public:
-    As(T* x, size_t n) : x_(x) {
-        if constexpr (!same) {
-            if (x && std::is_const_v<T>) copy_.assign(x, x + n);      // an input: the caller's values, converted
-            else if (x) copy_.resize(n);                               // an output: written by the evaluation, converted back by put()
-        }
-    }
-    auto get() {
-        if constexpr (same) return x_;
-        else return x_ ? copy_.data() : nullptr;
-    }
-    int put() {                                          // (outputs; returns 0)
-        if constexpr (!same) if (x_) std::copy(copy_.begin(), copy_.end(), x_);
-        return 0;
-    }
-};
-template <class V, class T> As<V, T> as(T* x, size_t n) { return As<V, T>(x, n); }
-
-int check_theta(const pinn_engine& E, const char* who, int64_t p) {
-    return p == E.ntheta ? 0 : fail(std::string(who) + ": theta length " + std::to_string(p) + " != ntheta " + std::to_string(E.ntheta));
 }
 
 }  // namespace
@@ -493,10 +463,6 @@ int pe::upload_theta(pinn_engine& E, const float* theta, int64_t p) {
 // =================================================================================================
 // C ABI
 // =================================================================================================
-static void hmc_free(pinn_engine& E);
-static void lbfgs_free(pinn_engine& E);
-static void ens_free(pinn_engine& E);
-
 extern "C" {
 
 const char* pinn_backend(void) { return plat_name(); }
@@ -704,9 +670,7 @@ static int gemm_auto_check(pinn_engine& E, const float* d_theta, const float* te
 static bool eval_eligible(pinn_engine& E);
 static int eval_fused(pinn_engine& E, const float* d_theta, float* d_out, const float* term_w, double* lossraw);
 static bool train_timed_out(pinn_engine& E);
-// loss + gradient for a host entry point that synchronises right after: small problems in ONE launch (eval_fused), everything else by
-// run_loss_grad; results in d_out / lossraw either way.  Synchronises.
-static int eval_and_sync(pinn_engine& E, float* d_out, const float* term_w, double* lossraw, bool timing) {
+extern "C++" int pe::eval_and_sync(pinn_engine& E, float* d_out, const float* term_w, double* lossraw, bool timing) {
     E.eval_path = 1;
     if (ensure_points(E)) return 1;                  // (every path: the one-launch evaluation below does not go through run_loss_grad's check — ADVICE r04)
     if (eval_eligible(E)) {
@@ -1103,9 +1067,7 @@ int pinn_get_points(pinn_handle h, int term, float* pts, int64_t n) {
     return 0;
 }
 
-// switch the GEMM arithmetic of a live handle: the kernel plan is rebuilt for the other mode (packed weight images, gradient-slab maps and
-// reduction tables differ), the installed point sets, samplers, per-point data / weights and the optimiser state stay
-static int replan_gemm(pinn_engine& E, int mode) {
+extern "C++" int pe::replan_gemm(pinn_engine& E, int mode) {
     if (mode == E.gemm) return 0;
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     const int prev = E.gemm;
@@ -1151,7 +1113,6 @@ static void measure_grad_health(pinn_engine& E, const float* grad_and_sums, cons
     for (int k = 0; k < K; ++k) L += (term_w ? (double)term_w[k] : 1.0) * (double)grad_and_sums[P + k] / (double)E.terms[k].n_norm;
     E.grad_health = L > 0.0 ? std::sqrt(g2) / std::sqrt(L) : -1.0;
 }
-static int replan_gemm(pinn_engine& E, int mode);
 // the policy's check at the device-resident parameters d_theta (clock: `now` optimiser steps / evaluations)
 static int gemm_auto_check(pinn_engine& E, const float* d_theta, const float* term_w, long long now) {
     if (!E.gemm_auto || E.f64 || E.comm) return 0;
@@ -1307,6 +1268,19 @@ static int adam_init_f32(pinn_engine& E, const float* theta) {
     return 0;
 }
 
+// the bias-correction table of steps opt_t + 1 .. opt_t + nsteps, [c1 | c2] = 1 / (1 - beta^t) per step: filled into c12 and queued for upload to
+// E.d_c12 (grown on demand; false: the allocation failed).  c12 is pageable: the caller keeps it until its next synchronisation
+static bool upload_c12(pinn_engine& E, int nsteps, float beta1, float beta2, std::vector<float>& c12) {
+    if (!dev_grow(E.d_c12, E.c12_cap, 2 * (size_t)nsteps, E.stream)) return false;
+    c12.resize(2 * (size_t)nsteps);
+    for (int s = 0; s < nsteps; ++s) {
+        c12[2 * s] = (float)(1.0 / (1.0 - std::pow((double)beta1, (double)(E.opt_t + s + 1))));
+        c12[2 * s + 1] = (float)(1.0 / (1.0 - std::pow((double)beta2, (double)(E.opt_t + s + 1))));
+    }
+    plat_h2d(E.d_c12, c12.data(), sizeof(float) * c12.size(), E.stream);
+    return true;
+}
+
 // pinn_adam_steps through a hipGraph (PINN_GRAPH=1; see the note there).  Returns 0 when all nsteps ran; -1 when the device-side step
 // state could not be set up (NOTHING has run: the caller takes the plain loop); 1 when a step failed after the optimiser state may
 // already have advanced (g_err holds the reason: the caller reports the failure and does NOT run the steps again).
@@ -1318,23 +1292,12 @@ static int adam_steps_graph(pinn_engine& E, int nsteps, float lr, float beta1, f
         E.d_sampled = (int*)plat_malloc(sizeof(int) * K);
         if (!E.d_step || !E.d_draws || !E.d_sampled) return -1;
     }
-    if (E.c12_cap < nsteps) {
-        plat_sync(E.stream);
-        plat_free(E.d_c12);
-        E.d_c12 = (float*)plat_malloc(sizeof(float) * 2 * (size_t)nsteps);
-        E.c12_cap = E.d_c12 ? nsteps : 0;
-        if (!E.d_c12) return -1;
-    }
-    std::vector<float> c12(2 * (size_t)nsteps);
-    for (int s = 0; s < nsteps; ++s) {
-        c12[2 * s] = (float)(1.0 / (1.0 - std::pow((double)beta1, (double)(E.opt_t + s + 1))));
-        c12[2 * s + 1] = (float)(1.0 / (1.0 - std::pow((double)beta2, (double)(E.opt_t + s + 1))));
-    }
+    std::vector<float> c12;
+    if (!upload_c12(E, nsteps, beta1, beta2, c12)) return -1;
     std::vector<unsigned> draws(K);
     std::vector<int> sampled(K);
     const int zero = 0;
     for (int t = 0; t < K; ++t) { draws[t] = E.terms[t].draws; sampled[t] = E.terms[t].sampler != 0; }
-    plat_h2d(E.d_c12, c12.data(), sizeof(float) * c12.size(), E.stream);
     plat_h2d(E.d_draws, draws.data(), sizeof(unsigned) * K, E.stream);
     plat_h2d(E.d_sampled, sampled.data(), sizeof(int) * K, E.stream);
     plat_h2d(E.d_step, &zero, sizeof(int), E.stream);
@@ -1407,12 +1370,7 @@ static int upload_resample_table(pinn_engine& E, int* max_n) {
     }
     if (samp.empty()) return 0;
     if (plat_sync(E.stream)) { fail(std::string("device error: ") + plat_last_error()); return -2; }      // (an earlier launch may still read the table)
-    if ((int)samp.size() > E.train_samp_cap) {
-        plat_free(E.d_train_samp);
-        E.d_train_samp = plat_malloc(sizeof(pk::TrainSampler) * samp.size());
-        E.train_samp_cap = E.d_train_samp ? (int)samp.size() : 0;
-        if (!E.d_train_samp) { fail("device allocation failed (table of redrawn terms)"); return -2; }
-    }
+    if (!dev_grow(E.d_train_samp, E.train_samp_cap, sizeof(pk::TrainSampler) * samp.size(), E.stream)) { fail("device allocation failed (table of redrawn terms)"); return -2; }
     plat_h2d(E.d_train_samp, samp.data(), sizeof(pk::TrainSampler) * samp.size(), E.stream);
     if (plat_sync(E.stream)) { fail(std::string("device error: ") + plat_last_error()); return -2; }      // (samp is a pageable temporary)
     return (int)samp.size();
@@ -1648,18 +1606,8 @@ static int adam_steps_train(pinn_engine& E, int nsteps, float lr, float beta1, f
     Group& G = E.groups[0];
     pk::TrainArgs ta;
     if (train_common(E, ta, term_w)) return 1;
-    if (E.c12_cap < nsteps) {
-        plat_sync(E.stream);
-        plat_free(E.d_c12);
-        E.d_c12 = (float*)plat_malloc(sizeof(float) * 2 * (size_t)nsteps);
-        E.c12_cap = E.d_c12 ? nsteps : 0;
-        if (!E.d_c12) return fail("device allocation failed (bias-correction table)");
-    }
-    std::vector<float> c12(2 * (size_t)nsteps);
-    for (int s = 0; s < nsteps; ++s) {
-        c12[2 * s] = (float)(1.0 / (1.0 - std::pow((double)beta1, (double)(E.opt_t + s + 1))));
-        c12[2 * s + 1] = (float)(1.0 / (1.0 - std::pow((double)beta2, (double)(E.opt_t + s + 1))));
-    }
+    std::vector<float> c12;
+    if (!upload_c12(E, nsteps, beta1, beta2, c12)) return fail("device allocation failed (bias-correction table)");
     // snapshot of the optimiser state: a launch whose workgroups were not all resident (another process filling the device) ends by its
     // barrier time-out with wrong numbers — then the state is restored and the caller runs the stand-alone loop instead
     if (!E.d_opt_bak) {
@@ -1671,7 +1619,6 @@ static int adam_steps_train(pinn_engine& E, int nsteps, float lr, float beta1, f
     plat_d2d(E.d_opt_bak + 2 * (size_t)P, E.d_opt_v, sizeof(float) * (size_t)P, E.stream);
     std::vector<unsigned> draws0(E.terms.size());
     for (size_t t = 0; t < E.terms.size(); ++t) draws0[t] = E.terms[t].draws;
-    plat_h2d(E.d_c12, c12.data(), sizeof(float) * c12.size(), E.stream);
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());       // (c12 is a pageable temporary)
     pack_all(E, E.d_opt_theta, false);                        // the weight image of the current theta; the kernel keeps it current from here on
     ta.out = E.d_opt_out; ta.lossraw = E.d_lossraw;
@@ -1727,12 +1674,7 @@ static int adam_prepare(pinn_engine& E, int nsteps, const float* term_w, const c
     for (auto& T : E.terms)
         if (T.sampler == 3 && T.seed == 0 && E.comm_size > 1)
             return fail(std::string(who) + ": an un-randomised Sobol design (seed 0) is the same on every rank and cannot be sharded; give the sampler a seed");
-    if (E.hist_cap < nsteps) {
-        plat_free(E.d_hist);
-        E.d_hist = (double*)plat_malloc(sizeof(double) * nsteps);
-        E.hist_cap = nsteps;
-        if (!E.d_hist) return fail("device allocation failed (loss history)");
-    }
+    if (!dev_grow(E.d_hist, E.hist_cap, (size_t)nsteps, E.stream)) return fail("device allocation failed (loss history)");
     std::vector<float> wn(K);
     for (int k = 0; k < K; ++k) wn[k] = (term_w ? term_w[k] : 1.0f) / (float)E.terms[k].n_norm;
     plat_h2d(E.d_w_over_n, wn.data(), sizeof(float) * K, E.stream);
@@ -1845,153 +1787,6 @@ int pinn_adam_apply(pinn_handle h, const float* grad_and_sums, int64_t n, float 
     if (loss && plat_d2h(loss, E.d_hist, sizeof(double), E.stream)) return fail("D2H copy failed");
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     return 0;
-}
-
-// The noise-floor switch of the L-BFGS routines (pinn_lbfgs, pinn_lbfgs_steps).  A line search that cannot decrease the objective along a descent
-// direction has reached the evaluation's noise floor; the split-operand GEMMs' floor is 2-4 x that of the fp32 MFMA kernels:
-// a handle in "split" mode is switched to them once per call and goes on from the same iterate.  The switch only changes arithmetic where a launch
-// group runs a family-2 kernel that exists as a split / fp32 twin; $PINN_LBFGS_KEEP_GEMM disables it; every exit path hands the handle back in the
-// mode it came in.
-struct GemmFloorSwitch {
-    pinn_engine& E;
-    bool switched = false, armed = false, has_twin = false;
-    explicit GemmFloorSwitch(pinn_engine& e) : E(e) {
-        for (const NetPlan& NP : E.netplans) has_twin = has_twin || (NP.spec && NP.spec->family == 2 && NP.spec->twin);
-    }
-    ~GemmFloorSwitch() { if (armed && E.gemm != pk::GEMM_SPLIT) { const std::string keep = g_err; replan_gemm(E, pk::GEMM_SPLIT); if (!keep.empty()) g_err = keep; } }
-    bool eligible() const { return !E.f64 && E.gemm == pk::GEMM_SPLIT && !switched && has_twin && std::getenv("PINN_LBFGS_KEEP_GEMM") == nullptr; }
-    // 0: done, `switched` says whether the handle now runs the fp32 kernels; 1: error; 2: the switch failed (the fp32 twin of a run-time specialised
-    // shape did not compile) and left the handle in split mode — replan_gemm restored the plan: the iterate reached so far is the answer, not an
-    // error
-    int engage() {
-        if (replan_gemm(E, pk::GEMM_FP32)) { if (E.gemm != pk::GEMM_SPLIT || E.groups.empty()) return 1; g_err.clear(); return 2; }
-        switched = E.gemm == pk::GEMM_FP32;
-        armed = switched;
-        return 0;
-    }
-    int finish() {                                       // the regular end of a call
-        if (!switched) return 0;
-        armed = false;
-        return replan_gemm(E, pk::GEMM_SPLIT) ? 1 : 0;
-    }
-};
-
-int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int history, double gtol, const float* term_w, double* loss_history,
-               int* iters_done) {
-    if (!h || !theta) return fail("pinn_lbfgs: null argument");
-    pinn_engine& E = *h;
-    DeviceScope scope(E.device);
-    if (p != E.ntheta) return fail("pinn_lbfgs: theta length " + std::to_string(p) + " != ntheta " + std::to_string(E.ntheta));
-    if (maxiters <= 0 || history <= 0 || history > 64) return fail("pinn_lbfgs: maxiters must be positive and history in 1..64");
-    for (auto& T : E.terms)
-        if (T.sampler != 0) return fail("pinn_lbfgs: a term redraws its points on the device; L-BFGS needs a fixed objective (fixed point sets)");
-    if (ensure_points(E)) return 1;
-    const int K = (int)E.terms.size();
-    const size_t P = (size_t)p;
-    std::vector<float> th32(P);
-    std::vector<double> g(P), x(theta, theta + P), xn(P), gn(P), d(P), q(P);
-    // one device evaluation: fused loss + gradient, or (grad == nullptr) the loss-only launch — a rejected line-search trial needs the
-    // objective only, at about a third of the cost
-    auto eval = [&](const std::vector<double>& at, std::vector<double>* grad, double& f) -> int {
-        if (E.f64) {                                     // float64 mode: the objective and its gradient in double, no fp32 noise floor
-            std::vector<double> w(K, 1.0), L(K);
-            if (term_w) for (int k = 0; k < K; ++k) w[k] = term_w[k];
-            if (f64_eval(E, at.data(), w.data(), L.data(), grad ? grad->data() : nullptr)) return 1;
-            f = 0.0;
-            for (int k = 0; k < K; ++k) f += w[k] * L[k];
-            return 0;
-        }
-        for (size_t i = 0; i < P; ++i) th32[i] = (float)at[i];
-        if (upload_theta(E, th32.data(), p)) return 1;
-        if (grad) {
-            if (eval_and_sync(E, E.hp_out, term_w, E.hp_raw, false)) return 1;
-        } else {
-            if (run_loss_grad(E, E.d_theta, E.hp_out, term_w, -1, false, E.hp_raw, false, true)) return 1;
-            if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-        }
-        f = 0.0;
-        for (int k = 0; k < K; ++k) f += (double)(term_w ? term_w[k] : 1.0f) * E.hp_raw[k] / (double)E.terms[k].n_norm;
-        if (grad)
-            for (size_t i = 0; i < P; ++i) (*grad)[i] = (double)E.hp_out[i];
-        return 0;
-    };
-    auto dot = [&](const std::vector<double>& a, const std::vector<double>& b) { double s = 0.0; for (size_t i = 0; i < P; ++i) s += a[i] * b[i]; return s; };
-    double f = 0.0;
-    if (eval(x, &g, f)) return 1;
-    std::deque<std::vector<double>> S, Y;
-    std::deque<double> RHO;
-    GemmFloorSwitch floor_switch(E);
-    int it = 0;
-    for (; it < maxiters; ++it) {
-        double gmax = 0.0;
-        for (size_t i = 0; i < P; ++i) gmax = std::max(gmax, std::fabs(g[i]));
-        if (!(gmax > gtol)) break;
-        // two-loop recursion: d = -H g
-        q = g;
-        std::vector<double> alpha(S.size());
-        for (int i = (int)S.size() - 1; i >= 0; --i) {
-            alpha[i] = RHO[i] * dot(S[i], q);
-            for (size_t j = 0; j < P; ++j) q[j] -= alpha[i] * Y[i][j];
-        }
-        double gamma = 1.0;
-        if (!S.empty()) gamma = dot(S.back(), Y.back()) / dot(Y.back(), Y.back());
-        for (size_t j = 0; j < P; ++j) q[j] *= gamma;
-        for (size_t i = 0; i < S.size(); ++i) {
-            const double beta = RHO[i] * dot(Y[i], q);
-            for (size_t j = 0; j < P; ++j) q[j] += (alpha[i] - beta) * S[i][j];
-        }
-        for (size_t j = 0; j < P; ++j) d[j] = -q[j];
-        double gd = dot(g, d);
-        if (!(gd < 0.0)) {                               // not a descent direction (stale curvature): restart from steepest descent
-            S.clear(); Y.clear(); RHO.clear();
-            for (size_t j = 0; j < P; ++j) d[j] = -g[j];
-            gd = dot(g, d);
-        }
-        // backtracking line search (Armijo, c1 = 1e-4); first iteration: step 1 / |g|_1-ish scale
-        double t = S.empty() ? std::min(1.0, 1.0 / std::sqrt(dot(g, g))) : 1.0;
-        double fn = f;
-        bool ok = false;
-        // the first trial (accepted most of the time) is a full evaluation: its gradient is the next iterate's; after a rejection the
-        // trials are loss-only evaluations and the accepted point gets its gradient from one more full evaluation
-        for (int ls = 0; ls < 30; ++ls) {
-            for (size_t j = 0; j < P; ++j) xn[j] = x[j] + t * d[j];
-            if (eval(xn, ls == 0 ? &gn : nullptr, fn)) return 1;
-            if (std::isfinite(fn) && fn <= f + 1e-4 * t * gd) {
-                if (ls > 0 && eval(xn, &gn, fn)) return 1;
-                ok = true;
-                break;
-            }
-            t *= 0.5;
-        }
-        if (!ok) {
-            // no decrease along a descent direction: the evaluation's noise floor (GemmFloorSwitch)
-            if (floor_switch.eligible()) {
-                const int sw = floor_switch.engage();
-                if (sw == 1) return 1;
-                if (sw == 2) break;
-                if (floor_switch.switched) {
-                    if (eval(x, &g, f)) return 1;
-                    S.clear(); Y.clear(); RHO.clear();   // curvature pairs carry the other arithmetic's gradient noise
-                    --it;
-                    continue;
-                }
-            }
-            break;
-        }
-        std::vector<double> sv(P), yv(P);
-        for (size_t j = 0; j < P; ++j) { sv[j] = xn[j] - x[j]; yv[j] = gn[j] - g[j]; }
-        const double sy = dot(sv, yv);
-        if (sy > 1e-10 * std::sqrt(dot(sv, sv) * dot(yv, yv))) {
-            S.push_back(std::move(sv)); Y.push_back(std::move(yv)); RHO.push_back(1.0 / sy);
-            if ((int)S.size() > history) { S.pop_front(); Y.pop_front(); RHO.pop_front(); }
-        }
-        x.swap(xn); g.swap(gn); f = fn;
-        if (loss_history) loss_history[it] = f;
-    }
-    if (loss_history) for (int i = it; i < maxiters; ++i) loss_history[i] = f;
-    if (iters_done) *iters_done = it;
-    for (size_t i = 0; i < P; ++i) theta[i] = x[i];
-    return floor_switch.finish();
 }
 
 static int adam_get_f32(pinn_engine& E, float* theta) {
@@ -2250,548 +2045,6 @@ int pinn_adam_init(pinn_handle h, const float* theta, int64_t p) { return adam_i
 int pinn_adam_init_f64(pinn_handle h, const double* theta, int64_t p) { return adam_init_twin(__func__, h, theta, p); }
 int pinn_adam_get(pinn_handle h, float* theta, int64_t p) { return adam_get_twin(__func__, h, theta, p); }
 int pinn_adam_get_f64(pinn_handle h, double* theta, int64_t p) { return adam_get_twin(__func__, h, theta, p); }
-
-}  // extern "C"
-
-// =================================================================================================
-// Resident HMC (pinn_hmc_*): the transition loop of neuralpde.jl_amd/bpinn.py `_hmc` with the chain on the device.
-// A leapfrog step = the handle's resident evaluation (float64 mode: f64_eval_resident; otherwise run_loss_grad at the narrowed copy of theta,
-// with the K sums in double) + ONE update launch (hmc_kernels.hpp); nothing is read back before the single download that ends pinn_hmc_draws.
-// The state has buffers of its own: evaluations and optimiser runs between two calls do not touch the chain, and the chain does not touch them.
-// =================================================================================================
-namespace {
-
-struct HmcState {
-    bool f64 = false;                    // the precision mode the state was initialised in
-    hmc::Args a;
-    std::vector<double> w64;             // term weights N_k / (2 s_k^2) of the evaluation, as pinn_loglik_grad forms them
-    std::vector<float> w32;
-    double* d_state = nullptr;           // [6 P + SC_COUNT]: th_cur | th_prop | r | g_cur | g_prop | minv | scalars
-    double* d_tab = nullptr;             // [3 n_prior + 3 K]: prior mu | prior sigma | lik_c | lik_d | lik_n (+ kinds as ints in d_kind)
-    int* d_kind = nullptr;
-    double* d_ev64 = nullptr;            // float64 mode: [P + K] gradient | raw sums of the running evaluation
-    float* d_ev32 = nullptr;             // fp32 mode: [P + K] floats, the K sums again as doubles in d_raw, the narrowed theta in d_th32
-    double* d_raw = nullptr;
-    float* d_th32 = nullptr;
-    double* d_samples = nullptr; double* d_stat = nullptr; double* d_mom = nullptr; double* d_uni = nullptr;
-    size_t samples_cap = 0, stat_cap = 0, mom_cap = 0, uni_cap = 0;
-    unsigned long long draws = 0;        // draw counter of the generator (advanced per completed draw, whatever supplies momenta and uniforms)
-};
-
-void hmc_release(HmcState* H) {
-    if (!H) return;
-    plat_free(H->d_state); plat_free(H->d_tab); plat_free(H->d_kind); plat_free(H->d_ev64); plat_free(H->d_ev32); plat_free(H->d_raw); plat_free(H->d_th32);
-    plat_free(H->d_samples); plat_free(H->d_stat); plat_free(H->d_mom); plat_free(H->d_uni);
-    delete H;
-}
-
-bool hmc_grow(double*& p, size_t& cap, size_t need, plat_stream st) {
-    if (cap >= need) return true;
-    plat_sync(st);
-    plat_free(p);
-    p = (double*)plat_malloc(sizeof(double) * need);
-    cap = p ? need : 0;
-    return p != nullptr;
-}
-
-// what every pinn_hmc_* call after init checks first; leaves the handle as it is
-int hmc_ready(pinn_engine& E, const char* who) {
-    if (!E.hmc) return fail(std::string(who) + ": no sampler state (call pinn_hmc_init first)");
-    if (((HmcState*)E.hmc)->f64 != (E.f64 != nullptr))
-        return fail(std::string(who) + ": the handle's precision changed since pinn_hmc_init (call pinn_hmc_init again)");
-    return 0;
-}
-int hmc_refuse_target(pinn_engine& E, const char* who) {
-    if (E.comm) return fail(std::string(who) + ": the handle belongs to a communicator; the resident sampler runs single-device chains only");
-    for (auto& T : E.terms)
-        if (T.sampler != 0) return fail(std::string(who) + ": a term redraws its points on the device; HMC needs a fixed target (fixed point sets)");
-    return 0;
-}
-
-// one evaluation at the proposal (already in the buffer the evaluation reads): [gradient | sums] into the sampler's vector
-int hmc_eval(pinn_engine& E, HmcState& H) {
-    if (H.f64) return f64_eval_resident(E, H.w64.data(), H.d_ev64);
-    return run_loss_grad(E, H.d_th32, H.d_ev32, H.w32.data(), -1, false, H.d_raw);
-}
-void hmc_leap(pinn_engine& E, HmcState& H, bool from_eval, double kick, double eps, int drift) {
-    if (H.f64) hmc::launch_leap<double>(H.a, from_eval ? H.d_ev64 : nullptr, kick, eps, drift, E.stream);
-    else hmc::launch_leap<float>(H.a, from_eval ? H.d_ev32 : nullptr, kick, eps, drift, E.stream);
-}
-const double* hmc_sse(const HmcState& H) { return H.f64 ? H.d_ev64 + H.a.P : H.d_raw; }
-
-}  // namespace
-
-static void hmc_free(pinn_engine& E) {
-    hmc_release((HmcState*)E.hmc);
-    E.hmc = nullptr;
-}
-
-extern "C" {
-
-int pinn_hmc_init(pinn_handle h, const double* theta, int64_t p, const double* stds, int k, double nn_mu, double nn_sigma,
-                  int n_prior, const int* prior_kind, const double* prior_mu, const double* prior_sigma) {
-    const char* who = "pinn_hmc_init";
-    if (!h || !theta || !stds) return fail(std::string(who) + ": null argument");
-    pinn_engine& E = *h;
-    if (check_theta(E, who, p)) return 1;
-    const int K = (int)E.terms.size();
-    if (k != K) return fail(std::string(who) + ": " + std::to_string(k) + " standard deviations for " + std::to_string(K) + " loss terms");
-    for (int j = 0; j < K; ++j)
-        if (!(stds[j] > 0.0) || !std::isfinite(stds[j])) return fail(std::string(who) + ": standard deviations must be positive");
-    if (!(nn_sigma > 0.0) || !std::isfinite(nn_sigma) || !std::isfinite(nn_mu)) return fail(std::string(who) + ": the weight prior needs a finite mean and a positive standard deviation");
-    if (n_prior < 0 || n_prior > p) return fail(std::string(who) + ": n_prior must be in 0..P");
-    if (n_prior > 0 && (!prior_kind || !prior_mu || !prior_sigma)) return fail(std::string(who) + ": null prior table");
-    for (int j = 0; j < n_prior; ++j) {
-        if (prior_kind[j] != hmc::PRIOR_NORMAL && prior_kind[j] != hmc::PRIOR_LOGNORMAL) return fail(std::string(who) + ": prior kind must be 0 (Normal) or 1 (LogNormal)");
-        if (!(prior_sigma[j] > 0.0) || !std::isfinite(prior_sigma[j]) || !std::isfinite(prior_mu[j])) return fail(std::string(who) + ": a parameter prior needs a finite mu and a positive sigma");
-    }
-    if (hmc_refuse_target(E, who)) return 1;
-    DeviceScope scope(E.device);
-    if (!E.f64 && ensure_points(E)) return 1;
-    const size_t P = (size_t)p;
-    std::unique_ptr<HmcState, void (*)(HmcState*)> H(new HmcState, hmc_release);
-    H->f64 = E.f64 != nullptr;
-    H->d_state = (double*)plat_malloc(sizeof(double) * (6 * P + hmc::SC_COUNT));
-    H->d_tab = (double*)plat_malloc(sizeof(double) * (size_t)(2 * n_prior + 3 * K));
-    H->d_kind = (int*)plat_malloc(sizeof(int) * (size_t)std::max(n_prior, 1));
-    if (H->f64) H->d_ev64 = (double*)plat_malloc(sizeof(double) * (P + K));
-    else {
-        H->d_ev32 = (float*)plat_malloc(sizeof(float) * (P + K));
-        H->d_raw = (double*)plat_malloc(sizeof(double) * (size_t)K);
-        H->d_th32 = (float*)plat_malloc(sizeof(float) * P);
-    }
-    if (!H->d_state || !H->d_tab || !H->d_kind || (H->f64 ? !H->d_ev64 : (!H->d_ev32 || !H->d_raw || !H->d_th32))) return fail(std::string(who) + ": device allocation failed");
-    hmc::Args& a = H->a;
-    std::memset(&a, 0, sizeof a);
-    a.P = (int)p; a.K = K; a.n_prior = n_prior; a.nn = (int)p - n_prior;
-    a.sse_roundtrip = H->f64 ? 1 : 0;
-    a.th_cur = H->d_state; a.th_prop = a.th_cur + P; a.r = a.th_prop + P; a.g_cur = a.r + P; a.g_prop = a.g_cur + P;
-    double* minv = a.g_prop + P;
-    a.minv = minv; a.sc = minv + P;
-    a.nn_mu = nn_mu; a.nn_sigma = nn_sigma; a.nn_var = nn_sigma * nn_sigma;
-    a.nn_const = (double)a.nn * (std::log(nn_sigma) + 0.5 * std::log(2.0 * 3.14159265358979323846));
-    double* tab = H->d_tab;
-    a.pr_mu = tab; a.pr_sigma = tab + n_prior; a.lik_c = tab + 2 * n_prior; a.lik_d = a.lik_c + K; a.lik_n = a.lik_d + K;
-    a.pr_kind = H->d_kind;
-    a.th_eval64 = H->f64 ? f64_theta_buffer(E) : nullptr;
-    a.th_eval32 = H->f64 ? nullptr : H->d_th32;
-    // host images: state (theta twice, zero momentum and gradients, unit metric), tables
-    std::vector<double> st(6 * P + hmc::SC_COUNT, 0.0), tb((size_t)(2 * n_prior + 3 * K));
-    std::copy(theta, theta + P, st.begin());
-    std::copy(theta, theta + P, st.begin() + P);
-    std::fill(st.begin() + 5 * P, st.begin() + 6 * P, 1.0);
-    for (int j = 0; j < n_prior; ++j) { tb[j] = prior_mu[j]; tb[n_prior + j] = prior_sigma[j]; }
-    H->w64.resize(K); H->w32.resize(K);
-    for (int j = 0; j < K; ++j) {
-        const double N = (double)E.terms[j].n, Nn = (double)E.terms[j].n_norm, sd = stds[j];
-        H->w64[j] = Nn / (2.0 * sd * sd);
-        H->w32[j] = (float)H->w64[j];
-        tb[2 * n_prior + j] = -0.5 * N * std::log(2.0 * 3.14159265358979323846) - N * std::log(sd);      // (loglik_from_sse's constants, same order of operations)
-        tb[2 * n_prior + K + j] = 2.0 * sd * sd;
-        tb[2 * n_prior + 2 * K + j] = Nn;
-    }
-    std::vector<int> kinds(prior_kind, prior_kind + n_prior);
-    if (plat_h2d(H->d_state, st.data(), sizeof(double) * st.size(), E.stream) || plat_h2d(H->d_tab, tb.data(), sizeof(double) * tb.size(), E.stream) ||
-        (n_prior > 0 && plat_h2d(H->d_kind, kinds.data(), sizeof(int) * kinds.size(), E.stream)))
-        return fail(std::string(who) + ": H2D copy failed");
-    if (H->f64) {
-        if (plat_h2d(a.th_eval64, theta, sizeof(double) * P, E.stream)) return fail(std::string(who) + ": H2D copy failed");
-    } else {
-        std::vector<float> t32(P);
-        for (size_t i = 0; i < P; ++i) t32[i] = (float)theta[i];
-        if (plat_h2d(H->d_th32, t32.data(), sizeof(float) * P, E.stream) || plat_sync(E.stream)) return fail(std::string(who) + ": H2D copy failed");
-    }
-    // logp and its gradient at theta: one evaluation, the update kernel with a zero kick (gradient only), the energy kernel at zero momentum
-    if (hmc_eval(E, *H)) return 1;
-    hmc_leap(E, *H, true, 0.0, 0.0, 0);
-    hmc::launch_energy(a, 1, hmc_sse(*H), E.stream);
-    plat_d2d(a.g_cur, a.g_prop, sizeof(double) * P, E.stream);
-    plat_d2d(a.sc + hmc::SC_LP_CUR, a.sc + hmc::SC_LP_PROP, sizeof(double), E.stream);
-    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-    hmc_free(E);
-    E.hmc = H.release();
-    return 0;
-}
-
-int pinn_hmc_set_metric(pinn_handle h, const double* inv_metric, int64_t p) {
-    const char* who = "pinn_hmc_set_metric";
-    if (!h) return fail(std::string(who) + ": null argument");
-    pinn_engine& E = *h;
-    if (hmc_ready(E, who) || check_theta(E, who, p)) return 1;
-    HmcState& H = *(HmcState*)E.hmc;
-    std::vector<double> m((size_t)p, 1.0);
-    for (int64_t i = 0; inv_metric && i < p; ++i) {
-        if (!(inv_metric[i] > 0.0) || !std::isfinite(inv_metric[i])) return fail(std::string(who) + ": the inverse metric must be positive and finite");
-        m[(size_t)i] = inv_metric[i];
-    }
-    DeviceScope scope(E.device);
-    if (plat_h2d((double*)H.a.minv, m.data(), sizeof(double) * (size_t)p, E.stream) || plat_sync(E.stream)) return fail(std::string(who) + ": H2D copy failed");
-    return 0;
-}
-
-int pinn_hmc_draws(pinn_handle h, int ndraws, int n_leapfrog, double eps, uint64_t seed, const double* momenta, const double* uniforms,
-                   double* samples, int64_t p, double* accept_prob, double* logp) {
-    const char* who = "pinn_hmc_draws";
-    if (!h || !accept_prob || !logp) return fail(std::string(who) + ": null argument");
-    pinn_engine& E = *h;
-    if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who)) return 1;
-    if (ndraws < 1) return fail(std::string(who) + ": ndraws must be at least 1");
-    if (n_leapfrog < 1) return fail(std::string(who) + ": n_leapfrog must be at least 1");
-    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(std::string(who) + ": the step size eps must be positive and finite");
-    HmcState& H = *(HmcState*)E.hmc;
-    DeviceScope scope(E.device);
-    if (H.f64) H.a.th_eval64 = f64_theta_buffer(E);      // (the mode may have been left and entered again since init)
-    const size_t P = (size_t)p, nd = (size_t)ndraws;
-    if ((samples && !hmc_grow(H.d_samples, H.samples_cap, nd * P, E.stream)) || !hmc_grow(H.d_stat, H.stat_cap, 2 * nd, E.stream) ||
-        (momenta && !hmc_grow(H.d_mom, H.mom_cap, nd * P, E.stream)) || (uniforms && !hmc_grow(H.d_uni, H.uni_cap, nd, E.stream)))
-        return fail(std::string(who) + ": device allocation failed");
-    if ((momenta && plat_h2d(H.d_mom, momenta, sizeof(double) * nd * P, E.stream)) || (uniforms && plat_h2d(H.d_uni, uniforms, sizeof(double) * nd, E.stream)))
-        return fail(std::string(who) + ": H2D copy failed");
-    double* d_acc = H.d_stat;
-    double* d_lp = H.d_stat + nd;
-    for (int d = 0; d < ndraws; ++d) {
-        const unsigned ctr = (unsigned)H.draws;
-        hmc::launch_momentum(H.a, momenta ? H.d_mom + (size_t)d * P : nullptr, seed, ctr, E.stream);
-        hmc::launch_energy(H.a, 0, nullptr, E.stream);
-        hmc_leap(E, H, false, 0.5 * eps, eps, 1);
-        for (int s = 0; s < n_leapfrog; ++s) {
-            if (hmc_eval(E, H)) return 1;                // (the current state only changes in the accept launch: a failed call leaves the chain at its last completed draw)
-            const bool last = s == n_leapfrog - 1;
-            hmc_leap(E, H, true, last ? 0.5 * eps : eps, eps, last ? 0 : 1);
-        }
-        hmc::launch_energy(H.a, 1, hmc_sse(H), E.stream);
-        hmc::launch_accept(H.a, d, uniforms ? H.d_uni : nullptr, seed, ctr, samples ? H.d_samples : nullptr, d_acc, d_lp, E.stream);
-        ++H.draws;
-    }
-    if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * P, E.stream)) || plat_d2h(accept_prob, d_acc, sizeof(double) * nd, E.stream) ||
-        plat_d2h(logp, d_lp, sizeof(double) * nd, E.stream))
-        return fail(std::string(who) + ": D2H copy failed");
-    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-    return 0;
-}
-
-int pinn_hmc_get(pinn_handle h, double* theta, int64_t p, double* logp, double* grad) {
-    const char* who = "pinn_hmc_get";
-    if (!h || !theta) return fail(std::string(who) + ": null argument");
-    pinn_engine& E = *h;
-    if (hmc_ready(E, who) || check_theta(E, who, p)) return 1;
-    HmcState& H = *(HmcState*)E.hmc;
-    DeviceScope scope(E.device);
-    if (plat_d2h(theta, H.a.th_cur, sizeof(double) * (size_t)p, E.stream) || (logp && plat_d2h(logp, H.a.sc + hmc::SC_LP_CUR, sizeof(double), E.stream)) ||
-        (grad && plat_d2h(grad, H.a.g_cur, sizeof(double) * (size_t)p, E.stream)) || plat_sync(E.stream))
-        return fail(std::string(who) + ": D2H copy failed");
-    return 0;
-}
-
-}  // extern "C"
-
-// =================================================================================================
-// Resident L-BFGS (pinn_lbfgs_init / _steps / _get): pinn_lbfgs's iteration with the iterate, the curvature rings and the
-// line search on the device.  A SLOT = one lbfgs::k_lbfgs_step launch (judge the evaluation just finished, propose the next point) + one full
-// resident evaluation (float64 mode: f64_eval_resident; otherwise run_loss_grad at the narrowed copy of the trial point, the K sums in double).
-// Slots are queued in chunks of "lbfgs_chunk"; the host reads the control block after a chunk and nothing else before the call's end.
-// The state has buffers of its own: evaluations, optimiser runs and HMC draws between two calls do not touch it, and it does not touch them.
-// =================================================================================================
-namespace {
-
-struct LbfgsState {
-    bool f64 = false;                    // the precision mode the state was initialised in
-    lbfgs::Args a;
-    lbfgs::Ctl ctl;                      // host mirror of the control block as of the last download
-    std::vector<double> w64;             // the term weights, fixed at init (the curvature pairs belong to one objective)
-    std::vector<float> w32;
-    double* d_state = nullptr;           // [4 P + 2 m P + m]: x | g | xn | d | S | Y | rho
-    lbfgs::Ctl* d_ctl = nullptr;
-    double* d_tab = nullptr;             // [2 K]: weights | n_norm
-    double* d_ev64 = nullptr;            // float64 mode: [P + K] gradient | raw sums of the running evaluation
-    float* d_ev32 = nullptr;             // fp32 mode: [P + K] floats, the K sums again as doubles in d_raw, the narrowed trial point in d_th32
-    double* d_raw = nullptr;
-    float* d_th32 = nullptr;
-    double* d_hist = nullptr;
-    size_t hist_cap = 0;
-};
-
-void lbfgs_release(LbfgsState* H) {
-    if (!H) return;
-    plat_free(H->d_state); plat_free(H->d_ctl); plat_free(H->d_tab); plat_free(H->d_ev64); plat_free(H->d_ev32); plat_free(H->d_raw); plat_free(H->d_th32);
-    plat_free(H->d_hist);
-    delete H;
-}
-
-// what pinn_lbfgs_steps / _get check first; leaves the handle as it is
-int lbfgs_ready(pinn_engine& E, const char* who) {
-    if (!E.lbfgs) return fail(std::string(who) + ": no optimiser state (call pinn_lbfgs_init first)");
-    if (((LbfgsState*)E.lbfgs)->f64 != (E.f64 != nullptr))
-        return fail(std::string(who) + ": the handle's precision changed since pinn_lbfgs_init (call pinn_lbfgs_init again)");
-    return 0;
-}
-int lbfgs_refuse_target(pinn_engine& E, const char* who) {
-    if (E.comm) return fail(std::string(who) + ": the handle belongs to a communicator; the resident L-BFGS loop runs on a single device only");
-    for (auto& T : E.terms)
-        if (T.sampler != 0) return fail(std::string(who) + ": a term redraws its points on the device; L-BFGS needs a fixed objective (fixed point sets)");
-    return 0;
-}
-int lbfgs_eval(pinn_engine& E, LbfgsState& H) {
-    if (H.f64) return f64_eval_resident(E, H.w64.data(), H.d_ev64);
-    return run_loss_grad(E, H.d_th32, H.d_ev32, H.w32.data(), -1, false, H.d_raw);
-}
-void lbfgs_step(pinn_engine& E, LbfgsState& H, int mode, int it0, int it_end, double gtol) {
-    if (H.f64) lbfgs::launch_step<double>(H.a, H.d_ev64, mode, it0, it_end, gtol, E.stream);
-    else lbfgs::launch_step<float>(H.a, H.d_ev32, mode, it0, it_end, gtol, E.stream);
-}
-// (f, g) at x from one evaluation; rings cleared, nothing pending (init, and after the noise-floor switch); downloads the control block
-int lbfgs_adopt(pinn_engine& E, LbfgsState& H) {
-    lbfgs_step(E, H, lbfgs::MODE_LOAD, 0, 0, 0.0);
-    if (lbfgs_eval(E, H)) return 1;
-    lbfgs_step(E, H, lbfgs::MODE_ADOPT, 0, 0, 0.0);
-    if (plat_d2h(&H.ctl, H.d_ctl, sizeof(lbfgs::Ctl), E.stream)) return fail("D2H copy failed");
-    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-    return 0;
-}
-
-}  // namespace
-
-static void lbfgs_free(pinn_engine& E) {
-    lbfgs_release((LbfgsState*)E.lbfgs);
-    E.lbfgs = nullptr;
-    E.lbfgs_history = 0;
-}
-
-extern "C" {
-
-int pinn_lbfgs_init(pinn_handle h, const double* theta, int64_t p, int history, const float* term_w) {
-    const char* who = "pinn_lbfgs_init";
-    if (!h || !theta) return fail(std::string(who) + ": null argument");
-    pinn_engine& E = *h;
-    if (check_theta(E, who, p)) return 1;
-    if (history < 1 || history > lbfgs::MAX_HISTORY) return fail(std::string(who) + ": history must be in 1.." + std::to_string(lbfgs::MAX_HISTORY));
-    if (lbfgs_refuse_target(E, who)) return 1;
-    DeviceScope scope(E.device);
-    if (!E.f64 && ensure_points(E)) return 1;
-    const size_t P = (size_t)p, m = (size_t)history;
-    const int K = (int)E.terms.size();
-    std::unique_ptr<LbfgsState, void (*)(LbfgsState*)> H(new LbfgsState, lbfgs_release);
-    H->f64 = E.f64 != nullptr;
-    const size_t nstate = 4 * P + 2 * m * P + m;
-    H->d_state = (double*)plat_malloc(sizeof(double) * nstate);
-    H->d_ctl = (lbfgs::Ctl*)plat_malloc(sizeof(lbfgs::Ctl));
-    H->d_tab = (double*)plat_malloc(sizeof(double) * (size_t)(2 * K));
-    if (H->f64) H->d_ev64 = (double*)plat_malloc(sizeof(double) * (P + K));
-    else {
-        H->d_ev32 = (float*)plat_malloc(sizeof(float) * (P + K));
-        H->d_raw = (double*)plat_malloc(sizeof(double) * (size_t)K);
-        H->d_th32 = (float*)plat_malloc(sizeof(float) * P);
-    }
-    if (!H->d_state || !H->d_ctl || !H->d_tab || (H->f64 ? !H->d_ev64 : (!H->d_ev32 || !H->d_raw || !H->d_th32))) return fail(std::string(who) + ": device allocation failed");
-    lbfgs::Args& a = H->a;
-    std::memset(&a, 0, sizeof a);
-    a.P = (int)p; a.K = K; a.m = history; a.f64form = H->f64 ? 1 : 0;
-    a.x = H->d_state; a.g = a.x + P; a.xn = a.g + P; a.d = a.xn + P; a.S = a.d + P; a.Y = a.S + m * P; a.rho = a.Y + m * P;
-    a.ctl = H->d_ctl;
-    a.w = H->d_tab; a.nrm = H->d_tab + K;
-    a.sums = H->f64 ? H->d_ev64 + P : H->d_raw;
-    a.th_eval64 = H->f64 ? f64_theta_buffer(E) : nullptr;
-    a.th_eval32 = H->f64 ? nullptr : H->d_th32;
-    H->w64.resize(K); H->w32.resize(K);
-    std::vector<double> tb((size_t)(2 * K));
-    for (int k = 0; k < K; ++k) {
-        H->w32[k] = term_w ? term_w[k] : 1.0f;
-        H->w64[k] = (double)H->w32[k];
-        tb[k] = H->w64[k];
-        tb[K + k] = (double)E.terms[k].n_norm;
-    }
-    std::memset(&H->ctl, 0, sizeof H->ctl);
-    plat_memset(H->d_state, 0, sizeof(double) * nstate, E.stream);
-    if (plat_h2d(a.x, theta, sizeof(double) * P, E.stream) || plat_h2d(H->d_tab, tb.data(), sizeof(double) * tb.size(), E.stream) ||
-        plat_h2d(H->d_ctl, &H->ctl, sizeof(lbfgs::Ctl), E.stream) || plat_sync(E.stream))
-        return fail(std::string(who) + ": H2D copy failed");
-    if (lbfgs_adopt(E, *H)) return 1;
-    lbfgs_free(E);
-    E.lbfgs = H.release();
-    E.lbfgs_history = history;
-    return 0;
-}
-
-int pinn_lbfgs_steps(pinn_handle h, int maxiters, int max_evals, double gtol, double* loss_history, int* iters_done, int* evals_done, int* status) {
-    const char* who = "pinn_lbfgs_steps";
-    if (!h) return fail(std::string(who) + ": null argument");
-    pinn_engine& E = *h;
-    if (lbfgs_ready(E, who) || lbfgs_refuse_target(E, who)) return 1;
-    if (maxiters < 1) return fail(std::string(who) + ": maxiters must be at least 1");
-    if (max_evals < 1) return fail(std::string(who) + ": max_evals must be at least 1");
-    LbfgsState& H = *(LbfgsState*)E.lbfgs;
-    DeviceScope scope(E.device);
-    if (H.f64) H.a.th_eval64 = f64_theta_buffer(E);      // (the mode may have been left and entered again since init)
-    if (H.hist_cap < (size_t)maxiters) {
-        plat_sync(E.stream);
-        plat_free(H.d_hist);
-        H.d_hist = (double*)plat_malloc(sizeof(double) * (size_t)maxiters);
-        H.hist_cap = H.d_hist ? (size_t)maxiters : 0;
-        if (!H.d_hist) return fail(std::string(who) + ": device allocation failed");
-    }
-    H.a.loss_hist = H.d_hist;
-    if (H.ctl.status >= lbfgs::ST_CONVERGED) {           // a terminal state ends a call, not the optimisation: the next call tests again
-        H.ctl.status = lbfgs::ST_RUN;
-        if (plat_h2d(H.d_ctl, &H.ctl, sizeof(lbfgs::Ctl), E.stream) || plat_sync(E.stream)) return fail(std::string(who) + ": H2D copy failed");
-    }
-    const int it0 = H.ctl.it, it_end = it0 + maxiters, ev0 = H.ctl.evals;
-    GemmFloorSwitch floor_switch(E);
-    for (;;) {
-        const int left = max_evals - (H.ctl.evals - ev0);
-        if (left <= 0) break;
-        const int n = std::min(E.lbfgs_chunk, left);     // (a slot proposes at most one trial point)
-        for (int s = 0; s < n; ++s) {
-            lbfgs_step(E, H, lbfgs::MODE_SLOT, it0, it_end, gtol);
-            if (lbfgs_eval(E, H)) return 1;
-        }
-        if (plat_d2h(&H.ctl, H.d_ctl, sizeof(lbfgs::Ctl), E.stream)) return fail(std::string(who) + ": D2H copy failed");
-        if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-        if (H.ctl.status < lbfgs::ST_CONVERGED) continue;
-        if (H.ctl.status == lbfgs::ST_STALLED && floor_switch.eligible()) {
-            const int sw = floor_switch.engage();
-            if (sw == 1) return 1;
-            if (sw == 0 && floor_switch.switched) {      // go on from the same iterate; curvature pairs carry the other arithmetic's gradient noise
-                if (lbfgs_adopt(E, H)) return 1;
-                continue;
-            }
-        }
-        break;
-    }
-    const int done = H.ctl.it - it0;
-    if (loss_history) {
-        if (done > 0 && (plat_d2h(loss_history, H.d_hist, sizeof(double) * (size_t)done, E.stream) || plat_sync(E.stream))) return fail(std::string(who) + ": D2H copy failed");
-        for (int i = done; i < maxiters; ++i) loss_history[i] = H.ctl.f;
-    }
-    if (iters_done) *iters_done = done;
-    if (evals_done) *evals_done = H.ctl.evals - ev0;
-    if (status) *status = H.ctl.status;
-    return floor_switch.finish();
-}
-
-int pinn_lbfgs_get(pinn_handle h, double* theta, int64_t p, double* f, double* grad) {
-    const char* who = "pinn_lbfgs_get";
-    if (!h || !theta) return fail(std::string(who) + ": null argument");
-    pinn_engine& E = *h;
-    if (lbfgs_ready(E, who) || check_theta(E, who, p)) return 1;
-    LbfgsState& H = *(LbfgsState*)E.lbfgs;
-    DeviceScope scope(E.device);
-    if (plat_d2h(theta, H.a.x, sizeof(double) * (size_t)p, E.stream) || (grad && plat_d2h(grad, H.a.g, sizeof(double) * (size_t)p, E.stream)) || plat_sync(E.stream))
-        return fail(std::string(who) + ": D2H copy failed");
-    if (f) *f = H.ctl.f;
-    return 0;
-}
-
-}  // extern "C"
-
-// =================================================================================================
-// Ensemble prediction (pinn_phi_ensemble): phi of one network at S parameter vectors and n points + the mean / standard
-// deviation over the S predictions (ens_kernels.hpp).  One upload of the parameter vectors, one of the points, the launches back to back on
-// the handle's stream, one download.  The buffers belong to this entry point and grow on demand; nothing else of the handle is touched.
-// =================================================================================================
-namespace {
-
-struct EnsState {
-    void* d_th = nullptr; void* d_pts = nullptr;         // [S][P] | [n][d] in the compute type
-    void* d_preds = nullptr; void* d_stat = nullptr;     // doubles: [S][points of one pass] | [mean n | std n]
-    size_t th_cap = 0, pts_cap = 0, preds_cap = 0, stat_cap = 0;      // bytes
-};
-
-bool ens_grow(void*& p, size_t& cap, size_t need, plat_stream st) {
-    if (cap >= need) return true;
-    plat_sync(st);
-    plat_free(p);
-    p = plat_malloc(need);
-    cap = p ? need : 0;
-    return p != nullptr;
-}
-
-// points per pass: all of them unless the predictions [S][n] exceed the budget ($PINN_ENS_GB, default 4) — then the largest multiple of the
-// point block within it.  $PINN_ENS_CHUNK (points, rounded up to whole blocks) overrides the budget: the tests force several passes with it.
-// Both are read per call.  Points are independent and the statistics never split over samples, so the passes change no bit.
-int64_t ens_chunk_points(int64_t n, int64_t S, int ppb) {
-    double gb = 4.0;
-    if (const char* e = std::getenv("PINN_ENS_GB")) { const double v = std::atof(e); if (v > 0.0) gb = v; }
-    int64_t c = (int64_t)(gb * 1073741824.0 / (8.0 * (double)S));
-    if (const char* e = std::getenv("PINN_ENS_CHUNK")) { const long long v = std::atoll(e); if (v > 0) c = (int64_t)v; }
-    c = std::min(c, (int64_t)(1 << 30) / S * ppb);       // (the launch's workgroup count S x blocks stays below 2^30
-    c = std::min(c, (int64_t)(1 << 30));                 //  and the points of one pass, an int in the kernels, too; 2^30 is a multiple of ppb)
-    c = std::max<int64_t>((c + ppb - 1) / ppb, 1) * ppb;
-    return std::min(c, n);
-}
-
-template <class T> int ens_run(const char* who, pinn_engine& E, EnsState& X, const ens::Net& net, int ppb, const double* thetas, int64_t S, const double* pts, int64_t n,
-                               int ddof, double* mean, double* sd, double* preds) {
-    const size_t P = (size_t)E.ntheta, d = (size_t)net.sizes[0], ns = (size_t)n;
-    const int64_t chunk = ens_chunk_points(n, S, ppb);
-    if (!ens_grow(X.d_th, X.th_cap, sizeof(T) * (size_t)S * P, E.stream) || !ens_grow(X.d_pts, X.pts_cap, sizeof(T) * ns * d, E.stream) ||
-        !ens_grow(X.d_preds, X.preds_cap, sizeof(double) * (size_t)S * (size_t)chunk, E.stream) || !ens_grow(X.d_stat, X.stat_cap, sizeof(double) * 2 * ns, E.stream))
-        return fail(std::string(who) + ": device allocation failed");
-    double* d_preds = (double*)X.d_preds;
-    double* d_stat = (double*)X.d_stat;
-    auto th = as<T>(thetas, (size_t)S * P); auto x = as<T>(pts, ns * d);          // (float)theta, (float)x on an fp32 handle
-    if (plat_h2d(X.d_th, th.get(), sizeof(T) * (size_t)S * P, E.stream) || plat_h2d(X.d_pts, x.get(), sizeof(T) * ns * d, E.stream))
-        return fail(std::string(who) + ": H2D copy failed");
-    for (int64_t p0 = 0; p0 < n; p0 += chunk) {
-        const int nc = (int)std::min(chunk, n - p0);
-        if (ens::launch_forward<T>(net, (const T*)X.d_th, (int)S, P, (const T*)X.d_pts + (size_t)p0 * d, nc, d_preds, (size_t)nc, ppb, E.stream) ||
-            ens::launch_stats(d_preds, (size_t)nc, (int)S, ddof, nc, d_stat + p0, d_stat + ns + p0, E.stream))
-            return fail(std::string(who) + ": kernel launch failed (" + plat_last_error() + ")");
-        for (int64_t s = 0; preds && s < (nc == n ? 1 : S); ++s)                  // (one pass: [S][n] is one contiguous block)
-            if (plat_d2h(preds + (size_t)s * ns + p0, d_preds + (size_t)s * nc, sizeof(double) * (size_t)(nc == n ? S * n : nc), E.stream))
-                return fail(std::string(who) + ": D2H copy failed");
-    }
-    std::vector<double> st(2 * ns);
-    if (plat_d2h(st.data(), d_stat, sizeof(double) * 2 * ns, E.stream)) return fail(std::string(who) + ": D2H copy failed");
-    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-    std::copy(st.begin(), st.begin() + ns, mean);
-    std::copy(st.begin() + ns, st.end(), sd);
-    return 0;
-}
-
-}  // namespace
-
-static void ens_free(pinn_engine& E) {
-    if (EnsState* X = (EnsState*)E.ens) {
-        plat_free(X->d_th); plat_free(X->d_pts); plat_free(X->d_preds); plat_free(X->d_stat);
-        delete X;
-    }
-    E.ens = nullptr;
-}
-
-extern "C" {
-
-int pinn_phi_ensemble(pinn_handle h, int net, const double* thetas, int64_t nsamples, int64_t p, const double* pts, int64_t n, int ddof,
-                      double* mean, double* std_, double* preds) {
-    const char* who = "pinn_phi_ensemble";
-    if (!h || !thetas || !pts || !mean || !std_) return fail(std::string(who) + ": null argument");
-    pinn_engine& E = *h;
-    if (net < 0 || net >= (int)E.nets.size()) return fail(std::string(who) + ": net index " + std::to_string(net) + " out of range (the handle has " + std::to_string(E.nets.size()) + " networks)");
-    if (check_theta(E, who, p)) return 1;
-    if (nsamples < 1) return fail(std::string(who) + ": nsamples must be at least 1");
-    if (nsamples > (int64_t)(1 << 30)) return fail(std::string(who) + ": nsamples must be at most 2^30");
-    if (ddof != 0 && ddof != 1) return fail(std::string(who) + ": ddof must be 0 or 1");
-    if (nsamples - ddof < 1) return fail(std::string(who) + ": nsamples - ddof must be at least 1 (" + std::to_string(nsamples) + " samples, ddof " + std::to_string(ddof) + ")");
-    if (n < 1) return fail(std::string(who) + ": n must be at least 1");
-    const Net& N = E.nets[net];
-    if (N.kind == 1) return fail(std::string(who) + ": not available for a DGM network (Dense chains only)");
-    if (!N.emb_idx.empty()) return fail(std::string(who) + ": not available for a network behind a periodic input embedding");
-    const int nl = (int)N.sizes.size() - 1;
-    if (nl > ens::MAX_LAYERS) return fail(std::string(who) + ": more than " + std::to_string(ens::MAX_LAYERS) + " Dense layers");
-    ens::Net en;
-    std::memset(&en, 0, sizeof en);
-    en.nl = nl; en.act = N.act; en.act_layers = N.act_layers; en.theta0 = N.theta_off;
-    for (int l = 0; l <= nl; ++l) { en.sizes[l] = N.sizes[l]; en.wmax = std::max(en.wmax, N.sizes[l]); }
-    const size_t elem = E.f64 ? sizeof(double) : sizeof(float);
-    const int ppb = ens::pick_ppb(en, elem);
-    if (ppb == 0)
-        return fail(std::string(who) + ": the widest layer (" + std::to_string(en.wmax) + " neurons) needs " + std::to_string(ens::lds_bytes(en, ens::MIN_PPB, elem)) +
-                    " bytes of LDS for two images of " + std::to_string(ens::MIN_PPB) + " points; the limit is " + std::to_string(ens::LDS_MAX));
-    DeviceScope scope(E.device);
-    if (!E.ens) E.ens = new EnsState;
-    EnsState& X = *(EnsState*)E.ens;
-    return E.f64 ? ens_run<double>(who, E, X, en, ppb, thetas, nsamples, pts, n, ddof, mean, std_, preds)
-                 : ens_run<float>(who, E, X, en, ppb, thetas, nsamples, pts, n, ddof, mean, std_, preds);
-}
 
 }  // extern "C"
 

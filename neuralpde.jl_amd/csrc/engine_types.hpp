@@ -1,5 +1,6 @@
 // engine_types.hpp — data model of the host side of the C ABI, shared by descriptor.cpp (parsing), program.cpp (residual-program
-// passes), plan.cpp (kernel selection, buffers, reduction maps) and engine.cpp (evaluation + the extern "C" entry points).
+// passes), plan.cpp (kernel selection, buffers, reduction maps), engine.cpp (evaluation + the extern "C" entry points) and the resident
+// solvers' units (hmc.cpp, lbfgs.cpp, ensemble.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -9,6 +10,7 @@
 #include <memory>
 #include <sstream>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pinn_hip.h"
@@ -224,6 +226,9 @@ struct NetPlan {
     std::vector<int> h_pack_idx;     // host copy (inverse map construction)
     int npacked = 0;
 };
+struct HmcState;                     // hmc.cpp
+struct LbfgsState;                   // lbfgs.cpp
+struct EnsState;                     // ensemble.cpp
 
 }  // namespace pe
 
@@ -285,7 +290,7 @@ struct pinn_engine {
     float* d_opt_out = nullptr;      // [P + K]
     float* d_w_over_n = nullptr;     // [K]
     double* d_hist = nullptr;
-    int hist_cap = 0;
+    size_t hist_cap = 0;
     long long opt_t = 0;
     // device-side step state of the resident loop (pinn_adam_steps): [0] = step index of the current call; draw counters and the
     // sampled-term mask per term; bias-correction table [2 x steps]
@@ -296,7 +301,7 @@ struct pinn_engine {
     unsigned* d_draws = nullptr;
     int* d_sampled = nullptr;
     float* d_c12 = nullptr;
-    int c12_cap = 0;
+    size_t c12_cap = 0;              // floats
     unsigned* d_bar = nullptr;       // grid-barrier words of the persistent training kernel (pinn_train.hpp)
     unsigned* h_flag = nullptr;      // host-mapped: a launch's barrier timed out
     unsigned bar_arrivals = 0;       // arrivals the barrier counter has seen so far (it is never reset between launches)
@@ -304,7 +309,7 @@ struct pinn_engine {
     int* d_own_r = nullptr;          // its thread -> element map (pinn_train.hpp: TrainArgs::own_r), built for own_blocks workgroups
     int own_blocks = 0, hist_gid = 0;
     void* d_train_samp = nullptr;    // its table of redrawn terms (pk::TrainSampler[train_samp_cap])
-    int train_samp_cap = 0;
+    size_t train_samp_cap = 0;       // bytes
     float* d_opt_bak = nullptr;      // [3 P] snapshot of (theta, m, v) at the start of a persistent launch (restored when its barrier times out)
     int max_contrib = 0, max_inv_pos = 0;      // most slab entries / image positions of one theta element (plan.cpp)
     bool persistent = true;          // pinn_set_option "persistent": small problems run pinn_adam_steps inside one launch
@@ -320,11 +325,11 @@ struct pinn_engine {
     size_t phi_scr_cap = 0;
     int64_t phi_cap = 0;
     int phi_chan = 0;                // jet channels d_phi_out holds per point
-    void* hmc = nullptr;             // resident HMC sampler state (engine.cpp: HmcState; pinn_hmc_init), nullptr = none
-    void* lbfgs = nullptr;           // resident L-BFGS state (engine.cpp: LbfgsState; pinn_lbfgs_init), nullptr = none
+    pe::HmcState* hmc = nullptr;     // resident HMC sampler state (hmc.cpp; pinn_hmc_init), nullptr = none
+    pe::LbfgsState* lbfgs = nullptr; // resident L-BFGS state (lbfgs.cpp; pinn_lbfgs_init), nullptr = none
     int lbfgs_history = 0;           // its history length (pinn_describe)
     int lbfgs_chunk = 8;             // option "lbfgs_chunk": slots pinn_lbfgs_steps queues between two downloads of the control block, 1..64
-    void* ens = nullptr;             // buffers of pinn_phi_ensemble (engine.cpp: EnsState), nullptr = none yet
+    pe::EnsState* ens = nullptr;     // buffers of pinn_phi_ensemble (ensemble.cpp), nullptr = none yet
 };
 
 namespace pe {
@@ -347,6 +352,44 @@ int run_loss_grad(pinn_engine& E, const float* d_theta, float* d_out, const floa
                   bool packed_fresh = false, bool loss_only = false, float* d_sums = nullptr);
 int upload_theta(pinn_engine& E, const float* theta, int64_t p);
 void sums_from_double(float* d_out_sums, const double* d_raw, int K, plat_stream st);      // (float)raw[k] -> out_sums[k], on the stream
+int ensure_points(pinn_engine& E);              // every term has its point set (and per-point data) installed, or the reason in g_err
+// loss + gradient for a host entry point that synchronises right after: small problems in ONE launch (eval_fused), everything else by
+// run_loss_grad; results in d_out / lossraw either way.  Synchronises.
+int eval_and_sync(pinn_engine& E, float* d_out, const float* term_w, double* lossraw, bool timing);
+// switch the GEMM arithmetic of a live handle: the kernel plan is rebuilt for the other mode (packed weight images, gradient-slab maps and
+// reduction tables differ), the installed point sets, samplers, per-point data / weights and the optimiser state stay
+int replan_gemm(pinn_engine& E, int mode);
+inline int check_theta(const pinn_engine& E, const char* who, int64_t p) {
+    return p == E.ntheta ? 0 : fail(std::string(who) + ": theta length " + std::to_string(p) + " != ntheta " + std::to_string(E.ntheta));
+}
+// one caller array of n elements of type T, seen as element type V at the precision boundary of a float / double entry point: the caller's
+// own array when T is V; otherwise a converted copy — of the caller's values for an input (T const), or one that put() converts back into
+// the caller's array for an output.  A null array stays null.
+template <class V, class T> class As {
+    static constexpr bool same = std::is_same_v<V, std::remove_const_t<T>>;
+    T* x_;
+    std::vector<V> copy_;
+public:
+    As(T* x, size_t n) : x_(x) {
+        if constexpr (!same) {
+            if (x && std::is_const_v<T>) copy_.assign(x, x + n);      // an input: the caller's values, converted
+            else if (x) copy_.resize(n);                               // an output: written by the evaluation, converted back by put()
+        }
+    }
+    auto get() {
+        if constexpr (same) return x_;
+        else return x_ ? copy_.data() : nullptr;
+    }
+    int put() {                                          // (outputs; returns 0)
+        if constexpr (!same) if (x_) std::copy(copy_.begin(), copy_.end(), x_);
+        return 0;
+    }
+};
+template <class V, class T> As<V, T> as(T* x, size_t n) { return As<V, T>(x, n); }
+// hmc.cpp, lbfgs.cpp, ensemble.cpp: release the handle's resident solver state / ensemble buffers (nothing to do when there is none)
+void hmc_free(pinn_engine& E);
+void lbfgs_free(pinn_engine& E);
+void ens_free(pinn_engine& E);
 // comm.cpp: sum vec[i] ([P + K] floats) and raw[i] (K doubles) of the ndev handles' ranks over their communicator, in place, each on its
 // handle's stream.  ndev == 1: a one-process-per-GPU communicator (RCCL or the caller's transport; no communicator: nothing to do);
 // ndev > 1: the handles of one pinn_comm_init_all communicator, one grouped RCCL call

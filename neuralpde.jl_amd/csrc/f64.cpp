@@ -7,7 +7,7 @@
 // Scope: Dense chains with tanh / sigmoid / sin, equations of one or SEVERAL dependent variables (systems: up to 6 networks per equation, all
 // with the same number of inputs), derivative orders <= 2 in 1-3 inputs (1-D: <= 4; 4-D: first and pure second derivatives), PDE parameters
 // (param_estim), quadrature weights, per-point DATA channels, device samplers, periodic input embeddings (r06: feature rows in double); no DGM networks.  Anything else fails at pinn_set_option with a message — the fp32 plan of the handle stays usable.
-#include "engine_types.hpp"
+#include "resident.hpp"
 #include "pinn_kernels6.hpp"
 
 namespace pk {
@@ -78,11 +78,11 @@ struct F64State {
     double* d_v = nullptr;
     double* d_w_over_n = nullptr;        // [K] w_k / N_k of the running call
     double* d_hist = nullptr;
-    int hist_cap = 0;
+    size_t hist_cap = 0;
     bool opt_ready = false;              // d_opt_theta holds the optimiser's parameters
     double* d_aux_pts = nullptr;         // caller-supplied points of pinn_phi_f64 / pinn_derivative_f64 [n][d]
     double* d_aux_out = nullptr;         // per-point outputs (residuals, trial-function values / derivatives) [n]
-    int64_t aux_pts_cap = 0, aux_out_cap = 0;
+    size_t aux_pts_cap = 0, aux_out_cap = 0;
     int path = 0;                        // kernels of the last evaluation: bit 0 one lane per point (family 4), bit 1 matrix pipe (family 4m)
     // MERGED launches of small problems (r06, f64_make_groups): terms that share networks, input binding and an instantiated jet set in ONE tile / dW /
     // reduction launch sequence; rebuilt when a term's point count changes
@@ -493,14 +493,6 @@ static int f64_build(pinn_engine& E, const F64Term& F, int dt, const std::map<in
     }
     return 0;
 }
-static bool grow(double*& buf, size_t& cap, size_t need, plat_stream st) {
-    if (need <= cap) return true;
-    plat_sync(st);
-    plat_free(buf);
-    buf = (double*)plat_malloc(sizeof(double) * need);
-    cap = buf ? need : 0;
-    return buf != nullptr;
-}
 // points per launch and the buffers of one: scratch rows (below 256 MB with one lane per point / 4 GB with the matrix-pipe kernels — one wave per
 // 16-32 points there, a chunk should hold several tiles per SIMD: the bench workload's 65,536-point terms are one chunk each; $PINN_F64_SCRATCH_MB
 // overrides), per-block slabs, per-tile partial sums.  An allocation that fails is retried with half the chunk down to one block.
@@ -516,9 +508,9 @@ static int f64_buffers(pinn_engine& E, F64State& S, F64Launch& L, int64_t n, boo
         chunk = std::min<int64_t>(chunk, ((n + pk::F64_BLOCK - 1) / pk::F64_BLOCK) * pk::F64_BLOCK);
         const bool last_try = chunk <= pk::F64_BLOCK;
         bool ok = true;
-        if (need_scratch) ok = grow(S.d_scratch, S.scratch_cap, (size_t)L.rows * (size_t)chunk + pk::F64S_PAD_SCRATCH, E.stream);
-        if (ok && with_sums) ok = grow(S.d_slab, S.slab_cap, (size_t)(chunk / pk::F64_BLOCK) * (size_t)a.nent, E.stream);
-        if (ok && with_sums && L.mfma) ok = grow(S.d_tpart, S.tpart_cap, (size_t)(chunk / a.tile_pts + 1) * (size_t)a.ntp, E.stream);
+        if (need_scratch) ok = dev_grow(S.d_scratch, S.scratch_cap, (size_t)L.rows * (size_t)chunk + pk::F64S_PAD_SCRATCH, E.stream);
+        if (ok && with_sums) ok = dev_grow(S.d_slab, S.slab_cap, (size_t)(chunk / pk::F64_BLOCK) * (size_t)a.nent, E.stream);
+        if (ok && with_sums && L.mfma) ok = dev_grow(S.d_tpart, S.tpart_cap, (size_t)(chunk / a.tile_pts + 1) * (size_t)a.ntp, E.stream);
         if (ok) {
             a.scratch = S.d_scratch; a.npad = (int)chunk; a.slab = S.d_slab; a.tpart = S.d_tpart;
             chunk_out = chunk;
@@ -545,7 +537,7 @@ static int f64_short_blocks(pinn_engine& E, F64State& S, F64Launch& L) {
     while (bp > F64_SMALL_BLOCK && (int64_t)((a.npts + bp - 1) / bp) * rows < target) bp >>= 1;
     if (bp == pk::F64_BLOCK) return full;
     const int nb = (a.npts + bp - 1) / bp;
-    if (!grow(S.d_slab, S.slab_cap, (size_t)nb * (size_t)a.nent, E.stream)) return full;
+    if (!dev_grow(S.d_slab, S.slab_cap, (size_t)nb * (size_t)a.nent, E.stream)) return full;
     a.slab = S.d_slab;
     a.block_pts = bp;
     return nb;
@@ -705,8 +697,8 @@ static int f64_stencil_term(pinn_engine& E, int t, const double* theta, double* 
     const int nv = (int)X.vnets.size(), stride = 2 + E.ne;
     int dmax = 1;
     for (auto& vn : X.vnets) dmax = std::max(dmax, E.nets[vn.net].sizes[0]);
-    if (!grow(S.d_uv, S.uv_cap, (size_t)nv * n, E.stream) || !grow(S.d_seeds, S.seeds_cap, (size_t)nv * n * stride, E.stream) ||
-        !grow(S.d_spts, S.spts_cap, (size_t)nv * n * dmax, E.stream)) return fail("device allocation failed (stencil evaluation)");
+    if (!dev_grow(S.d_uv, S.uv_cap, (size_t)nv * n, E.stream) || !dev_grow(S.d_seeds, S.seeds_cap, (size_t)nv * n * stride, E.stream) ||
+        !dev_grow(S.d_spts, S.spts_cap, (size_t)nv * n * dmax, E.stream)) return fail("device allocation failed (stencil evaluation)");
     // 1. shifted sets and the virtual networks' values
     for (int v = 0; v < nv; ++v) {
         const F64VNet& vn = X.vnets[v];
@@ -1063,9 +1055,7 @@ int f64_residual(pinn_engine& E, int term, const double* theta, double* r) {
     if (F.n <= 0 || F.n != E.terms[term].n) return fail("pinn_residual: term has no points");
     if (F.ndata > 0 && F.data_n != F.n) return fail("pinn_residual: the term uses per-point data channels but none are installed for its current point set");
     if (plat_h2d(S.d_theta, theta, sizeof(double) * E.ntheta, E.stream)) return fail("H2D copy of theta failed");
-    size_t cap = (size_t)S.aux_out_cap;
-    if (!grow(S.d_aux_out, cap, (size_t)F.n, E.stream)) { S.aux_out_cap = 0; return fail("device allocation failed (float64 residuals)"); }
-    S.aux_out_cap = (int64_t)cap;
+    if (!dev_grow(S.d_aux_out, S.aux_out_cap, (size_t)F.n, E.stream)) return fail("device allocation failed (float64 residuals)");
     S.path = 0;
     S.max_chunks = 0;
     if (S.stencil && S.sten[term].active) {
@@ -1110,9 +1100,7 @@ int f64_net_eval(pinn_engine& E, int net, const double* theta, const double* pts
     F.slot_net = {0};
     F.nops = 0; F.nslots = 1; F.out_row = d + E.np;
     F.n = n;
-    size_t cp = (size_t)S.aux_pts_cap, co = (size_t)S.aux_out_cap;
-    const bool okp = grow(S.d_aux_pts, cp, (size_t)n * d, E.stream), oko = grow(S.d_aux_out, co, (size_t)n, E.stream);
-    S.aux_pts_cap = (int64_t)cp; S.aux_out_cap = (int64_t)co;
+    const bool okp = dev_grow(S.d_aux_pts, S.aux_pts_cap, (size_t)n * d, E.stream), oko = dev_grow(S.d_aux_out, S.aux_out_cap, (size_t)n, E.stream);
     if (!okp || !oko) return fail("device allocation failed (float64 trial-function points)");
     F.d_pts = S.d_aux_pts;
     if (plat_h2d(S.d_theta, theta, sizeof(double) * E.ntheta, E.stream) || plat_h2d(S.d_aux_pts, pts, sizeof(double) * (size_t)n * d, E.stream)) {
@@ -1212,13 +1200,7 @@ int f64_adam_steps_comm(pinn_engine** es, int ndev, int nsteps, double lr, doubl
         F64State& S = *(F64State*)E.f64;
         if (!S.opt_ready) return fail("pinn_adam_steps: call pinn_adam_init first (float64 mode keeps its own optimiser state)");
         plat_h2d(S.d_w_over_n, won.data(), sizeof(double) * K, E.stream);
-        if (S.hist_cap < nsteps) {
-            plat_sync(E.stream);
-            plat_free(S.d_hist);
-            S.d_hist = (double*)plat_malloc(sizeof(double) * nsteps);
-            S.hist_cap = S.d_hist ? nsteps : 0;
-            if (!S.d_hist) return fail("device allocation failed (loss history)");
-        }
+        if (!dev_grow(S.d_hist, S.hist_cap, (size_t)nsteps, E.stream)) return fail("device allocation failed (loss history)");
         vec[i] = S.d_grad;
     }
     const bool collective = ndev > 1 || es[0]->comm != nullptr;
@@ -1300,7 +1282,7 @@ int f64_eval_from_device_f64(pinn_engine& E, const double* d_theta, const float*
     return f64_eval_device(E, d_theta, d_out, d_out + P, w.data());
 }
 
-// the resident HMC loop (engine.cpp: pinn_hmc_*) in float64 mode: its update kernel writes the proposal into the evaluation's own parameter buffer
+// the resident HMC loop (hmc.cpp: pinn_hmc_*) in float64 mode: its update kernel writes the proposal into the evaluation's own parameter buffer
 // (padded as the matrix-pipe kernels need) and every leapfrog step evaluates there, [gradient | raw sums] into the sampler's own vector (P + K doubles)
 double* f64_theta_buffer(pinn_engine& E) { return ((F64State*)E.f64)->d_theta; }
 int f64_eval_resident(pinn_engine& E, const double* term_w, double* d_out) {

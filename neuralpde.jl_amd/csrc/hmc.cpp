@@ -1,0 +1,205 @@
+// hmc.cpp — resident HMC (pinn_hmc_init / _set_metric / _draws / _get): the transition loop of
+// neuralpde.jl_amd/bpinn.py `_hmc` with the chain on the device.
+// A leapfrog step = the handle's resident evaluation (resident.hpp: ResidentEval) + ONE update launch (hmc_kernels.hpp); nothing is read back
+// before the single download that ends pinn_hmc_draws.
+// The state has buffers of its own: evaluations and optimiser runs between two calls do not touch the chain, and the chain does not touch them.
+#include "resident.hpp"
+#include "hmc_kernels.hpp"
+
+using namespace pe;
+
+struct pe::HmcState {
+    hmc::Args a;
+    ResidentEval ev;                     // term weights N_k / (2 s_k^2), as pinn_loglik_grad forms them
+    double* d_state = nullptr;           // [6 P + SC_COUNT]: th_cur | th_prop | r | g_cur | g_prop | minv | scalars
+    double* d_tab = nullptr;             // [3 n_prior + 3 K]: prior mu | prior sigma | lik_c | lik_d | lik_n (+ kinds as ints in d_kind)
+    int* d_kind = nullptr;
+    double* d_samples = nullptr; double* d_stat = nullptr; double* d_mom = nullptr; double* d_uni = nullptr;
+    size_t samples_cap = 0, stat_cap = 0, mom_cap = 0, uni_cap = 0;
+    unsigned long long draws = 0;        // draw counter of the generator (advanced per completed draw, whatever supplies momenta and uniforms)
+};
+
+namespace {
+
+void hmc_release(HmcState* H) {
+    if (!H) return;
+    H->ev.release();
+    plat_free(H->d_state); plat_free(H->d_tab); plat_free(H->d_kind);
+    plat_free(H->d_samples); plat_free(H->d_stat); plat_free(H->d_mom); plat_free(H->d_uni);
+    delete H;
+}
+
+// what every pinn_hmc_* call after init checks first; leaves the handle as it is
+int hmc_ready(pinn_engine& E, const char* who) {
+    if (!E.hmc) return fail(std::string(who) + ": no sampler state (call pinn_hmc_init first)");
+    return E.hmc->ev.ready(E, who, "pinn_hmc_init");
+}
+int hmc_refuse_target(pinn_engine& E, const char* who) {
+    return resident_refuse_target(E, who, "the resident sampler runs single-device chains only", "HMC needs a fixed target");
+}
+// the update launch after an evaluation at the proposal (from_eval), or the opening half kick
+void hmc_leap(pinn_engine& E, HmcState& H, bool from_eval, double kick, double eps, int drift) {
+    if (H.ev.f64) hmc::launch_leap<double>(H.a, from_eval ? H.ev.out<double>() : nullptr, kick, eps, drift, E.stream);
+    else hmc::launch_leap<float>(H.a, from_eval ? H.ev.out<float>() : nullptr, kick, eps, drift, E.stream);
+}
+
+}  // namespace
+
+void pe::hmc_free(pinn_engine& E) {
+    hmc_release(E.hmc);
+    E.hmc = nullptr;
+}
+
+extern "C" {
+
+int pinn_hmc_init(pinn_handle h, const double* theta, int64_t p, const double* stds, int k, double nn_mu, double nn_sigma,
+                  int n_prior, const int* prior_kind, const double* prior_mu, const double* prior_sigma) {
+    const char* who = "pinn_hmc_init";
+    if (!h || !theta || !stds) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (check_theta(E, who, p)) return 1;
+    const int K = (int)E.terms.size();
+    if (k != K) return fail(std::string(who) + ": " + std::to_string(k) + " standard deviations for " + std::to_string(K) + " loss terms");
+    for (int j = 0; j < K; ++j)
+        if (!(stds[j] > 0.0) || !std::isfinite(stds[j])) return fail(std::string(who) + ": standard deviations must be positive");
+    if (!(nn_sigma > 0.0) || !std::isfinite(nn_sigma) || !std::isfinite(nn_mu)) return fail(std::string(who) + ": the weight prior needs a finite mean and a positive standard deviation");
+    if (n_prior < 0 || n_prior > p) return fail(std::string(who) + ": n_prior must be in 0..P");
+    if (n_prior > 0 && (!prior_kind || !prior_mu || !prior_sigma)) return fail(std::string(who) + ": null prior table");
+    for (int j = 0; j < n_prior; ++j) {
+        if (prior_kind[j] != hmc::PRIOR_NORMAL && prior_kind[j] != hmc::PRIOR_LOGNORMAL) return fail(std::string(who) + ": prior kind must be 0 (Normal) or 1 (LogNormal)");
+        if (!(prior_sigma[j] > 0.0) || !std::isfinite(prior_sigma[j]) || !std::isfinite(prior_mu[j])) return fail(std::string(who) + ": a parameter prior needs a finite mu and a positive sigma");
+    }
+    if (hmc_refuse_target(E, who)) return 1;
+    DeviceScope scope(E.device);
+    if (!E.f64 && ensure_points(E)) return 1;
+    const size_t P = (size_t)p;
+    std::unique_ptr<HmcState, void (*)(HmcState*)> H(new HmcState, hmc_release);
+    H->d_state = (double*)plat_malloc(sizeof(double) * (6 * P + hmc::SC_COUNT));
+    H->d_tab = (double*)plat_malloc(sizeof(double) * (size_t)(2 * n_prior + 3 * K));
+    H->d_kind = (int*)plat_malloc(sizeof(int) * (size_t)std::max(n_prior, 1));
+    if (!H->d_state || !H->d_tab || !H->d_kind) return fail(std::string(who) + ": device allocation failed");
+    // tables: prior, likelihood constants, the evaluation's term weights
+    std::vector<double> tb((size_t)(2 * n_prior + 3 * K)), w((size_t)K);
+    for (int j = 0; j < n_prior; ++j) { tb[j] = prior_mu[j]; tb[n_prior + j] = prior_sigma[j]; }
+    for (int j = 0; j < K; ++j) {
+        const double N = (double)E.terms[j].n, Nn = (double)E.terms[j].n_norm, sd = stds[j];
+        w[j] = Nn / (2.0 * sd * sd);
+        tb[2 * n_prior + j] = -0.5 * N * std::log(2.0 * 3.14159265358979323846) - N * std::log(sd);      // (loglik_from_sse's constants, same order of operations)
+        tb[2 * n_prior + K + j] = 2.0 * sd * sd;
+        tb[2 * n_prior + 2 * K + j] = Nn;
+    }
+    if (H->ev.init(E, who, w.data(), K)) return 1;
+    const bool f64 = H->ev.f64;
+    hmc::Args& a = H->a;
+    std::memset(&a, 0, sizeof a);
+    a.P = (int)p; a.K = K; a.n_prior = n_prior; a.nn = (int)p - n_prior;
+    a.sse_roundtrip = f64 ? 1 : 0;
+    a.th_cur = H->d_state; a.th_prop = a.th_cur + P; a.r = a.th_prop + P; a.g_cur = a.r + P; a.g_prop = a.g_cur + P;
+    double* minv = a.g_prop + P;
+    a.minv = minv; a.sc = minv + P;
+    a.nn_mu = nn_mu; a.nn_sigma = nn_sigma; a.nn_var = nn_sigma * nn_sigma;
+    a.nn_const = (double)a.nn * (std::log(nn_sigma) + 0.5 * std::log(2.0 * 3.14159265358979323846));
+    double* tab = H->d_tab;
+    a.pr_mu = tab; a.pr_sigma = tab + n_prior; a.lik_c = tab + 2 * n_prior; a.lik_d = a.lik_c + K; a.lik_n = a.lik_d + K;
+    a.pr_kind = H->d_kind;
+    a.th_eval64 = H->ev.theta64(E);
+    a.th_eval32 = H->ev.theta32();
+    // host image of the state: theta twice, zero momentum and gradients, unit metric
+    std::vector<double> st(6 * P + hmc::SC_COUNT, 0.0);
+    std::copy(theta, theta + P, st.begin());
+    std::copy(theta, theta + P, st.begin() + P);
+    std::fill(st.begin() + 5 * P, st.begin() + 6 * P, 1.0);
+    std::vector<int> kinds(prior_kind, prior_kind + n_prior);
+    if (plat_h2d(H->d_state, st.data(), sizeof(double) * st.size(), E.stream) || plat_h2d(H->d_tab, tb.data(), sizeof(double) * tb.size(), E.stream) ||
+        (n_prior > 0 && plat_h2d(H->d_kind, kinds.data(), sizeof(int) * kinds.size(), E.stream)))
+        return fail(std::string(who) + ": H2D copy failed");
+    if (f64) {
+        if (plat_h2d(a.th_eval64, theta, sizeof(double) * P, E.stream)) return fail(std::string(who) + ": H2D copy failed");
+    } else {
+        std::vector<float> t32(P);
+        for (size_t i = 0; i < P; ++i) t32[i] = (float)theta[i];
+        if (plat_h2d(a.th_eval32, t32.data(), sizeof(float) * P, E.stream) || plat_sync(E.stream)) return fail(std::string(who) + ": H2D copy failed");
+    }
+    // logp and its gradient at theta: one evaluation, the update kernel with a zero kick (gradient only), the energy kernel at zero momentum
+    if (H->ev.eval(E)) return 1;
+    hmc_leap(E, *H, true, 0.0, 0.0, 0);
+    hmc::launch_energy(a, 1, H->ev.sums(P), E.stream);
+    plat_d2d(a.g_cur, a.g_prop, sizeof(double) * P, E.stream);
+    plat_d2d(a.sc + hmc::SC_LP_CUR, a.sc + hmc::SC_LP_PROP, sizeof(double), E.stream);
+    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    hmc_free(E);
+    E.hmc = H.release();
+    return 0;
+}
+
+int pinn_hmc_set_metric(pinn_handle h, const double* inv_metric, int64_t p) {
+    const char* who = "pinn_hmc_set_metric";
+    if (!h) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (hmc_ready(E, who) || check_theta(E, who, p)) return 1;
+    HmcState& H = *E.hmc;
+    std::vector<double> m((size_t)p, 1.0);
+    for (int64_t i = 0; inv_metric && i < p; ++i) {
+        if (!(inv_metric[i] > 0.0) || !std::isfinite(inv_metric[i])) return fail(std::string(who) + ": the inverse metric must be positive and finite");
+        m[(size_t)i] = inv_metric[i];
+    }
+    DeviceScope scope(E.device);
+    if (plat_h2d((double*)H.a.minv, m.data(), sizeof(double) * (size_t)p, E.stream) || plat_sync(E.stream)) return fail(std::string(who) + ": H2D copy failed");
+    return 0;
+}
+
+int pinn_hmc_draws(pinn_handle h, int ndraws, int n_leapfrog, double eps, uint64_t seed, const double* momenta, const double* uniforms,
+                   double* samples, int64_t p, double* accept_prob, double* logp) {
+    const char* who = "pinn_hmc_draws";
+    if (!h || !accept_prob || !logp) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who)) return 1;
+    if (ndraws < 1) return fail(std::string(who) + ": ndraws must be at least 1");
+    if (n_leapfrog < 1) return fail(std::string(who) + ": n_leapfrog must be at least 1");
+    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(std::string(who) + ": the step size eps must be positive and finite");
+    HmcState& H = *E.hmc;
+    DeviceScope scope(E.device);
+    H.a.th_eval64 = H.ev.theta64(E);
+    const size_t P = (size_t)p, nd = (size_t)ndraws;
+    if ((samples && !dev_grow(H.d_samples, H.samples_cap, nd * P, E.stream)) || !dev_grow(H.d_stat, H.stat_cap, 2 * nd, E.stream) ||
+        (momenta && !dev_grow(H.d_mom, H.mom_cap, nd * P, E.stream)) || (uniforms && !dev_grow(H.d_uni, H.uni_cap, nd, E.stream)))
+        return fail(std::string(who) + ": device allocation failed");
+    if ((momenta && plat_h2d(H.d_mom, momenta, sizeof(double) * nd * P, E.stream)) || (uniforms && plat_h2d(H.d_uni, uniforms, sizeof(double) * nd, E.stream)))
+        return fail(std::string(who) + ": H2D copy failed");
+    double* d_acc = H.d_stat;
+    double* d_lp = H.d_stat + nd;
+    for (int d = 0; d < ndraws; ++d) {
+        const unsigned ctr = (unsigned)H.draws;
+        hmc::launch_momentum(H.a, momenta ? H.d_mom + (size_t)d * P : nullptr, seed, ctr, E.stream);
+        hmc::launch_energy(H.a, 0, nullptr, E.stream);
+        hmc_leap(E, H, false, 0.5 * eps, eps, 1);
+        for (int s = 0; s < n_leapfrog; ++s) {
+            if (H.ev.eval(E)) return 1;                 // (the current state only changes in the accept launch: a failed call leaves the chain at its last completed draw)
+            const bool last = s == n_leapfrog - 1;
+            hmc_leap(E, H, true, last ? 0.5 * eps : eps, eps, last ? 0 : 1);
+        }
+        hmc::launch_energy(H.a, 1, H.ev.sums(P), E.stream);
+        hmc::launch_accept(H.a, d, uniforms ? H.d_uni : nullptr, seed, ctr, samples ? H.d_samples : nullptr, d_acc, d_lp, E.stream);
+        ++H.draws;
+    }
+    if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * P, E.stream)) || plat_d2h(accept_prob, d_acc, sizeof(double) * nd, E.stream) ||
+        plat_d2h(logp, d_lp, sizeof(double) * nd, E.stream))
+        return fail(std::string(who) + ": D2H copy failed");
+    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    return 0;
+}
+
+int pinn_hmc_get(pinn_handle h, double* theta, int64_t p, double* logp, double* grad) {
+    const char* who = "pinn_hmc_get";
+    if (!h || !theta) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (hmc_ready(E, who) || check_theta(E, who, p)) return 1;
+    HmcState& H = *E.hmc;
+    DeviceScope scope(E.device);
+    if (plat_d2h(theta, H.a.th_cur, sizeof(double) * (size_t)p, E.stream) || (logp && plat_d2h(logp, H.a.sc + hmc::SC_LP_CUR, sizeof(double), E.stream)) ||
+        (grad && plat_d2h(grad, H.a.g_cur, sizeof(double) * (size_t)p, E.stream)) || plat_sync(E.stream))
+        return fail(std::string(who) + ": D2H copy failed");
+    return 0;
+}
+
+}  // extern "C"

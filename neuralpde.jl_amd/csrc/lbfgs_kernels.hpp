@@ -13,7 +13,7 @@
 //             two-loop recursion newest pair first, gamma = sy / yy of the newest pair; restart to -g with cleared rings when gd >= 0; first step
 //             min(1, 1 / sqrt(g.g)) when the rings are empty, 1 otherwise; xn and the evaluation's copy.
 //   In a terminal state (CONVERGED / STALLED / MAXITER) the launch does nothing.
-// The arithmetic restates pinn_lbfgs (engine.cpp) operation by operation with floating-point contraction off.  Every dot product has the fixed
+// The arithmetic restates pinn_lbfgs (lbfgs.cpp) operation by operation with floating-point contraction off.  Every dot product has the fixed
 // order of hmc::k_hmc_energy: thread t takes elements t, t + 256, ...; per-wave butterfly (xor 32, 16, ... 1); the four waves in order.  No
 // atomics: the launch is bit-reproducible.  alpha and rho are held in LDS (<= 64 doubles each).  Every thread only ever touches the elements
 // i = t (mod 256) of the vectors, so the vector passes need no barrier; a ring pair's address is base + slot * P + i with a workgroup-uniform
