@@ -440,6 +440,16 @@ static int plan_assign_terms(pinn_engine& E) {
             int cmin = 1 + (int)npairs.size() + ((nh >> 24) ? 1 : 0);
             for (int a = 0; a < 8; ++a) cmin += ((nf >> a) & 1) + (a < 6 && ((nh >> (4 * a)) & 0xF) >= 3) + (a < 6 && ((nh >> (4 * a)) & 0xF) >= 4);
             if (nh & GEN_FLAG) cmin = (int)gen_set((int)(nh & ~GEN_FLAG)).size();
+            // the rows count the channels of the kernel that will run the term, not of the term: inside the ahead-of-time table a wider set
+            // may serve (ensure_spec: the full-Hessian kernel of a small net for {u, u_x, u_y, u_xx, u_yy}, 6 channels for 5) — a residual
+            // that fits with cmin and not with those must take the two-launch path, not fail "too long for the fused kernel tape" below.
+            // (This covers the term's own kernel only.  A small term with a descriptor `hint` that rides on a wider group of its network,
+            // below, is still counted with that group's channels there and can still be refused.)
+            const Net& N0 = E.nets[term_nets[t][0]];
+            if (N0.kind != 1 && !(nh & GEN_FLAG)) {
+                const pk::SpecInfo* s0 = find_spec(round_hp(N0.maxhidden()), (int)N0.sizes.size() - 3, N0.sizes[0], nf, npairs, nh, nullptr, variant_of(N0.act));
+                if (s0 && !s0->jit) cmin = std::max(cmin, s0->C);
+            }
             two_launch[t] = T.d + E.np + cmin + (int)probe.src_root.size() + (int)probe.tape_ops.size() > rp::MAX_ROWS_FUSED;
         }
         if (two_launch[t])

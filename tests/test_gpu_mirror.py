@@ -1,5 +1,5 @@
 """Hardware mirror of the CPU parity suite: every test of tests/test_emu_parity.py, tests/test_adaptive_losses.py,
-tests/test_reference_examples.py, tests/test_jit.py (kernels specialised with hipcc on the box), tests/test_sexpr_frontend.py, tests/test_dgm.py, tests/test_f64_mode.py (the float64 evaluation mode), tests/test_launch_geometry.py (chunked, ragged and merged launches), tests/test_random_residuals.py (random residual programs), tests/test_handle_history.py (reused handles against fresh ones) and tests/test_train_kernel.py (the persistent training kernel against the stand-alone loop, bit for bit) is re-run with the PRODUCT library (libpinn_hip.so on a gfx950 device) instead of the g++ lock-step
+tests/test_reference_examples.py, tests/test_jit.py (kernels specialised with hipcc on the box), tests/test_sexpr_frontend.py, tests/test_dgm.py, tests/test_f64_mode.py (the float64 evaluation mode), tests/test_launch_geometry.py (chunked, ragged and merged launches), tests/test_random_residuals.py (random residual programs), tests/test_handle_history.py (reused handles against fresh ones), tests/test_op_matrix.py (every tape op, value and adjoint, in every interpreter) and tests/test_train_kernel.py (the persistent training kernel against the stand-alone loop, bit for bit) is re-run with the PRODUCT library (libpinn_hip.so on a gfx950 device) instead of the g++ lock-step
 emulation — same statements, same float64 oracle, same 1e-5 tolerance.  This is where the per-term gradients (pinn_term_grads), the
 BPINN physics log-likelihood, the resident-theta Adam loop (against a host Adam), the device samplers and the adaptive-weight rules
 are checked against the oracle ON THE GPU ("Next round" item 1b)."""
@@ -14,6 +14,7 @@ import test_handle_history as th
 import test_f64_mode as tf
 import test_jit as tj
 import test_launch_geometry as tl
+import test_op_matrix as to
 import test_random_residuals as tq
 import test_reference_examples as tr
 import test_sexpr_frontend as ts
@@ -24,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 def _cases():
     out = []
-    for mod in (tp, ta, tr, tj, ts, td, tf, tk, tl, tq, th):
+    for mod in (tp, ta, tr, tj, ts, td, tf, tk, tl, tq, th, to):
         for name, fn in sorted(vars(mod).items()):
             if not (name.startswith("test_") and inspect.isfunction(fn) and fn.__module__ == mod.__name__):
                 continue

@@ -86,6 +86,46 @@ def test_lux_dense_layout_and_phi():
     np.testing.assert_allclose(po.phi_values(chain, theta, x), ref, rtol=1e-14)
 
 
+def test_max_min_nodes_value_and_selected_branch_gradient():
+    """sp.Max / sp.Min in build_residual.ev (n-ary, both modes) against a numpy evaluation written out by hand on fixed inputs; the gradient
+    is the selected operand's gradient.  No point of this test sits on a tie (there torch splits the gradient in half, the engine gives
+    it to one operand: DESIGN §6)."""
+    import sympy as sp
+    x, y = sp.symbols("x y")
+    u = sp.Function("u")
+    chain = po.Chain((2, 3, 1), "tanh")
+    theta = np.linspace(-0.9, 1.1, chain.nparams)
+    pts = np.array([[0.1, 0.35, 0.6, 0.85, 0.5], [0.9, 0.2, 0.7, 0.4, 0.05]])
+    W1, b1, W2, b2 = theta[:6].reshape(2, 3).T, theta[6:9], theta[9:12].reshape(3, 1).T, theta[12:13]
+    h = np.tanh(W1 @ pts + b1[:, None])
+    U = (W2 @ h + b2[:, None])[0]
+    ux = ((W2 * W1[:, 0]) @ (1 - h * h))[0]
+    X, Y = pts
+    cases = [(sp.Max(u(x, y), 0.2 + x), np.maximum(U, 0.2 + X), [U, 0.2 + X], np.argmax),
+             (sp.Min(u(x, y), 0.2 + x), np.minimum(U, 0.2 + X), [U, 0.2 + X], np.argmin),
+             (sp.Max(u(x, y), x * y, 0.5 - y), np.maximum(np.maximum(U, X * Y), 0.5 - Y), [U, X * Y, 0.5 - Y], np.argmax),
+             (sp.Min(sp.Derivative(u(x, y), x) + 1.2, y - 0.5, 2 * x - 1.2), np.minimum(np.minimum(ux + 1.2, Y - 0.5), 2 * X - 1.2), [ux + 1.2, Y - 0.5, 2 * X - 1.2], np.argmin)]
+    for mode in ("exact", "stencil"):
+        for e, want, operands, pick in cases:
+            prob = po.Problem(chains=[chain], depvars=[u], net_indvars=[(x, y)], pde_terms=[po.TermSpec(e, sp.Integer(0), (x, y))], bc_terms=[])
+            got = po.residual_values(prob, theta, 0, pts, mode=mode)[0]
+            ops = np.stack(operands)
+            assert np.min(np.abs(np.diff(np.sort(ops, axis=0), axis=0))) > 1e-3                 # no tie, not nearly
+            np.testing.assert_allclose(got, want, rtol=0, atol=1e-14 if mode == "exact" or operands[0] is U else 1e-8)
+            # d loss / d theta = that of the residual with every point's selected operand alone (the network operand where it is selected,
+            # a coordinate function, whose gradient is zero, elsewhere)
+            sel = pick(ops, axis=0)
+            assert 0 < np.count_nonzero(sel == 0) < pts.shape[1]                                # both kinds of point occur
+            g = po.loss_and_grad(prob, theta, [pts], mode=mode).grad
+            net = po.TermSpec(e.args[[a.has(u) for a in e.args].index(True)], sp.Integer(0), (x, y))
+            res_net = po.build_residual(po.Problem(chains=[chain], depvars=[u], net_indvars=[(x, y)], pde_terms=[net], bc_terms=[]), net, mode=mode)
+            th = torch.tensor(theta, dtype=po.DT, requires_grad=True)
+            r = res_net(torch.tensor(pts, dtype=po.DT), th)[0]
+            mask = torch.tensor((sel == 0).astype(np.float64))
+            (g_sel,) = torch.autograd.grad(torch.mean((r * mask + torch.tensor(want) * (1 - mask)) ** 2), th)
+            np.testing.assert_allclose(g, g_sel.numpy(), rtol=1e-12, atol=1e-15)
+
+
 # The stencil mode differentiates by finite differences, which turns the last bits of every float64 GEMM into ~1e-10 of a loss: the
 # math library's code path (CPU model, thread count) then decides whether a 1e-12 pin holds.  The pinned stencil values of the fixtures
 # below are therefore computed, and re-checked, in one child process with a fixed code path: MKL's conditional numerical

@@ -33,6 +33,10 @@ def _cases(npde):
     yield "cfg1_full", wl.pde_system, wl.chains[0], wl.strategy, wl.theta, None            # every thread owns one element, placed by slab entry)
     sysm, chain = poisson2d(npde, "sigmoid", width=16, hidden=2)     # 2 x 16 sigmoid, 2-D, {u, u_x, u_y, lap u}: 25 + 4 x 5 grid points
     yield "poisson2d_2x16_sigmoid", sysm, chain, npde.GridTraining(0.25), theta_for(chain, 7), [1.0, 2.0, 1.0, 3.0, 1.0]
+    import op_matrix as om                                           # op-rich residuals (tests/op_matrix.py: TRAIN): the tape inside the launch on the
+    for name in om.TRAIN:                                            # nonlinear ops — 2 x 16, 2 x 32, and MAX / POW / TAN / DIV together
+        sysm, chain, strat, th = om.train_problem(npde, name)
+        yield name, sysm, chain, strat, th, [1.0, 2.0, 0.5]
 
 
 def test_persistent_training_kernel_equals_the_loop_bit_for_bit(npde, use_emu, monkeypatch):
