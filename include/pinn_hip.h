@@ -379,7 +379,35 @@ int pinn_phi_ensemble(pinn_handle h, int net, const double* thetas, int64_t nsam
                       double* mean, double* std, double* preds);
 
 /*
- * Run-time options of a handle.  "gemm" = arithmetic of the hidden-layer GEMMs of the 64- / 128-wide (neuron-split) kernels:
+ * ENSEMBLE DERIVATIVES: posterior mean and standard deviation of derivatives of the trial function — a flux -k du/dx, a
+ * velocity from a stream function, the u_xx of a residual — over the same samples and points, in one call instead of one pinn_derivative[_f64]
+ * call per sample.  thetas, p, pts, n, ddof: exactly as pinn_phi_ensemble, which is unchanged.
+ *   orders  [nder], axes [nder][4]: request j is the derivative of order orders[j] (0 .. 4) along axes[4j .. 4j + orders[j]) — the multi-index
+ *           grammar of pinn_derivative.  Order 0 is phi itself, order 2 may be mixed, orders 3 and 4 run along one axis.  1 <= nder <= 32.
+ *   mean, std  [nder][n]: the statistics of pinn_phi_ensemble per request (double sums in the fixed order s = 0 .. nsamples-1)
+ *   preds   nullable: [nder][nsamples][n]
+ * The requests are grouped into jet passes so that no network forward runs more often than needed: every mixed (a, b) takes a two-axis pass
+ * (u, d_a u, d_b u, d_a d_b u) that also serves the first derivatives along a or b; the remaining pure requests along one axis share a line
+ * jet u, d_a u, .., d_a^K u, K the highest order left on that axis; the value rides in the first pass (a table of order 0 alone takes
+ * pinn_phi_ensemble's kernel).  One result does not depend on what else is in the table (bit for bit), and the order-0 request equals
+ * pinn_phi_ensemble bit for bit.  pinn_get_option(h, "ens_passes") = the jet passes of the last call ("ens_point_passes": its passes over
+ * points; "ens_scratch_passes": its jet passes whose images lived in device scratch).
+ * The compute type follows the handle as in pinn_phi_ensemble.  One upload of thetas, one of pts (the request table travels in the launch
+ * arguments), the launches back to back on the handle's stream, one download of mean | std and one of preds when asked for.  The budget
+ * $PINN_ENS_GB counts nder prediction slabs; $PINN_ENS_CHUNK as in pinn_phi_ensemble.  A jet multiplies the activation images by its channel
+ * count (2 .. 5): a pass keeps them in LDS while four workgroups fit a CU (40 KB each); beyond that — and always where two images of 64
+ * points exceed the 160 KB of LDS — they live in a device scratch buffer of 8 (double) / 16 (float) workgroups per CU instead: same
+ * arithmetic, same bits.  $PINN_ENS_NO_LDS (read per call) = 1 forces that storage, = 0 the LDS wherever two images of 64 points fit;
+ * $PINN_ENS_SCRATCH_WGS = workgroups per CU of the scratch storage (1 .. 64; A/B).
+ * Refused, with the handle left as it was: everything pinn_phi_ensemble refuses (its LDS limit only for a table of order 0 alone); nder outside
+ * 1..32; an order outside 0..4; an axis outside the network's inputs; a mixed request of order >= 3; a table that repeats a request (the axes of
+ * a mixed request in either order are one request); a scratch buffer beyond $PINN_ENS_GB — the message names the sizes.
+ */
+int pinn_derivative_ensemble(pinn_handle h, int net, const double* thetas, int64_t nsamples, int64_t p, const double* pts, int64_t n,
+                             int nder, const int* orders, const int* axes, int ddof, double* mean, double* std, double* preds);
+
+/*
+ * Run-time options of a handle. "gemm" = arithmetic of the hidden-layer GEMMs of the 64- / 128-wide (neuron-split) kernels:
  *   "split" (default) — every fp32 product rebuilt from three bf16 pieces per operand on the bf16 matrix pipe (6 MFMAs, fp32 accumulation):
  *                       2-4 x the rounding error of an fp32 fmaf chain, ~1.35 x faster (error budget: DESIGN.md section 6);
  *   "fp32"            — v_mfma_f32_16x16x4_f32: bit-for-bit an fmaf chain per product, for callers that need the last bit (a quasi-Newton

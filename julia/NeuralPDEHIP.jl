@@ -298,6 +298,30 @@ function phi_ensemble(e::HIPEngine, net::Integer, Θ::AbstractMatrix{<:Real}, x:
 end
 
 """
+    derivative_ensemble(e, net, Θ, x, requests; ddof = 0, return_preds = false) -> (mean, std[, preds])
+
+Derivatives of the trial function of network `net` (1-based) at every COLUMN of `Θ` (P × S) and the columns of `x` (d × N), with the mean and
+the standard deviation over the S predictions formed on the device (`pinn_derivative_ensemble`, DESIGN.md §4.10): the posterior mean / std of a
+flux, a velocity or the `u_xx` of a residual in one call instead of one `derivative` call per draw.  `requests` is a vector of axis vectors
+(1-based input axes, `length` = order 0 … 4; `Int[]` is `phi` itself; order 2 may be mixed, orders 3 and 4 run along one axis).  `mean` and
+`std` are N × R, `preds` is N × S × R.
+"""
+function derivative_ensemble(e::HIPEngine, net::Integer, Θ::AbstractMatrix{<:Real}, x::AbstractMatrix, requests::AbstractVector; ddof::Integer = 0,
+                             return_preds::Bool = false)
+    Θ64 = Matrix{Float64}(Θ); x64 = Matrix{Float64}(x); n = size(x64, 2); S = size(Θ64, 2); R = length(requests)
+    all(r -> length(r) <= 4, requests) || error("derivative_ensemble: a request takes at most 4 axes")
+    orders = Cint[length(r) for r in requests]; ax = zeros(Cint, 4, max(R, 1))
+    for (j, r) in enumerate(requests), (k, a) in enumerate(r)
+        ax[k, j] = a - 1
+    end
+    μ = zeros(Float64, n, R); σ = zeros(Float64, n, R); preds = return_preds ? zeros(Float64, n, S, R) : zeros(Float64, 0, 0, 0)
+    GC.@preserve Θ64 x64 orders ax μ σ preds check(ccall(sym(:pinn_derivative_ensemble), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Cint, Ptr{Cint}, Ptr{Cint}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        e.h, net - 1, Θ64, S, size(Θ64, 1), x64, n, R, orders, ax, ddof, μ, σ, return_preds ? pointer(preds) : Ptr{Float64}(C_NULL)), "pinn_derivative_ensemble")
+    return return_preds ? (μ, σ, preds) : (μ, σ)
+end
+
+"""
     derivative(e, net, θ, x, axes) -> 1 × N
 
 `numeric_derivative(phi, u, x, εs, order, θ)` of the reference (src/pinn_types.jl:445-482) through the engine: the EXACT derivative of the trial

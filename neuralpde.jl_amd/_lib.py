@@ -40,7 +40,7 @@ SYMBOLS = [
     "pinn_loss_grad_sharded_device_f64", "pinn_loss_grad_sharded_f64",
     "pinn_hmc_init", "pinn_hmc_set_metric", "pinn_hmc_draws", "pinn_hmc_get",
     "pinn_lbfgs_init", "pinn_lbfgs_steps", "pinn_lbfgs_get",
-    "pinn_phi_ensemble",
+    "pinn_phi_ensemble", "pinn_derivative_ensemble",
 ]
 
 
@@ -129,6 +129,10 @@ class Library:
             pass
         try:                                     # (ensemble prediction: variant libraries built before it still load)
             L.pinn_phi_ensemble.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int, dp, dp, dp]
+        except AttributeError:
+            pass
+        try:                                     # (ensemble derivatives: variant libraries built before them still load)
+            L.pinn_derivative_ensemble.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, dp, dp, dp]
         except AttributeError:
             pass
         L.pinn_lbfgs.argtypes = [vp, C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_double, fp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -454,6 +458,31 @@ class Engine:
         self.L.check(self.L.lib.pinn_phi_ensemble(self.h, int(net), th.ctypes.data_as(dp), th.shape[0], th.shape[1], flat.ctypes.data_as(dp), n, int(ddof),
                                                   mean.ctypes.data_as(dp), std.ctypes.data_as(dp), preds.ctypes.data_as(dp) if return_preds else None),
                      "pinn_phi_ensemble")
+        return (mean, std, preds) if return_preds else (mean, std)
+
+    def derivative_ensemble(self, net: int, thetas, pts, requests, ddof: int = 0, return_preds: bool = False):
+        """`pinn_derivative_ensemble`: derivatives of the trial function of network `net` at every row of thetas (S x P full parameter vectors)
+        and the columns of pts (d x N; a single point may be given as (d,)), reduced over the rows on the device.  `requests` = [(order, axes),
+        ...]: request j is d^order phi / dx_axes (order 0, axes (): phi itself; order 2 may be mixed; orders 3 and 4 along one axis).
+        -> (mean (R x N), std (R x N)[, preds (R x S x N)]), `std` with numpy's `ddof`.  The compute type follows the handle, as in `phi_ensemble`."""
+        th = np.atleast_2d(_f64(thetas))
+        pts = np.asarray(pts, dtype=np.float64)
+        if pts.ndim == 1:
+            pts = pts.reshape(-1, 1)
+        flat = np.ascontiguousarray(pts.T).reshape(-1)
+        n, dp, R = pts.shape[1], C.POINTER(C.c_double), len(requests)
+        orders = (C.c_int * max(R, 1))(*[int(o) for o, _ in requests])
+        axes = (C.c_int * (4 * max(R, 1)))()
+        for j, (o, ax) in enumerate(requests):
+            ax = [int(a) for a in ax]
+            if len(ax) != int(o) or len(ax) > 4:
+                raise ValueError(f"request {j}: order {o} takes {o} axes (at most 4), not {ax}")
+            axes[4 * j:4 * j + len(ax)] = ax
+        mean, std = np.zeros((R, n), dtype=np.float64), np.zeros((R, n), dtype=np.float64)
+        preds = np.zeros((R, th.shape[0], n), dtype=np.float64) if return_preds else None
+        self.L.check(self.L.lib.pinn_derivative_ensemble(self.h, int(net), th.ctypes.data_as(dp), th.shape[0], th.shape[1], flat.ctypes.data_as(dp), n,
+                                                         R, orders, axes, int(ddof), mean.ctypes.data_as(dp), std.ctypes.data_as(dp),
+                                                         preds.ctypes.data_as(dp) if return_preds else None), "pinn_derivative_ensemble")
         return (mean, std, preds) if return_preds else (mean, std)
 
     def phi(self, net: int, theta, pts) -> np.ndarray:

@@ -224,7 +224,7 @@ class Normal:
 
 def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, bcstd=(0.01,), l2std=(0.05,), phystd=(0.05,), priorsNNw=(0.0, 2.0),
                            param=(), n_leapfrog=30, step_size=0.1, targetacceptancerate=0.8, saveats=(0.1,), numensemble=None, rng=None,
-                           sampler="host", seed=0, ensemble="host"):
+                           sampler="host", seed=0, ensemble="host", ensemble_derivatives=()):
     """`ahmc_bayesian_pinn_pde(pde_system, discretization; draw_samples, bcstd, phystd, priorsNNw, Kernel = HMC(0.1, 30), saveats,
     numensemble)` — the forward-problem form of ext/bpinn/PDE_BPINN.jl:371-640: the posterior over the network parameters is
     prior N(priorsNNw[1], priorsNNw[2]^2 I) x physics likelihood (`pinn_loglik_grad`: every leapfrog step is ONE fused device evaluation,
@@ -236,7 +236,17 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
     `sampler = "device"` runs the transitions resident on the device (`pinn_hmc_*`; momenta and uniforms from its counter-based generator
     keyed by `seed`, the host `rng` — default_rng(seed) unless given — only feeds the initial step-size search); `stats["sampler"]` says which ran.
     `ensemble = "device"` (independent of `sampler`) forms the ensemble curves in ONE `pinn_phi_ensemble` call per dependent variable — every
-    retained draw's prediction and the mean / std over them on the device — instead of one trial-function call per draw; `stats["ensemble"]`."""
+    retained draw's prediction and the mean / std over them on the device — instead of one trial-function call per draw; `stats["ensemble"]`.
+    `ensemble_derivatives = [(depvar name, order, axes), ...]` adds the posterior mean / std of derivatives of the trial functions on the same
+    grid (a flux, a velocity, the u_xx of a residual): `sol.ensemble_derivs` / `sol.ensemble_derivs_std`, dicts keyed by (name, order, axes
+    as a tuple).  `ensemble = "device"` forms them in ONE `pinn_derivative_ensemble` call per dependent variable, `"host"` with one
+    `pinn_derivative[_f64]` call per draw and numpy.  The default `()` adds nothing."""
+    reqs = []
+    for r in ensemble_derivatives:
+        name, order, axes = r
+        reqs.append((str(name), int(order), tuple(int(a) for a in axes)))
+        if len(reqs[-1][2]) != reqs[-1][1]:
+            raise ValueError(f"ensemble_derivatives: order {order} takes {order} axes, not {list(axes)}")
     if sampler not in ("host", "device"):
         raise ValueError(f"sampler must be \"host\" or \"device\", not {sampler!r}")
     if ensemble not in ("host", "device"):
@@ -294,6 +304,11 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
     # parameters over all of them (:264-269) and builds the ensemble curves from the first numensemble of the slice (:302); restated as is
     ens_samples = samples[-(numensemble + 1):]
     ens, ens_std, tps = [], [], []
+    ens_d, ens_d_std = {}, {}
+    for r in reqs:
+        if r[0] not in [str(v) for v in rep.depvars]:
+            raise ValueError(f"ensemble_derivatives: no dependent variable {r[0]!r} (known: {[str(v) for v in rep.depvars]})")
+    f64_mode = bool(reqs) and eng.get_option("precision") == "f64"
     for i, name in enumerate(rep.depvars):
         ins = list(rep.dict_depvar_input[name])
         if len(saveats) not in (1, len(pde_system.ivs)):
@@ -306,8 +321,18 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
             axes.append(np.arange(lo, hi + 0.5 * step, step))
         mesh = np.meshgrid(*axes, indexing="ij")
         pts = np.stack([m.ravel() for m in mesh])
+        net = (rep.phi[i] if isinstance(rep.phi, (list, tuple)) else rep.phi).net
+        mine = [r for r in reqs if r[0] == str(name)]
+        if mine and ensemble == "device":        # every derivative of this variable in one call
+            dmean, dstd = eng.derivative_ensemble(net, ens_samples[:numensemble], pts, [(o, ax) for _, o, ax in mine])
+            for j, r in enumerate(mine):
+                ens_d[r], ens_d_std[r] = dmean[j], dstd[j]
+        elif mine:                               # the comparison path: one derivative call per draw and request (the full vectors: the engine slices)
+            for r in mine:
+                der = (lambda th: eng.derivative_f64(net, th, pts, r[2])) if f64_mode else (lambda th: eng.derivative(net, th, pts, r[2]).astype(np.float64))
+                dpreds = np.stack([der(th) for th in ens_samples[:numensemble]])
+                ens_d[r], ens_d_std[r] = dpreds.mean(axis=0), dpreds.std(axis=0)
         if ensemble == "device":                 # the full sample vectors and the variable's network index: the engine slices
-            net = (rep.phi[i] if isinstance(rep.phi, (list, tuple)) else rep.phi).net
             mean, std = eng.phi_ensemble(net, ens_samples[:numensemble], pts)
             ens.append(mean); ens_std.append(std); tps.append(pts)
             continue
@@ -315,5 +340,7 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
                           for th in ens_samples[:numensemble]])     # the reference predicts with the FIRST numensemble of its slice (:302)
         ens.append(preds.mean(axis=0)); ens_std.append(preds.std(axis=0)); tps.append(pts)
     sol = BPINNsolution(samples, ens, ens_std, tps, stats)
+    if reqs:
+        sol.ensemble_derivs, sol.ensemble_derivs_std = ens_d, ens_d_std
     sol.estimated_de_params = [float(ens_samples[:, nn + j].mean()) for j in range(ninv)]
     return sol

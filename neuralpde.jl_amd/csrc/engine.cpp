@@ -1245,7 +1245,10 @@ int pinn_get_option(pinn_handle h, const char* name, char* buf, int64_t buflen) 
     if (k == "f64_chunks") { std::snprintf(buf, (size_t)buflen, "%d", pe::f64_chunks(*h)); return 0; }          // chunks of the largest point set in the last float64 call
     if (k == "adam_path") { std::snprintf(buf, (size_t)buflen, "%s", h->adam_path == 2 ? "persistent" : (h->adam_path == 1 ? "loop" : "none")); return 0; }
     if (k == "lbfgs_chunk") { std::snprintf(buf, (size_t)buflen, "%d", h->lbfgs_chunk); return 0; }
-    return fail("pinn_get_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, lbfgs_chunk, grad_health, gemm_delta, adam_path, eval_path, f64_path, f64_merged, f64_chunks, f64_affine)");
+    if (k == "ens_passes") { std::snprintf(buf, (size_t)buflen, "%d", pe::ens_counter(*h, 0)); return 0; }            // jet passes of the last pinn_derivative_ensemble call
+    if (k == "ens_point_passes") { std::snprintf(buf, (size_t)buflen, "%d", pe::ens_counter(*h, 1)); return 0; }      // ... its point passes
+    if (k == "ens_scratch_passes") { std::snprintf(buf, (size_t)buflen, "%d", pe::ens_counter(*h, 2)); return 0; }    // ... its jet passes with the images in device scratch
+    return fail("pinn_get_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, lbfgs_chunk, grad_health, gemm_delta, adam_path, eval_path, f64_path, f64_merged, f64_chunks, f64_affine, ens_passes, ens_point_passes, ens_scratch_passes)");
 }
 
 // fp32 optimiser state (float64 mode: f64.cpp keeps its own, in double)

@@ -390,6 +390,8 @@ template <class V, class T> As<V, T> as(T* x, size_t n) { return As<V, T>(x, n);
 void hmc_free(pinn_engine& E);
 void lbfgs_free(pinn_engine& E);
 void ens_free(pinn_engine& E);
+// ensemble.cpp: of the last pinn_derivative_ensemble call — 0: jet passes, 1: point passes, 2: jet passes on the scratch storage (0 before any call)
+int ens_counter(const pinn_engine& E, int which);
 // comm.cpp: sum vec[i] ([P + K] floats) and raw[i] (K doubles) of the ndev handles' ranks over their communicator, in place, each on its
 // handle's stream.  ndev == 1: a one-process-per-GPU communicator (RCCL or the caller's transport; no communicator: nothing to do);
 // ndev > 1: the handles of one pinn_comm_init_all communicator, one grouped RCCL call

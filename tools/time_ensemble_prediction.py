@@ -1,8 +1,10 @@
 """BPINN prediction stage, milliseconds per dependent variable: the host loop of `ahmc_bayesian_pinn_pde` (one `phi` call per retained draw,
 mean / std in numpy) against one `phi_ensemble` call (pinn_phi_ensemble) on the same samples and points.  Medians
 of --reps runs after one warm-up run each, both paths in the same process.  Also prints the largest difference of the two paths' curves.
-  python tools/time_ensemble_prediction.py [--only small|mid|big] [--reps 21] [--samples 333] [--once device]
---once device: one warm-up and one device call per problem, nothing else (the run a kernel trace is taken from)."""
+  python tools/time_ensemble_prediction.py [--only small|mid|big] [--reps 21] [--samples 333] [--once device] [--derivatives]
+--once device: one warm-up and one device call per problem, nothing else (the run a kernel trace is taken from).
+--derivatives: the same comparison for u_x and u_xx on "mid" and "big": the host loop of one `derivative[_f64]` call per
+retained draw and request, mean / std in numpy, against ONE `derivative_ensemble` call (pinn_derivative_ensemble) for both requests."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
@@ -14,6 +16,7 @@ ap.add_argument("--only", default="")
 ap.add_argument("--reps", type=int, default=21)
 ap.add_argument("--samples", type=int, default=333)
 ap.add_argument("--once", default="")
+ap.add_argument("--derivatives", action="store_true")
 args = ap.parse_args()
 
 PROBLEMS = {            # name -> (layer sizes, points per axis)
@@ -60,11 +63,25 @@ for name, (sizes, per_axis) in PROBLEMS.items():
         def device():
             return rep.engine.phi_ensemble(0, thetas, pts)
 
+        if args.derivatives:
+            if name == "small":
+                continue
+            eng, reqs = rep.engine, [(1, (0,)), (2, (0, 0))]
+            der = (lambda t, ax: eng.derivative_f64(0, t, pts, ax)) if prec == "f64" else (lambda t, ax: eng.derivative(0, t, pts, ax).astype(np.float64))
+
+            def host():                                                  # (bpinn.py: the ensemble="host" loop over ensemble_derivatives)
+                preds = np.stack([np.stack([der(t, ax) for t in thetas]) for _, ax in reqs])
+                return preds.mean(axis=1), preds.std(axis=1)
+
+            def device():
+                return eng.derivative_ensemble(0, thetas, pts, reqs)
+
         if args.once == "device":
             device(); device()
             continue
         (mh, sh), (md, sd) = host(), device()
         diff = max(np.max(np.abs(mh - md)), np.max(np.abs(sh - sd))) / max(1.0, np.max(np.abs(mh)))
         t_host, t_dev = median_ms(host, args.reps), median_ms(device, args.reps)
-        print(f"{'-'.join(map(str, sizes)):18s} {prec} n={pts.shape[1]:6d} S={args.samples:4d}  host loop {t_host:9.3f} ms  phi_ensemble {t_dev:8.3f} ms  "
+        what = "derivative_ensemble (u_x, u_xx)" if args.derivatives else "phi_ensemble"
+        print(f"{'-'.join(map(str, sizes)):18s} {prec} n={pts.shape[1]:6d} S={args.samples:4d}  host loop {t_host:9.3f} ms  {what} {t_dev:8.3f} ms  "
               f"x{t_host / t_dev:7.1f}  curves differ by {diff:.2e}", flush=True)
