@@ -12,7 +12,6 @@
 #include "int_limits.hpp"
 #include "plat.hpp"
 #include "rprog.hpp"
-#include "update_rules.hpp"
 #include "sample_rules.hpp"
 
 namespace aux {
@@ -279,49 +278,6 @@ AUX_DEV float int_expr_point(int p, const IntExprArgs& a, float (&pb)[4]) {
     return rs;
 }
 
-// ---- resident-theta training loop ----
-// the Adam rule itself lives in update_rules.hpp (shared with the persistent training kernel, pinn_train.hpp)
-using ur::adam_update;
-AUX_DEV void adam_body(int i, float* theta, float* m, float* v, const float* grad, float lr, float b1, float b2, float eps, float c1, float c2) {
-    float mi = m[i], vi = v[i];
-    const float t = adam_update(theta[i], mi, vi, grad[i], lr, b1, b2, eps, c1, c2);
-    m[i] = mi;
-    v[i] = vi;
-    theta[i] = t;
-}
-// the resident loop's update kernel: Adam step of element i, its new value scattered into the packed weight images (inverse pack
-// map), and — one thread — the evaluation's total weighted loss into the history: one launch instead of total_loss + adam + pack
-struct AdamFusedArgs {
-    float* theta; float* m; float* v; const float* out;      // out = [P gradient | K raw per-term sums]
-    int P, K;
-    float lr, b1, b2, eps, c1, c2;
-    const int* inv_ptr; const int* inv_pos;
-    float* packed[MAX_PACK_NETS];
-    double* hist; int step; const float* w_over_n;
-};
-AUX_DEV void adam_fused_body(int i, const AdamFusedArgs& a) {
-    if (i == 0) {
-        double s = 0.0;
-        for (int k = 0; k < a.K; ++k) s += (double)a.out[a.P + k] * (double)a.w_over_n[k];
-        a.hist[a.step] = s;
-    }
-    if (i >= a.P) return;
-    float mi = a.m[i], vi = a.v[i];
-    const float t = adam_update(a.theta[i], mi, vi, a.out[i], a.lr, a.b1, a.b2, a.eps, a.c1, a.c2);
-    a.m[i] = mi;
-    a.v[i] = vi;
-    a.theta[i] = t;
-    for (int q = a.inv_ptr[i]; q < a.inv_ptr[i + 1]; ++q) {
-        const int pos = a.inv_pos[q];
-        a.packed[pos >> 24][pos & 0xFFFFFF] = t;
-    }
-}
-// total weighted loss of one evaluation from the raw per-term sums in out[P..P+K)
-AUX_DEV void total_loss_body(double* hist, int step, const float* out, int P, int K, const float* w_over_n) {
-    double s = 0.0;
-    for (int k = 0; k < K; ++k) s += (double)out[P + k] * (double)w_over_n[k];
-    hist[step] = s;
-}
 // sharded evaluations: the K per-term sums of squares cross the ranks as DOUBLES (their own all-reduce, grouped with the gradient's), so
 // that N > 1 delivers the same losses as N = 1 to double rounding; this writes them back into the float out vector [P .. P + K)
 AUX_DEV void sums_from_double_body(int k, float* out_sums, const double* raw) { out_sums[k] = (float)raw[k]; }
@@ -497,8 +453,7 @@ AUX_DEV void reduce2_body(int r, const Reduce2Args& a) {
 
 // one-stage variant for SMALL launches (every group at most REDUCE_DIRECT_MAX workgroups): theta element r sums its slab entries over the
 // workgroups directly, in the fixed order (map entry, workgroup); two kernels of ~6 us each for a 17-workgroup problem were a third of
-// its evaluation time
-constexpr int REDUCE_DIRECT_MAX = 32;
+// its evaluation time (REDUCE_DIRECT_MAX: aux_limits.hpp)
 AUX_DEV void reduce_direct_body(int t, const Reduce1Args& a1, const Reduce2Args& a) {
     if (t >= a.P + a.K) return;
     const int r = a.perm ? a.perm[t] : t;
@@ -554,39 +509,12 @@ inline void launch_pack_bf16(const PackBfArgs& a, plat_stream) {
 inline void launch_sums_from_double(float* out_sums, const double* raw, int K, plat_stream) {
     for (int k = 0; k < K; ++k) sums_from_double_body(k, out_sums, raw);
 }
-inline void launch_adam(float* theta, float* m, float* v, const float* grad, int P, float lr, float b1, float b2, float eps, float c1, float c2, plat_stream) {
-    for (int i = 0; i < P; ++i) adam_body(i, theta, m, v, grad, lr, b1, b2, eps, c1, c2);
-}
-inline void launch_total_loss(double* hist, int step, const float* out, int P, int K, const float* w_over_n, plat_stream) {
-    total_loss_body(hist, step, out, P, K, w_over_n);
-}
 inline void launch_sample(int kind, float* pts, int n_elems, int d, const float* lb, const float* ub, unsigned seed, unsigned draw, plat_stream) {
     for (int e = 0; e < n_elems; ++e) {
         if (kind == 3) sample_sobol_body(e, pts, d, lb, ub, seed, draw);
         else if (kind == 2) sample_lhs_body(e, pts, d, n_elems / d, lb, ub, seed, draw);
         else sample_body(e, pts, d, lb, ub, seed, draw);
     }
-}
-inline void launch_adam_fused(const AdamFusedArgs& a, plat_stream) {
-    for (int i = 0; i < (a.P > 1 ? a.P : 1); ++i) adam_fused_body(i, a);
-}
-inline void launch_resample(const ResampleTerm* samp, int nsamp, int max_n, int step, plat_stream) {
-    for (int p = 0; p < max_n; ++p) resample_point_sets(samp, nsamp, p, max_n, step);
-}
-// device-counter variants for the resident optimiser loop: the step index and the samplers' draw counters live in device memory, so one
-// step's launch sequence is the same every step and can be replayed as a graph (engine.cpp: pinn_adam_steps)
-inline void launch_adam_dev(float* theta, float* m, float* v, const float* grad, int P, float lr, float b1, float b2, float eps, const float* c12, const int* step, plat_stream st) {
-    launch_adam(theta, m, v, grad, P, lr, b1, b2, eps, c12[2 * step[0]], c12[2 * step[0] + 1], st);
-}
-inline void launch_total_loss_dev(double* hist, const int* step, const float* out, int P, int K, const float* w_over_n, plat_stream st) {
-    launch_total_loss(hist, step[0], out, P, K, w_over_n, st);
-}
-inline void launch_sample_dev(int kind, float* pts, int n_elems, int d, const float* lb, const float* ub, unsigned seed, const unsigned* draw, plat_stream st) {
-    launch_sample(kind, pts, n_elems, d, lb, ub, seed, draw[0], st);
-}
-inline void launch_advance(int* step, unsigned* draws, const int* sampled, int K, plat_stream) {
-    for (int t = 0; t < K; ++t) if (sampled[t]) ++draws[t];
-    ++step[0];
 }
 inline void launch_src(const SrcArgs& a, plat_stream) {
     for (int p = 0; p < a.N; ++p) src_point(p, a);
@@ -671,13 +599,6 @@ __global__ void k_params(float* params, const float* theta, const float* default
     const int j = threadIdx.x;
     if (j < np) params_body(j, params, theta, defaults, ne, p_off);
 }
-__global__ void k_adam(float* theta, float* m, float* v, const float* grad, int P, float lr, float b1, float b2, float eps, float c1, float c2) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < P) adam_body(i, theta, m, v, grad, lr, b1, b2, eps, c1, c2);
-}
-__global__ void k_total_loss(double* hist, int step, const float* out, int P, int K, const float* w_over_n) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) total_loss_body(hist, step, out, P, K, w_over_n);
-}
 __global__ void k_sample(float* pts, int n_elems, int d, const float* lb, const float* ub, unsigned seed, unsigned draw) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < n_elems) sample_body(e, pts, d, lb, ub, seed, draw);
@@ -690,61 +611,10 @@ __global__ void k_sample_sobol(float* pts, int n_elems, int d, const float* lb, 
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < n_elems) sample_sobol_body(e, pts, d, lb, ub, seed, draw);
 }
-inline void launch_adam(float* theta, float* m, float* v, const float* grad, int P, float lr, float b1, float b2, float eps, float c1, float c2, plat_stream st) {
-    hipLaunchKernelGGL(k_adam, dim3((P + 255) / 256), dim3(256), 0, st, theta, m, v, grad, P, lr, b1, b2, eps, c1, c2);
-}
-inline void launch_total_loss(double* hist, int step, const float* out, int P, int K, const float* w_over_n, plat_stream st) {
-    hipLaunchKernelGGL(k_total_loss, dim3(1), dim3(64), 0, st, hist, step, out, P, K, w_over_n);
-}
 inline void launch_sample(int kind, float* pts, int n_elems, int d, const float* lb, const float* ub, unsigned seed, unsigned draw, plat_stream st) {
     if (kind == 3) hipLaunchKernelGGL(k_sample_sobol, dim3((n_elems + 255) / 256), dim3(256), 0, st, pts, n_elems, d, lb, ub, seed, draw);
     else if (kind == 2) hipLaunchKernelGGL(k_sample_lhs, dim3((n_elems + 255) / 256), dim3(256), 0, st, pts, n_elems, d, lb, ub, seed, draw);
     else hipLaunchKernelGGL(k_sample, dim3((n_elems + 255) / 256), dim3(256), 0, st, pts, n_elems, d, lb, ub, seed, draw);
-}
-// every redrawn term of a problem in ONE launch (sample_rules.hpp: ResampleTerm): one thread per point index over the largest set
-__global__ void __launch_bounds__(256) k_resample(const ResampleTerm* samp, int nsamp, int step) {
-    resample_point_sets(samp, nsamp, (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)(gridDim.x * blockDim.x), step);
-}
-inline void launch_resample(const ResampleTerm* samp, int nsamp, int max_n, int step, plat_stream st) {
-    hipLaunchKernelGGL(k_resample, dim3((max_n + 255) / 256), dim3(256), 0, st, samp, nsamp, step);
-}
-__global__ void k_adam_fused(const AdamFusedArgs a) { adam_fused_body((int)(blockIdx.x * blockDim.x + threadIdx.x), a); }
-inline void launch_adam_fused(const AdamFusedArgs& a, plat_stream st) {
-    hipLaunchKernelGGL(k_adam_fused, dim3((a.P + 255) / 256), dim3(256), 0, st, a);
-}
-// device-counter variants for the resident optimiser loop (see the emulation section above)
-__global__ void k_adam_dev(float* theta, float* m, float* v, const float* grad, int P, float lr, float b1, float b2, float eps, const float* c12, const int* step) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int s = step[0];
-    if (i < P) adam_body(i, theta, m, v, grad, lr, b1, b2, eps, c12[2 * s], c12[2 * s + 1]);
-}
-__global__ void k_total_loss_dev(double* hist, const int* step, const float* out, int P, int K, const float* w_over_n) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) total_loss_body(hist, step[0], out, P, K, w_over_n);
-}
-__global__ void k_sample_dev(int kind, float* pts, int n_elems, int d, const float* lb, const float* ub, unsigned seed, const unsigned* draw) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n_elems) return;
-    const unsigned dr = draw[0];
-    if (kind == 3) sample_sobol_body(e, pts, d, lb, ub, seed, dr);
-    else if (kind == 2) sample_lhs_body(e, pts, d, n_elems / d, lb, ub, seed, dr);
-    else sample_body(e, pts, d, lb, ub, seed, dr);
-}
-__global__ void k_advance(int* step, unsigned* draws, const int* sampled, int K) {
-    const int t = threadIdx.x;
-    if (t < K && sampled[t]) ++draws[t];
-    if (t == 0) ++step[0];
-}
-inline void launch_adam_dev(float* theta, float* m, float* v, const float* grad, int P, float lr, float b1, float b2, float eps, const float* c12, const int* step, plat_stream st) {
-    hipLaunchKernelGGL(k_adam_dev, dim3((P + 255) / 256), dim3(256), 0, st, theta, m, v, grad, P, lr, b1, b2, eps, c12, step);
-}
-inline void launch_total_loss_dev(double* hist, const int* step, const float* out, int P, int K, const float* w_over_n, plat_stream st) {
-    hipLaunchKernelGGL(k_total_loss_dev, dim3(1), dim3(64), 0, st, hist, step, out, P, K, w_over_n);
-}
-inline void launch_sample_dev(int kind, float* pts, int n_elems, int d, const float* lb, const float* ub, unsigned seed, const unsigned* draw, plat_stream st) {
-    hipLaunchKernelGGL(k_sample_dev, dim3((n_elems + 255) / 256), dim3(256), 0, st, kind, pts, n_elems, d, lb, ub, seed, draw);
-}
-inline void launch_advance(int* step, unsigned* draws, const int* sampled, int K, plat_stream st) {
-    hipLaunchKernelGGL(k_advance, dim3(1), dim3(256), 0, st, step, draws, sampled, K);
 }
 __global__ void __launch_bounds__(256) k_expr(const ExprArgs a) {
     __shared__ double sh[5][256];

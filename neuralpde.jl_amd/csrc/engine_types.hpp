@@ -1,6 +1,6 @@
 // engine_types.hpp — data model of the host side of the C ABI, shared by descriptor.cpp (parsing), program.cpp (residual-program
 // passes), plan.cpp (kernel selection, buffers, reduction maps), engine.cpp (evaluation + the extern "C" entry points) and the resident
-// solvers' units (hmc.cpp, lbfgs.cpp, ensemble.cpp).
+// solvers' units (adam.cpp, hmc.cpp, lbfgs.cpp, ensemble.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -283,24 +283,25 @@ struct pinn_engine {
     bool timing_valid = false;
     int timing_level = 0;        // 0 (default since r04): no events, 1: per-launch-group kernel events, 2: + phase events (pinn_last_timing)
     int timing_group = -1;       // level >= 1: which launch group gets events (-1: all)
-    // resident-theta Adam state
+    // resident fp32 Adam (adam.cpp; pinn_adam_*).  The optimiser state lives from pinn_adam_init to pinn_destroy and survives a re-plan; the
+    // inverse pack map and the contribution counts belong to the kernel plan (plan.cpp builds them, free_plan releases the map); everything
+    // from d_c12 down is the persistent training kernel's (pinn_train.hpp), allocated at its first launch and kept to pinn_destroy (free_plan
+    // only marks the thread map stale: own_blocks = 0)
     float* d_opt_theta = nullptr;
     float* d_opt_m = nullptr;
     float* d_opt_v = nullptr;
-    float* d_opt_out = nullptr;      // [P + K]
-    float* d_w_over_n = nullptr;     // [K]
-    double* d_hist = nullptr;
+    float* d_opt_out = nullptr;      // [P + K] the step's [gradient | raw sums]
+    float* d_w_over_n = nullptr;     // [K] term weight / n_norm of the current call
+    double* d_hist = nullptr;        // loss history of the current call
     size_t hist_cap = 0;
-    long long opt_t = 0;
-    // device-side step state of the resident loop (pinn_adam_steps): [0] = step index of the current call; draw counters and the
-    // sampled-term mask per term; bias-correction table [2 x steps]
-    int* d_inv_ptr = nullptr;        // theta element -> positions (net << 24 | offset) in the packed weight images
-    int* d_inv_pos = nullptr;
+    long long opt_t = 0;             // steps taken since pinn_adam_init
+    int adam_path = 0;               // what the last pinn_adam_steps call ran: 0 nothing yet, 1 the stand-alone loop, 2 the persistent kernel
+    int* d_inv_ptr = nullptr;        // theta element -> positions (net << 24 | offset) in the packed weight images: the update kernels write
+    int* d_inv_pos = nullptr;        // the new parameters straight into the images
     bool inv_ok = false;
-    int* d_step = nullptr;
-    unsigned* d_draws = nullptr;
-    int* d_sampled = nullptr;
-    float* d_c12 = nullptr;
+    int max_contrib = 0, max_inv_pos = 0;      // most slab entries / image positions of one theta element (plan.cpp)
+    bool persistent = true;          // pinn_set_option "persistent": small problems run pinn_adam_steps inside one launch
+    float* d_c12 = nullptr;          // bias-correction table [2 x steps] of a persistent launch
     size_t c12_cap = 0;              // floats
     unsigned* d_bar = nullptr;       // grid-barrier words of the persistent training kernel (pinn_train.hpp)
     unsigned* h_flag = nullptr;      // host-mapped: a launch's barrier timed out
@@ -311,13 +312,10 @@ struct pinn_engine {
     void* d_train_samp = nullptr;    // its table of redrawn terms (pk::TrainSampler[train_samp_cap])
     size_t train_samp_cap = 0;       // bytes
     float* d_opt_bak = nullptr;      // [3 P] snapshot of (theta, m, v) at the start of a persistent launch (restored when its barrier times out)
-    int max_contrib = 0, max_inv_pos = 0;      // most slab entries / image positions of one theta element (plan.cpp)
-    bool persistent = true;          // pinn_set_option "persistent": small problems run pinn_adam_steps inside one launch
-    int eval_path = 0;               // what the last host-entry loss + gradient evaluation ran: 1 the stand-alone kernels, 2 one launch (eval_fused)
+    int eval_path = 0;              // what the last host-entry loss + gradient evaluation ran: 1 the stand-alone kernels, 2 one launch (eval_fused)
     int int_q = 16;                  // pinn_set_option "integral_nodes": Gauss-Legendre nodes per integral node (2..64)
     double* d_int_xi = nullptr;      // [int_q] nodes on [-1, 1] (double) and
     float* d_int_w = nullptr;        // [int_q] weights of the rule, computed in double on the host
-    int adam_path = 0;               // what the last pinn_adam_steps call ran: 0 nothing yet, 1 the stand-alone loop, 2 the persistent kernel
     // phi scratch
     float* d_phi_pts = nullptr;
     float* d_phi_out = nullptr;
@@ -347,7 +345,7 @@ int lower_sexpr_term(const SexprContext& C, const std::vector<std::string>& indv
 // program.cpp
 void analyse_static(Term& T, int np);
 bool fuse_laplacian(Term& T, int np);
-// engine.cpp (shared with comm.cpp)
+// engine.cpp (shared with comm.cpp, adam.cpp and the resident solvers' units)
 int run_loss_grad(pinn_engine& E, const float* d_theta, float* d_out, const float* term_w, int only_term, bool timing, double* lossraw = nullptr,
                   bool packed_fresh = false, bool loss_only = false, float* d_sums = nullptr);
 int upload_theta(pinn_engine& E, const float* theta, int64_t p);
@@ -359,6 +357,24 @@ int eval_and_sync(pinn_engine& E, float* d_out, const float* term_w, double* los
 // switch the GEMM arithmetic of a live handle: the kernel plan is rebuilt for the other mode (packed weight images, gradient-slab maps and
 // reduction tables differ), the installed point sets, samplers, per-point data / weights and the optimiser state stay
 int replan_gemm(pinn_engine& E, int mode);
+// the weights every network's kernels read in the next evaluation: the packed images rebuilt from d_theta (nullptr: E.d_theta) by k_pack;
+// packed_fresh: the optimiser's update kernel has written the fp32 images already
+void pack_all(pinn_engine& E, const float* d_theta = nullptr, bool packed_fresh = false);
+// seed of a term's device sampler on this rank: ranks of a communicator draw different points (their shards of one global draw)
+inline unsigned sampler_seed(const pinn_engine& E, const Term& T) {
+    return E.comm_size > 1 ? T.seed + 0x85EBCA6BU * (unsigned)(E.comm_rank + 1) : T.seed;
+}
+// one redraw of a sampled term's float point set on the handle's stream: the draw with the rank's seed (the draw counter advances), the
+// embedding rows, and with `sources` the term's coordinate-only source channels.  The float64 optimiser loop passes false: its kernels
+// read the widened copy (f64_points_from_device) and not the float source rows
+void redraw_term(pinn_engine& E, Term& T, bool sources);
+// "gemm" = "auto" (engine.cpp): the gradient-health figure of a host copy of [gradient | raw sums], and the policy's check at d_theta
+void measure_grad_health(pinn_engine& E, const float* grad_and_sums, const float* term_w);
+int gemm_auto_check(pinn_engine& E, const float* d_theta, const float* term_w, long long now);
+// adam.cpp: loss + gradient of a small problem in ONE launch of the persistent kernel (its eval_only form), synchronised.  0: done, results
+// in d_out / lossraw; 1: failed (g_err); 2: the handle does not qualify, or the launch's grid barrier timed out — the caller takes the
+// stand-alone kernels
+int eval_one_launch(pinn_engine& E, float* d_out, const float* term_w, double* lossraw);
 inline int check_theta(const pinn_engine& E, const char* who, int64_t p) {
     return p == E.ntheta ? 0 : fail(std::string(who) + ": theta length " + std::to_string(p) + " != ntheta " + std::to_string(E.ntheta));
 }
@@ -422,16 +438,14 @@ int f64_stencil_enable(pinn_engine& E, bool on);      // pinn_set_option "deriva
 bool f64_stencil_on(const pinn_engine& E);
 int f64_adam_init(pinn_engine& E, const double* theta);
 int f64_adam_get(pinn_engine& E, double* theta);
-int f64_adam_steps(pinn_engine& E, int nsteps, double lr, double beta1, double beta2, double eps, const float* term_w, double* loss_history,
-                   void (*redraw)(pinn_engine&, pe::Term&));
+int f64_adam_steps(pinn_engine& E, int nsteps, double lr, double beta1, double beta2, double eps, const float* term_w, double* loss_history);
 int f64_points_from_device(pinn_engine& E, int term);
 int f64_eval_from_device_f32(pinn_engine& E, const float* d_theta, const float* term_w, float* d_out, bool want_grad);
 int f64_eval_from_device_f64(pinn_engine& E, const double* d_theta, const float* term_w, double* d_out);
 double* f64_theta_buffer(pinn_engine& E);          // the device buffer [P, padded] every float64 evaluation of the handle reads its parameters from
 int f64_eval_resident(pinn_engine& E, const double* term_w, double* d_out);      // evaluate at the parameters in that buffer: d_out = [gradient | raw sums] (P + K doubles, device)
 int f64_eval_sharded_local(pinn_engine& E, const double* theta, const double* term_w, double** d_out);      // host theta -> this device's [gradient | sums] (P + K doubles, device)
-int f64_adam_steps_comm(pinn_engine** es, int ndev, int nsteps, double lr, double beta1, double beta2, double eps, const float* term_w, double* loss_history,
-                        void (*redraw)(pinn_engine&, pe::Term&));
+int f64_adam_steps_comm(pinn_engine** es, int ndev, int nsteps, double lr, double beta1, double beta2, double eps, const float* term_w, double* loss_history);
 // plan.cpp
 // GEMM arithmetic the kernel look-ups of the calling thread select (family 2 kernels exist as split-operand and fp32 twins): set for the
 // duration of an entry point that may look kernels up

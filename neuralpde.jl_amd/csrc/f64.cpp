@@ -1173,9 +1173,9 @@ int f64_points_from_device(pinn_engine& E, int term) {
     F.data_n = 0;                                        // (per-point data belong to the previous set: a sampled term with DATA channels fails its next evaluation with the message — ADVICE r05)
     return 0;
 }
-int f64_adam_steps(pinn_engine& E, int nsteps, double lr, double beta1, double beta2, double eps, const float* term_w, double* loss_history, void (*redraw)(pinn_engine&, Term&)) {
+int f64_adam_steps(pinn_engine& E, int nsteps, double lr, double beta1, double beta2, double eps, const float* term_w, double* loss_history) {
     pinn_engine* es[1] = {&E};
-    return f64_adam_steps_comm(es, 1, nsteps, lr, beta1, beta2, eps, term_w, loss_history, redraw);
+    return f64_adam_steps_comm(es, 1, nsteps, lr, beta1, beta2, eps, term_w, loss_history);
 }
 // this device's part of a single-process multi-device evaluation (pinn_loss_grad_sharded_f64): theta from the host, [gradient | sums] stay on the device
 int f64_eval_sharded_local(pinn_engine& E, const double* theta, const double* term_w, double** d_out) {
@@ -1187,8 +1187,7 @@ int f64_eval_sharded_local(pinn_engine& E, const double* theta, const double* te
 }
 // the resident float64 Adam loop over a communicator (r06): per iteration every rank / device evaluates its shards, ONE all-reduce of [P + K] doubles,
 // the identical update on every rank.  ndev == 1: a one-process-per-GPU communicator (or none); ndev > 1: the handles of a pinn_comm_init_all communicator
-int f64_adam_steps_comm(pinn_engine** es, int ndev, int nsteps, double lr, double beta1, double beta2, double eps, const float* term_w, double* loss_history,
-                        void (*redraw)(pinn_engine&, Term&)) {
+int f64_adam_steps_comm(pinn_engine** es, int ndev, int nsteps, double lr, double beta1, double beta2, double eps, const float* term_w, double* loss_history) {
     const int K = (int)es[0]->terms.size();
     const int P = (int)es[0]->ntheta;
     std::vector<double> w(K), won(K);
@@ -1212,7 +1211,7 @@ int f64_adam_steps_comm(pinn_engine** es, int ndev, int nsteps, double lr, doubl
             for (size_t t = 0; t < E.terms.size(); ++t) {
                 Term& T = E.terms[t];
                 if (T.sampler == 0) continue;
-                redraw(E, T);                                    // (engine.cpp: the fp32 sampler kernels, rank-specific seeds, draw counter advanced)
+                redraw_term(E, T, false);                        // (engine.cpp: the fp32 sampler kernels, rank-specific seeds, draw counter advanced)
                 if (f64_points_from_device(E, (int)t)) return 1;
             }
             if (f64_eval_device(E, S.d_opt_theta, S.d_grad, S.d_sumsq, w.data())) return 1;

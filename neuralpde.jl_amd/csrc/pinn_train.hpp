@@ -2,7 +2,7 @@
 //
 // The reference's own regime — 12..32-wide networks on 100..1,000 collocation points, trained for thousands of Adam iterations
 // (test/NNPDE1/nnpde__pde_ii_2d_poisson.jl:83-85: solve(prob, Adam(0.1); maxiters = 4000) over full_loss_function,
-// src/discretize.jl:567-598) — is launch-bound on a GPU: the stand-alone loop (engine.cpp: adam_loop) pays three dependent launches per
+// src/discretize.jl:567-598) — is launch-bound on a GPU: the stand-alone loop (adam.cpp: adam_loop) pays three dependent launches per
 // iteration (residual kernel -> fixed-order reduction -> Adam + weight-image scatter), each a few microseconds of work behind a kernel
 // boundary, a grid ramp and first-touch cache misses.  Here the whole iteration is one pass of a persistent kernel whose workgroups are
 // all resident (at most REDUCE_DIRECT_MAX = 32 workgroups on 256 CUs):

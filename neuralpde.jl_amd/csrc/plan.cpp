@@ -672,7 +672,7 @@ static int plan_pack_maps(pinn_engine& E) {
         NP.h_pack_idx = idx;
     }
     // inverse map (theta element -> its positions in the packed images): the resident optimiser's update kernel writes the new value
-    // of every parameter straight into the images, so the next evaluation needs no pack launch (engine.cpp: pinn_adam_steps)
+    // of every parameter straight into the images, so the next evaluation needs no pack launch (adam.cpp: pinn_adam_steps)
     E.inv_ok = E.nets.size() <= (size_t)aux::MAX_PACK_NETS;
     if (E.inv_ok) {
         std::vector<std::vector<int>> inv((size_t)E.ntheta);

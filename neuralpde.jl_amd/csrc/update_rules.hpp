@@ -1,4 +1,4 @@
-// update_rules.hpp — the optimiser arithmetic shared by the stand-alone update kernels (aux_kernels.hpp: k_adam, k_adam_fused, k_adam_dev)
+// update_rules.hpp — the optimiser arithmetic shared by the stand-alone update kernels (adam_kernels.hpp: k_adam, k_adam_fused)
 // and the persistent training kernel (pinn_train.hpp): ONE statement of the rule, so that K iterations inside one launch and K single steps
 // round identically.  Free of host headers (the kernel translation units and the hiprtc back end include it).
 #pragma once

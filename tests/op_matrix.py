@@ -140,7 +140,7 @@ def problem(npde, case, site, symbolic):
 
 
 # op-rich problems for the persistent training kernel (tests/test_train_kernel.py): name -> (width, expression).  The kernel exists for
-# family-1 launch groups only (engine.cpp: train_eligible) and the ahead-of-time table has no family-1 kernel for 2 x 64 (a 64-wide net runs
+# family-1 launch groups only (adam.cpp: train_eligible) and the ahead-of-time table has no family-1 kernel for 2 x 64 (a 64-wide net runs
 # family 2 and keeps the stand-alone loop), so the widest two-layer shape the kernel takes, 2 x 32, stands where a 2 x 64 problem would
 TRAIN = {
     "ops_2x16": (16, lambda A: sp.sech(A.U) + sp.log(2 + A.U) * sp.sqrt(2 + A.U) + sp.sinh(A.U) * sp.cosh(A.ux) + sp.sin(sp.pi * A.U) + A.U ** 3),

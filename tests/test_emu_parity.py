@@ -480,26 +480,29 @@ def test_resident_adam_matches_host_adam_and_sampler(npde, use_emu):
     assert not np.array_equal(np.argsort(draws[0][0]), np.argsort(draws[0][1]))      # axes are permuted independently
 
 
-def test_adam_loop_graph_replay_matches_plain_launches(npde, use_emu, monkeypatch):
-    """PINN_GRAPH=1 (step index, bias corrections and draw counters in device memory, one step recorded and replayed as a hipGraph; on
-    the emulation: the same device-counter kernels launched one by one) reproduces the default loop bit for bit, with fixed point sets
-    and with on-device resampling, across a resume."""
+def test_adam_loop_fused_update_matches_three_launches(npde, use_emu, monkeypatch):
+    """PINN_NO_FUSED_ADAM=1 (total loss, Adam step and the next step's weight pack as three launches) reproduces the loop's default — ONE
+    update kernel that also scatters the new parameters into the packed weight images — bit for bit, with fixed point sets and with
+    on-device resampling, across a resume.  Both legs are the stand-alone loop (PINN_PERSISTENT=0: this problem is small enough for the
+    persistent kernel, which has its own update and does not read the switch)."""
     sysm, chain = poisson2d(npde)
     th0 = theta_for(chain, 53)
+    monkeypatch.setenv("PINN_PERSISTENT", "0")
     for strat in (lambda: npde.GridTraining(0.25), lambda: npde.StochasticTraining(64, bcs_points=32, rng=np.random.default_rng(3))):
         out = []
-        for graph in (False, True):
-            if graph:
-                monkeypatch.setenv("PINN_GRAPH", "1")
+        for three in (False, True):
+            if three:
+                monkeypatch.setenv("PINN_NO_FUSED_ADAM", "1")
             else:
-                monkeypatch.delenv("PINN_GRAPH", raising=False)
+                monkeypatch.delenv("PINN_NO_FUSED_ADAM", raising=False)
             prob = npde.discretize(sysm, npde.PhysicsInformedNN(chain, strat(), init_params=th0, precision="f32"))
             res = npde.solve(prob, npde.Adam(0.01), maxiters=20)
+            assert prob.pinnrep.engine.get_option("adam_path") == "loop"
             res_b = npde.solve(npde.remake(prob, u0=res.u), npde.Adam(0.01), maxiters=12)
             out.append((np.asarray(res.losses), res.u, np.asarray(res_b.losses), res_b.u))
         for a, b in zip(out[0], out[1]):
             assert np.array_equal(a, b)
-    monkeypatch.delenv("PINN_GRAPH", raising=False)
+    monkeypatch.delenv("PINN_NO_FUSED_ADAM", raising=False)
 
 
 def test_library_lbfgs(npde, use_emu):

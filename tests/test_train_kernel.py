@@ -113,12 +113,6 @@ def test_persistent_training_kernel_redraws_the_point_sets_like_the_loop(npde, u
 def test_persistent_training_kernel_is_refused_where_it_does_not_apply(npde, use_emu, monkeypatch):
     sysm, chain = poisson2d(npde, "tanh", width=16, hidden=2)
     th0 = theta_for(chain, 3)
-    # the graph-replay experiment of the loop keeps the loop
-    monkeypatch.setenv("PINN_GRAPH", "1")
-    prob = npde.discretize(sysm, npde.PhysicsInformedNN(chain, npde.GridTraining(0.25), init_params=th0, precision="f32"))
-    npde.solve(prob, npde.Adam(0.01), maxiters=9)
-    assert prob.pinnrep.engine.get_option("adam_path") == "loop"
-    monkeypatch.delenv("PINN_GRAPH")
     # fixed sets: the kernel; the environment switch: the loop again
     disc = npde.PhysicsInformedNN(chain, npde.GridTraining(0.25), init_params=th0, precision="f32")
     prob = npde.discretize(sysm, disc)

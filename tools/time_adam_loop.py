@@ -1,8 +1,7 @@
 """Resident-theta Adam loop (pinn_adam_steps): us per iteration for BASELINE config 1 (1-D Poisson 3x32, 1,026 points: launch-bound), the
 reference's 2-D Poisson test at its own size (2 x 16 net, GridTraining(0.1): 121 + 4 x 11 points) and config 2 (2-D Poisson 4x64,
 65,536 + 4 x 65,536 points: kernel-bound).  Small problems run twice: the stand-alone loop (three launches per iteration, PINN_PERSISTENT=0)
-and the persistent training kernel (csrc/pinn_train.hpp: every iteration inside one launch); the two must end at the SAME parameters.
-PINN_GRAPH=1 replays one recorded step of the loop as a hipGraph instead of launching kernel by kernel."""
+and the persistent training kernel (csrc/pinn_train.hpp: every iteration inside one launch); the two must end at the SAME parameters."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
@@ -69,8 +68,7 @@ for name, make, iters in cases:
         dt = time.perf_counter() - t0
         path = prob.pinnrep.engine.get_option("adam_path")
         ends[mode] = res.u
-        print(f"{name:24s} {mode:10s} -> ran '{path}': {iters} iterations in {dt:.3f} s = {dt / iters * 1e6:7.1f} us/iteration, final loss {res.losses[-1]:.6e}"
-              f"  ({'graph replay' if os.environ.get('PINN_GRAPH') else 'plain launches'})", flush=True)
+        print(f"{name:24s} {mode:10s} -> ran '{path}': {iters} iterations in {dt:.3f} s = {dt / iters * 1e6:7.1f} us/iteration, final loss {res.losses[-1]:.6e}", flush=True)
         if path == "persistent" and LIB is not None and hasattr(LIB.lib, "pinn_debug_train_stamps"):
             import ctypes as C
             st = (C.c_ulonglong * 4)()
