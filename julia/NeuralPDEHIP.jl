@@ -400,6 +400,36 @@ function hmc_get(e::HIPEngine)
 end
 
 """
+    hmc_find_stepsize(e, ϵ0; seed = 0, normals = nothing) -> (ϵ, ntrials)
+    hmc_warmup(e, n_adapts, n_leapfrog, ϵ0; target = 0.8, seed = 0, normals = nothing, uniforms = nothing)
+        -> (samples P × n_adapts, accept_prob, logp, step_sizes, ϵ_final, inv_metric)
+
+The resident warm-up (`pinn_hmc_find_stepsize` / `pinn_hmc_warmup`, DESIGN.md §4.11): AdvancedHMC's `find_good_stepsize` and the
+`StanHMCAdaptor` over a `DiagEuclideanMetric` (dual averaging of ϵ, windowed diagonal metric) with the chain of `hmc_init` on the device.
+`normals` are STANDARD normals (P × n_adapts; the device divides by √metric, which changes inside the call).  Afterwards the handle holds
+`inv_metric` and `hmc_draws(e, n, n_leapfrog, ϵ_final)` continues the run.
+"""
+function hmc_find_stepsize(e::HIPEngine, ϵ0::Real; seed::Integer = 0, normals = nothing)
+    z = normals === nothing ? Float64[] : Vector{Float64}(normals)
+    ϵ = Ref{Float64}(0.0); nt = Ref{Cint}(0)
+    GC.@preserve z check(ccall(sym(:pinn_hmc_find_stepsize), Cint,
+        (Ptr{Cvoid}, Cdouble, UInt64, Ptr{Float64}, Int64, Ref{Float64}, Ref{Cint}),
+        e.h, Float64(ϵ0), UInt64(seed), normals === nothing ? Ptr{Float64}(C_NULL) : pointer(z), e.P, ϵ, nt), "pinn_hmc_find_stepsize")
+    return ϵ[], Int(nt[])
+end
+
+function hmc_warmup(e::HIPEngine, n_adapts::Integer, n_leapfrog::Integer, ϵ0::Real; target::Real = 0.8, seed::Integer = 0, normals = nothing, uniforms = nothing)
+    z = normals === nothing ? Float64[] : Vector{Float64}(vec(normals)); uni = uniforms === nothing ? Float64[] : Vector{Float64}(uniforms)
+    samples = zeros(Float64, e.P, n_adapts); acc = zeros(Float64, n_adapts); lp = zeros(Float64, n_adapts)
+    steps = zeros(Float64, n_adapts); minv = zeros(Float64, e.P); ϵf = Ref{Float64}(0.0)
+    GC.@preserve z uni samples acc lp steps minv check(ccall(sym(:pinn_hmc_warmup), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cdouble, Cdouble, UInt64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}),
+        e.h, n_adapts, n_leapfrog, Float64(ϵ0), Float64(target), UInt64(seed), normals === nothing ? Ptr{Float64}(C_NULL) : pointer(z),
+        uniforms === nothing ? Ptr{Float64}(C_NULL) : pointer(uni), samples, e.P, acc, lp, steps, ϵf, minv), "pinn_hmc_warmup")
+    return samples, acc, lp, steps, ϵf[], minv
+end
+
+"""
     lbfgs_init(e, θ; history = 10, weights = nothing)
     lbfgs_steps(e, maxiters; max_evals = 31 * maxiters, gtol = 1e-8) -> (loss_history, evals, status)
     lbfgs_get(e) -> (θ, f, ∇f)

@@ -38,7 +38,7 @@ SYMBOLS = [
     "pinn_adam_init_f64", "pinn_adam_get_f64", "pinn_set_point_data_f64", "pinn_loss_grad_device_f64",
     "pinn_residual_f64", "pinn_phi_f64", "pinn_derivative_f64", "pinn_term_grads_f64", "pinn_loglik_grad_f64",
     "pinn_loss_grad_sharded_device_f64", "pinn_loss_grad_sharded_f64",
-    "pinn_hmc_init", "pinn_hmc_set_metric", "pinn_hmc_draws", "pinn_hmc_get",
+    "pinn_hmc_init", "pinn_hmc_set_metric", "pinn_hmc_draws", "pinn_hmc_get", "pinn_hmc_find_stepsize", "pinn_hmc_warmup",
     "pinn_lbfgs_init", "pinn_lbfgs_steps", "pinn_lbfgs_get",
     "pinn_phi_ensemble", "pinn_derivative_ensemble",
 ]
@@ -119,6 +119,11 @@ class Library:
             L.pinn_hmc_set_metric.argtypes = [vp, dp, C.c_int64]
             L.pinn_hmc_draws.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint64, dp, dp, dp, C.c_int64, dp, dp]
             L.pinn_hmc_get.argtypes = [vp, dp, C.c_int64, dp, dp]
+        except AttributeError:
+            pass
+        try:                                     # (resident HMC warm-up: variant libraries built before it still load)
+            L.pinn_hmc_find_stepsize.argtypes = [vp, C.c_double, C.c_uint64, dp, C.c_int64, dp, C.POINTER(C.c_int)]
+            L.pinn_hmc_warmup.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint64, dp, dp, dp, C.c_int64, dp, dp, dp, dp, dp]
         except AttributeError:
             pass
         try:                                     # (resident L-BFGS: variant libraries built before it still load)
@@ -658,6 +663,36 @@ class Engine:
         lp, dp = C.c_double(), C.POINTER(C.c_double)
         self.L.check(self.L.lib.pinn_hmc_get(self.h, th.ctypes.data_as(dp), th.size, C.byref(lp), g.ctypes.data_as(dp) if g is not None else None), "pinn_hmc_get")
         return th, lp.value, g
+
+    def hmc_find_stepsize(self, eps0: float, seed: int = 0, normals=None):
+        """`pinn_hmc_find_stepsize`: the initial step-size search from the chain's current state, which it leaves alone.  normals: P standard
+        normals (None: the device generator at its reserved counter).  Returns (eps, ntrials)."""
+        z = None if normals is None else _f64(normals).reshape(-1)
+        if z is not None and z.size != self.P:
+            raise ValueError("normals: P values")
+        eps, nt, dp = C.c_double(), C.c_int(), C.POINTER(C.c_double)
+        self.L.check(self.L.lib.pinn_hmc_find_stepsize(self.h, float(eps0), int(seed) & 0xFFFFFFFFFFFFFFFF, z.ctypes.data_as(dp) if z is not None else None,
+                                                       self.P, C.byref(eps), C.byref(nt)), "pinn_hmc_find_stepsize")
+        return eps.value, nt.value
+
+    def hmc_warmup(self, n_adapts: int, n_leapfrog: int, eps0: float, target: float = 0.8, seed: int = 0, normals=None, uniforms=None):
+        """`pinn_hmc_warmup`: `n_adapts` transitions with the step size (dual averaging) and the diagonal metric (windowed variance) adapted on
+        the device, one download.  normals ([n_adapts x P] STANDARD normals: the device divides by sqrt(metric)) / uniforms ([n_adapts]) replace
+        the device generator's draws when given.  Returns (samples, accept_prob, logp, step_sizes, eps_final, inv_metric); the handle holds
+        inv_metric afterwards and `hmc_draws(..., eps_final, ...)` continues the run."""
+        nd, dp = max(int(n_adapts), 0), C.POINTER(C.c_double)
+        z = None if normals is None else _f64(normals).reshape(-1)
+        uni = None if uniforms is None else _f64(uniforms).reshape(-1)
+        if (z is not None and z.size != nd * self.P) or (uni is not None and uni.size != nd):
+            raise ValueError("normals: n_adapts x P values, uniforms: n_adapts values")
+        smp = np.zeros((nd, self.P), dtype=np.float64)
+        acc, lp, steps, minv = np.zeros(nd, dtype=np.float64), np.zeros(nd, dtype=np.float64), np.zeros(nd, dtype=np.float64), np.zeros(self.P, dtype=np.float64)
+        eps = C.c_double()
+        self.L.check(self.L.lib.pinn_hmc_warmup(self.h, int(n_adapts), int(n_leapfrog), float(eps0), float(target), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                z.ctypes.data_as(dp) if z is not None else None, uni.ctypes.data_as(dp) if uni is not None else None,
+                                                smp.ctypes.data_as(dp), self.P, acc.ctypes.data_as(dp), lp.ctypes.data_as(dp), steps.ctypes.data_as(dp),
+                                                C.byref(eps), minv.ctypes.data_as(dp)), "pinn_hmc_warmup")
+        return smp, acc, lp, steps, eps.value, minv
 
     def adam_init_f64(self, theta):
         th = _f64(theta)

@@ -14,7 +14,8 @@ which is one `pinn_loss_grad` call with those term weights (reverse mode over al
 uses forward-mode ForwardDiff over every parameter of the network).  By default the priors and the HMC sampler itself stay on the
 host as in the reference (`sampler="host"`: one device evaluation and one host round trip per leapfrog step).  `sampler="device"` runs the
 transitions on the device (`pinn_hmc_*`): theta, momentum, metric, gradient and energies stay resident, a call
-makes many draws and downloads once; the step-size search, dual averaging and the windowed metric stay here in Python.
+makes many draws and downloads once; the step-size search, dual averaging and the windowed metric stay here in Python unless
+`adaptation="device"` runs the whole warm-up in ONE resident call (`pinn_hmc_warmup`).
 """
 from __future__ import annotations
 
@@ -127,10 +128,12 @@ def _hmc(logp_grad, theta0, draw_samples, n_leapfrog, eps0, target, rng, n_adapt
     return np.asarray(samples), {"acceptance": np.asarray(accs), "step_size": eps, "inv_metric": minv, "n_adapts": n_adapts}
 
 
-def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, eps0, target, rng, seed, n_adapts=None, chunk=256):
+def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, eps0, target, rng, seed, n_adapts=None, chunk=256, adaptation="host"):
     """`_hmc` with the transitions on the device (Engine.hmc_*): the same initial step-size search on the host evaluation path (at most 42
     evaluations), the same dual averaging and windowed metric in Python around `hmc_draws(1, ...)` during adaptation (a new metric goes down
-    through `hmc_set_metric`), then the remaining draws in chunks of `chunk`.  Momenta and uniforms come from the device generator (`seed`)."""
+    through `hmc_set_metric`), then the remaining draws in chunks of `chunk`.  Momenta and uniforms come from the device generator (`seed`).
+    adaptation="device": the adaptation draws are ONE `hmc_warmup` call — the same recurrence and window on the device — after the same host
+    search, so both settings start from the same step size."""
     n = theta0.size
     n_adapts = min(draw_samples // 10, 1000) if n_adapts is None else n_adapts
     th = theta0.astype(np.float64).copy()
@@ -161,7 +164,15 @@ def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, ep
     w0, w1 = int(0.15 * n_adapts), int(0.9 * n_adapts)
     win, samples, accs = [], [], []
     m_count = 0
-    for it in range(min(n_adapts, draw_samples)):
+    host_adapts = min(n_adapts, draw_samples)
+    if adaptation == "device" and host_adapts >= 1:
+        if n_adapts > draw_samples:
+            raise ValueError("adaptation=\"device\": the warm-up is one call of n_adapts draws; draw_samples must be at least n_adapts")
+        smp, acc, _, _, eps, minv = eng.hmc_warmup(n_adapts, n_leapfrog, eps, target, seed)
+        samples.extend(smp)
+        accs.extend(acc)
+        host_adapts = 0
+    for it in range(host_adapts):
         smp, acc, _ = eng.hmc_draws(1, n_leapfrog, eps, seed)
         th, a = smp[0], float(acc[0])
         samples.append(th)
@@ -224,7 +235,7 @@ class Normal:
 
 def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, bcstd=(0.01,), l2std=(0.05,), phystd=(0.05,), priorsNNw=(0.0, 2.0),
                            param=(), n_leapfrog=30, step_size=0.1, targetacceptancerate=0.8, saveats=(0.1,), numensemble=None, rng=None,
-                           sampler="host", seed=0, ensemble="host", ensemble_derivatives=()):
+                           sampler="host", seed=0, ensemble="host", ensemble_derivatives=(), adaptation="host"):
     """`ahmc_bayesian_pinn_pde(pde_system, discretization; draw_samples, bcstd, phystd, priorsNNw, Kernel = HMC(0.1, 30), saveats,
     numensemble)` — the forward-problem form of ext/bpinn/PDE_BPINN.jl:371-640: the posterior over the network parameters is
     prior N(priorsNNw[1], priorsNNw[2]^2 I) x physics likelihood (`pinn_loglik_grad`: every leapfrog step is ONE fused device evaluation,
@@ -240,7 +251,10 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
     `ensemble_derivatives = [(depvar name, order, axes), ...]` adds the posterior mean / std of derivatives of the trial functions on the same
     grid (a flux, a velocity, the u_xx of a residual): `sol.ensemble_derivs` / `sol.ensemble_derivs_std`, dicts keyed by (name, order, axes
     as a tuple).  `ensemble = "device"` forms them in ONE `pinn_derivative_ensemble` call per dependent variable, `"host"` with one
-    `pinn_derivative[_f64]` call per draw and numpy.  The default `()` adds nothing."""
+    `pinn_derivative[_f64]` call per draw and numpy.  The default `()` adds nothing.
+    `adaptation = "device"` (needs `sampler = "device"`) runs the adaptation draws — dual averaging of the step size, the windowed diagonal
+    metric — in ONE `pinn_hmc_warmup` call instead of one `pinn_hmc_draws(1)` round trip per draw; the initial step-size search stays on the
+    host, so both settings start from the same step size; `stats["adaptation"]` says which ran.  The default `"host"` changes nothing."""
     reqs = []
     for r in ensemble_derivatives:
         name, order, axes = r
@@ -251,6 +265,10 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
         raise ValueError(f"sampler must be \"host\" or \"device\", not {sampler!r}")
     if ensemble not in ("host", "device"):
         raise ValueError(f"ensemble must be \"host\" or \"device\", not {ensemble!r}")
+    if adaptation not in ("host", "device"):
+        raise ValueError(f"adaptation must be \"host\" or \"device\", not {adaptation!r}")
+    if adaptation == "device" and sampler != "device":
+        raise ValueError("adaptation=\"device\" needs sampler=\"device\": the host sampler adapts on the host")
     if rng is None:
         rng = np.random.default_rng() if sampler == "host" else np.random.default_rng(seed)
     rep = npde.symbolic_discretize(pde_system, discretization)
@@ -292,11 +310,12 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
                 raise ValueError("sampler=\"device\": parameter priors must be Normal or LogNormal")
             kinds.append((1 if isinstance(pr, LogNormal) else 0,) + tuple(pr.params()))
         samples, stats = _hmc_device(eng, logp_grad, theta0, lambda th: eng.hmc_init(th, stds, (mu0, sd0), kinds), int(draw_samples), int(n_leapfrog),
-                                     float(step_size), float(targetacceptancerate), rng, int(seed))
+                                     float(step_size), float(targetacceptancerate), rng, int(seed), adaptation=adaptation)
     else:
         samples, stats = _hmc(logp_grad, theta0, int(draw_samples), int(n_leapfrog), float(step_size), float(targetacceptancerate), rng)
     stats["sampler"] = sampler
     stats["ensemble"] = ensemble
+    stats["adaptation"] = adaptation
     numensemble = int(draw_samples // 3) if numensemble is None else int(numensemble)
     # inference: the last `numensemble` draws on the saveats grid (one spacing per independent variable), per dependent variable
     doms = {str(d.variable): (float(d.domain.lo), float(d.domain.hi)) for d in pde_system.domain}

@@ -1,5 +1,6 @@
 // hmc.cpp — resident HMC (pinn_hmc_init / _set_metric / _draws / _get): the transition loop of
-// neuralpde.jl_amd/bpinn.py `_hmc` with the chain on the device.
+// neuralpde.jl_amd/bpinn.py `_hmc` with the chain on the device; and its warm-up (pinn_hmc_find_stepsize / _warmup; section 4.11): the initial
+// step-size search, dual averaging and the windowed diagonal metric of `_hmc_device`.
 // A leapfrog step = the handle's resident evaluation (resident.hpp: ResidentEval) + ONE update launch (hmc_kernels.hpp); nothing is read back
 // before the single download that ends pinn_hmc_draws.
 // The state has buffers of its own: evaluations and optimiser runs between two calls do not touch the chain, and the chain does not touch them.
@@ -15,7 +16,8 @@ struct pe::HmcState {
     double* d_tab = nullptr;             // [3 n_prior + 3 K]: prior mu | prior sigma | lik_c | lik_d | lik_n (+ kinds as ints in d_kind)
     int* d_kind = nullptr;
     double* d_samples = nullptr; double* d_stat = nullptr; double* d_mom = nullptr; double* d_uni = nullptr;
-    size_t samples_cap = 0, stat_cap = 0, mom_cap = 0, uni_cap = 0;
+    double* d_r0 = nullptr; double* d_steps = nullptr;      // the search's momentum [P]; the warm-up's step sizes [n_adapts + 1]
+    size_t samples_cap = 0, stat_cap = 0, mom_cap = 0, uni_cap = 0, r0_cap = 0, steps_cap = 0;
     unsigned long long draws = 0;        // draw counter of the generator (advanced per completed draw, whatever supplies momenta and uniforms)
 };
 
@@ -26,6 +28,7 @@ void hmc_release(HmcState* H) {
     H->ev.release();
     plat_free(H->d_state); plat_free(H->d_tab); plat_free(H->d_kind);
     plat_free(H->d_samples); plat_free(H->d_stat); plat_free(H->d_mom); plat_free(H->d_uni);
+    plat_free(H->d_r0); plat_free(H->d_steps);
     delete H;
 }
 
@@ -41,6 +44,11 @@ int hmc_refuse_target(pinn_engine& E, const char* who) {
 void hmc_leap(pinn_engine& E, HmcState& H, bool from_eval, double kick, double eps, int drift) {
     if (H.ev.f64) hmc::launch_leap<double>(H.a, from_eval ? H.ev.out<double>() : nullptr, kick, eps, drift, E.stream);
     else hmc::launch_leap<float>(H.a, from_eval ? H.ev.out<float>() : nullptr, kick, eps, drift, E.stream);
+}
+// the same with the step size read from the scalar block on the device: kick = kfac * eps
+void hmc_leap_dev(pinn_engine& E, HmcState& H, bool from_eval, double kfac, int drift) {
+    if (H.ev.f64) hmc::launch_leap_dev<double>(H.a, from_eval ? H.ev.out<double>() : nullptr, kfac, drift, E.stream);
+    else hmc::launch_leap_dev<float>(H.a, from_eval ? H.ev.out<float>() : nullptr, kfac, drift, E.stream);
 }
 
 }  // namespace
@@ -184,6 +192,103 @@ int pinn_hmc_draws(pinn_handle h, int ndraws, int n_leapfrog, double eps, uint64
     }
     if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * P, E.stream)) || plat_d2h(accept_prob, d_acc, sizeof(double) * nd, E.stream) ||
         plat_d2h(logp, d_lp, sizeof(double) * nd, E.stream))
+        return fail(std::string(who) + ": D2H copy failed");
+    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    return 0;
+}
+
+int pinn_hmc_find_stepsize(pinn_handle h, double eps0, uint64_t seed, const double* normals, int64_t p, double* eps, int* ntrials) {
+    const char* who = "pinn_hmc_find_stepsize";
+    if (!h || !eps) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who)) return 1;
+    if (!(eps0 > 0.0) || !std::isfinite(eps0)) return fail(std::string(who) + ": the step size eps0 must be positive and finite");
+    HmcState& H = *E.hmc;
+    DeviceScope scope(E.device);
+    H.a.th_eval64 = H.ev.theta64(E);
+    const size_t P = (size_t)p;
+    if (!dev_grow(H.d_r0, H.r0_cap, P, E.stream) || (normals && !dev_grow(H.d_mom, H.mom_cap, P, E.stream)))
+        return fail(std::string(who) + ": device allocation failed");
+    if (normals && plat_h2d(H.d_mom, normals, sizeof(double) * P, E.stream)) return fail(std::string(who) + ": H2D copy failed");
+    // r0 and h0 = -logp(current) + 1/2 sum minv r0^2; the current state, its gradient and logp are only read from here on
+    hmc::launch_momentum_z(H.a, normals ? H.d_mom : nullptr, seed, 0xFFFFFFFFu, E.stream);
+    hmc::launch_energy(H.a, 0, nullptr, E.stream);
+    plat_d2d(H.d_r0, H.a.r, sizeof(double) * P, E.stream);
+    const double log08 = std::log(0.8);
+    double e = eps0, direction = 0.0;
+    int trials = 0;
+    for (int t = 0; t <= 40; ++t) {
+        if (t > 0) {
+            e *= direction > 0 ? 2.0 : 0.5;
+            plat_d2d(H.a.r, H.d_r0, sizeof(double) * P, E.stream);
+        }
+        hmc_leap(E, H, false, 0.5 * e, e, 1);
+        if (H.ev.eval(E)) return 1;
+        hmc_leap(E, H, true, 0.5 * e, e, 0);
+        hmc::launch_energy(H.a, 1, H.ev.sums(P), E.stream);
+        double hh[2];                                    // H_old, H_new: neighbours in the scalar block
+        if (plat_d2h(hh, H.a.sc + hmc::SC_H_OLD, sizeof hh, E.stream) || plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+        double d = hh[0] - hh[1];
+        ++trials;
+        if (t == 0) {
+            direction = (std::isfinite(d) && d > log08) ? 1.0 : -1.0;
+            continue;
+        }
+        if (!std::isfinite(d)) d = -INFINITY;
+        if ((direction > 0) == (d <= log08)) break;
+    }
+    *eps = e;
+    if (ntrials) *ntrials = trials;
+    return 0;
+}
+
+int pinn_hmc_warmup(pinn_handle h, int n_adapts, int n_leapfrog, double eps0, double target, uint64_t seed, const double* normals, const double* uniforms,
+                    double* samples, int64_t p, double* accept_prob, double* logp, double* step_sizes, double* eps_final, double* inv_metric) {
+    const char* who = "pinn_hmc_warmup";
+    if (!h || !accept_prob || !logp || !eps_final) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who)) return 1;
+    if (n_adapts < 1) return fail(std::string(who) + ": n_adapts must be at least 1");
+    if (n_leapfrog < 1) return fail(std::string(who) + ": n_leapfrog must be at least 1");
+    if (!(eps0 > 0.0) || !std::isfinite(eps0)) return fail(std::string(who) + ": the step size eps0 must be positive and finite");
+    if (!(target > 0.0) || !(target < 1.0)) return fail(std::string(who) + ": the target acceptance rate must be in (0, 1)");
+    HmcState& H = *E.hmc;
+    DeviceScope scope(E.device);
+    H.a.th_eval64 = H.ev.theta64(E);
+    const size_t P = (size_t)p, nd = (size_t)n_adapts;
+    if (!dev_grow(H.d_samples, H.samples_cap, nd * P, E.stream) || !dev_grow(H.d_stat, H.stat_cap, 2 * nd, E.stream) ||
+        !dev_grow(H.d_steps, H.steps_cap, nd + 1, E.stream) ||
+        (normals && !dev_grow(H.d_mom, H.mom_cap, nd * P, E.stream)) || (uniforms && !dev_grow(H.d_uni, H.uni_cap, nd, E.stream)))
+        return fail(std::string(who) + ": device allocation failed");
+    // eps, mu, hbar, log_eps_bar, m: neighbours in the scalar block; step_sizes[0]
+    const double sc0[5] = {eps0, std::log(10.0 * eps0), 0.0, 0.0, 0.0};
+    if ((normals && plat_h2d(H.d_mom, normals, sizeof(double) * nd * P, E.stream)) || (uniforms && plat_h2d(H.d_uni, uniforms, sizeof(double) * nd, E.stream)) ||
+        plat_h2d(H.a.sc + hmc::SC_EPS, sc0, sizeof sc0, E.stream) || plat_h2d(H.d_steps, sc0, sizeof(double), E.stream))
+        return fail(std::string(who) + ": H2D copy failed");
+    const int w0 = (int)(0.15 * (double)n_adapts), w1 = (int)(0.9 * (double)n_adapts);      // the variance window of the metric
+    const bool metric_event = w1 - w0 >= 8 && n_adapts >= 100;
+    double* d_acc = H.d_stat;
+    double* d_lp = H.d_stat + nd;
+    for (int d = 0; d < n_adapts; ++d) {
+        const unsigned ctr = (unsigned)H.draws;
+        hmc::launch_momentum_z(H.a, normals ? H.d_mom + (size_t)d * P : nullptr, seed, ctr, E.stream);
+        hmc::launch_energy(H.a, 0, nullptr, E.stream);
+        hmc_leap_dev(E, H, false, 0.5, 1);
+        for (int s = 0; s < n_leapfrog; ++s) {
+            if (H.ev.eval(E)) return 1;                 // (the chain is at its last completed draw, under the metric in force there)
+            const bool last = s == n_leapfrog - 1;
+            hmc_leap_dev(E, H, true, last ? 0.5 : 1.0, last ? 0 : 1);
+        }
+        hmc::launch_energy(H.a, 1, H.ev.sums(P), E.stream);
+        const bool restart = metric_event && d == w1 - 1;
+        const int flags = (restart ? hmc::ADAPT_RESTART : 0) | (d == n_adapts - 1 ? hmc::ADAPT_LAST : 0);
+        hmc::launch_accept_adapt(H.a, d, uniforms ? H.d_uni : nullptr, seed, ctr, H.d_samples, d_acc, d_lp, target, flags, H.d_steps, E.stream);
+        if (restart) hmc::launch_window_metric(H.a, H.d_samples, w0, w1, E.stream);
+        ++H.draws;
+    }
+    if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * P, E.stream)) || plat_d2h(accept_prob, d_acc, sizeof(double) * nd, E.stream) ||
+        plat_d2h(logp, d_lp, sizeof(double) * nd, E.stream) || (step_sizes && plat_d2h(step_sizes, H.d_steps, sizeof(double) * nd, E.stream)) ||
+        plat_d2h(eps_final, H.d_steps + nd, sizeof(double), E.stream) || (inv_metric && plat_d2h(inv_metric, H.a.minv, sizeof(double) * P, E.stream)))
         return fail(std::string(who) + ": D2H copy failed");
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     return 0;

@@ -9,6 +9,13 @@
 //                    thread t takes elements t, t + 256, ...; per-wave butterfly (xor 32, 16, ... 1); the four waves in order.  No atomics.
 //   k_hmc_accept   : a = exp(min(0, H_old - H_new)) (0 when H_new is not finite), u < a, elementwise selection of theta / gradient / logp,
 //                    row `draw` of the sample buffer, accept_prob[draw], logp[draw]
+// The warm-up (pinn_hmc_find_stepsize / pinn_hmc_warmup) adds, with the same bodies where a body exists:
+//   k_hmc_momentum_z      : r_i = z_i / sqrt(minv_i) with z from the caller's standard normals (or the generator): the metric changes inside the call
+//   k_hmc_leap_dev<T>     : leap_body with eps read from the scalar block (a uniform load), kick = kfac * eps, kfac in {1/2, 1} from the host
+//   k_hmc_accept_adapt    : accept_body; element 0 then runs adapt_body — dual averaging of eps (bpinn.py `_hmc_device`), the restart after a
+//                           metric event, the final average — and writes the next draw's eps to the scalar block and to step_sizes[draw + 1]
+//   k_hmc_window_metric   : minv_i = (k / (k + 5)) var_i + 1e-3 (5 / (k + 5)), var_i the population variance of column i over sample rows
+//                           [w0, w1): mean first, then squared deviations, rows in order (numpy.var's two passes); one thread per parameter
 // The arithmetic restates neuralpde.jl_amd/bpinn.py (`_hmc`, `logp_grad`, `Normal` / `LogNormal`) operation by operation, with floating-point
 // contraction off: elementwise results equal the host sampler's bit for bit, sums to their order.
 // Every body exists once; the PINN_EMU build runs the same bodies serially (the energy sums in the device's order).
@@ -31,7 +38,10 @@ namespace hmc {
 #define HMC_NO_CONTRACT
 #endif
 
-enum { SC_LP_CUR = 0, SC_H_OLD = 1, SC_H_NEW = 2, SC_LP_PROP = 3, SC_COUNT = 4 };
+enum { SC_LP_CUR = 0, SC_H_OLD = 1, SC_H_NEW = 2, SC_LP_PROP = 3,
+       SC_EPS = 4, SC_MU = 5, SC_HBAR = 6, SC_LOG_EPS_BAR = 7, SC_M = 8,      // the warm-up's step size and dual-averaging state (m as a double)
+       SC_COUNT = 9 };
+enum { ADAPT_RESTART = 1, ADAPT_LAST = 2 };
 enum { PRIOR_NORMAL = 0, PRIOR_LOGNORMAL = 1 };
 constexpr int BLOCK = 256;
 
@@ -42,7 +52,7 @@ struct Args {
     double* r;                           // [P] momentum
     double* g_cur; double* g_prop;       // [P] log-posterior gradient at th_cur / th_prop
     const double* minv;                  // [P] diagonal inverse metric
-    double* sc;                          // [SC_COUNT] logp(current), H_old, H_new, logp(proposal)
+    double* sc;                          // [SC_COUNT] logp(current), H_old, H_new, logp(proposal); eps, mu, hbar, log_eps_bar, m of a warm-up
     double nn_mu, nn_sigma, nn_var, nn_const;      // nn_var = sigma^2, nn_const = nn (log sigma + 1/2 log 2 pi)
     const int* pr_kind; const double* pr_mu; const double* pr_sigma;      // [n_prior]
     const double* lik_c; const double* lik_d; const double* lik_n;        // [K] -N/2 log 2 pi - N log s | 2 s^2 | N_norm
@@ -171,6 +181,47 @@ HMC_DEV void accept_body(int i, const Args& a, int draw, const double* uniforms,
     }
 }
 
+// ---- the warm-up ----
+HMC_DEV void momentum_z_body(int i, const Args& a, const double* z, unsigned key) {
+    a.r[i] = (z ? z[i] : rng_normal(key, (unsigned)i)) / sqrt(a.minv[i]);
+}
+
+// bpinn.py `_hmc_device`, the adaptation after a draw with acceptance probability `acc`, in its order of operations; element 0 of the accept
+// launch only.  flags: what the host knows from (draw, n_adapts) alone.  `next` = step_sizes[draw + 1] (the final step size after the last draw).
+HMC_DEV void adapt_body(const Args& a, double acc, double target, int flags, double* next) {
+    HMC_NO_CONTRACT
+    const double t0 = 10.0, gamma = 0.05, kappa = 0.75;
+    double mu = a.sc[SC_MU], hbar = a.sc[SC_HBAR], leb = a.sc[SC_LOG_EPS_BAR], m = a.sc[SC_M];
+    m = m + 1.0;
+    hbar = (1.0 - 1.0 / (m + t0)) * hbar + (target - acc) / (m + t0);
+    const double log_eps = mu - sqrt(m) / gamma * hbar;
+    const double eta = pow(m, -kappa);
+    leb = eta * log_eps + (1.0 - eta) * leb;
+    double eps = exp(log_eps);
+    if (flags & ADAPT_RESTART) {                         // a new metric follows this launch: search again from the step just found
+        mu = log(10.0 * eps);
+        hbar = 0.0; leb = 0.0; m = 0.0;
+    }
+    if ((flags & ADAPT_LAST) && m > 0.0) eps = exp(leb);
+    a.sc[SC_MU] = mu; a.sc[SC_HBAR] = hbar; a.sc[SC_LOG_EPS_BAR] = leb; a.sc[SC_M] = m;
+    a.sc[SC_EPS] = eps;                                  // (its first readers are the next draw's launches)
+    *next = eps;
+}
+
+HMC_DEV void window_metric_body(int i, const Args& a, double* minv, const double* samples, int w0, int w1) {
+    HMC_NO_CONTRACT
+    const double k = (double)(w1 - w0);
+    double s = 0.0;
+    for (int row = w0; row < w1; ++row) s += samples[(size_t)row * a.P + i];
+    const double mean = s / k;
+    double q = 0.0;
+    for (int row = w0; row < w1; ++row) {
+        const double d = samples[(size_t)row * a.P + i] - mean;
+        q += d * d;
+    }
+    minv[i] = (k / (k + 5.0)) * (q / k) + 1e-3 * (5.0 / (k + 5.0));
+}
+
 #ifdef PINN_EMU
 inline void launch_momentum(const Args& a, const double* row, uint64_t seed, unsigned draw, plat_stream) {
     const unsigned key = rng_key((unsigned)seed, (unsigned)(seed >> 32), draw);
@@ -198,6 +249,24 @@ inline void launch_energy(const Args& a, int mode, const double* sse, plat_strea
 inline void launch_accept(const Args& a, int draw, const double* uniforms, uint64_t seed, unsigned ctr, double* samples, double* accept_prob, double* logp, plat_stream) {
     const unsigned key = rng_key((unsigned)seed, (unsigned)(seed >> 32), ctr);
     for (int i = a.P - 1; i >= 0; --i) accept_body(i, a, draw, uniforms, key, samples, accept_prob, logp);      // (element 0 last: it overwrites logp(current))
+}
+inline void launch_momentum_z(const Args& a, const double* z, uint64_t seed, unsigned draw, plat_stream) {
+    const unsigned key = rng_key((unsigned)seed, (unsigned)(seed >> 32), draw);
+    for (int i = 0; i < a.P; ++i) momentum_z_body(i, a, z, key);
+}
+template <class T> inline void launch_leap_dev(const Args& a, const T* ev, double kfac, int drift, plat_stream) {
+    HMC_NO_CONTRACT
+    const double eps = a.sc[SC_EPS];
+    for (int i = 0; i < a.P; ++i) leap_body<T>(i, a, ev, kfac * eps, eps, drift);
+}
+inline void launch_accept_adapt(const Args& a, int draw, const double* uniforms, uint64_t seed, unsigned ctr, double* samples, double* accept_prob, double* logp,
+                                double target, int flags, double* step_sizes, plat_stream) {
+    const unsigned key = rng_key((unsigned)seed, (unsigned)(seed >> 32), ctr);
+    for (int i = a.P - 1; i >= 0; --i) accept_body(i, a, draw, uniforms, key, samples, accept_prob, logp);
+    adapt_body(a, accept_prob[draw], target, flags, step_sizes + draw + 1);
+}
+inline void launch_window_metric(const Args& a, const double* samples, int w0, int w1, plat_stream) {
+    for (int i = 0; i < a.P; ++i) window_metric_body(i, a, const_cast<double*>(a.minv), samples, w0, w1);
 }
 #else
 __global__ void __launch_bounds__(BLOCK) k_hmc_momentum(const Args a, const double* row, unsigned seed_lo, unsigned seed_hi, unsigned draw) {
@@ -229,6 +298,26 @@ __global__ void __launch_bounds__(BLOCK) k_hmc_accept(const Args a, int draw, co
     const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
     if (i < a.P) accept_body(i, a, draw, uniforms, rng_key(seed_lo, seed_hi, ctr), samples, accept_prob, logp);
 }
+__global__ void __launch_bounds__(BLOCK) k_hmc_momentum_z(const Args a, const double* z, unsigned seed_lo, unsigned seed_hi, unsigned draw) {
+    const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
+    if (i < a.P) momentum_z_body(i, a, z, rng_key(seed_lo, seed_hi, draw));
+}
+template <class T> __global__ void __launch_bounds__(BLOCK) k_hmc_leap_dev(const Args a, const T* ev, double kfac, int drift) {
+    HMC_NO_CONTRACT
+    const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
+    const double eps = a.sc[SC_EPS];                     // (the same address in every lane)
+    if (i < a.P) leap_body<T>(i, a, ev, kfac * eps, eps, drift);
+}
+__global__ void __launch_bounds__(BLOCK) k_hmc_accept_adapt(const Args a, int draw, const double* uniforms, unsigned seed_lo, unsigned seed_hi, unsigned ctr,
+                                                            double* samples, double* accept_prob, double* logp, double target, int flags, double* step_sizes) {
+    const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
+    if (i < a.P) accept_body(i, a, draw, uniforms, rng_key(seed_lo, seed_hi, ctr), samples, accept_prob, logp);
+    if (i == 0) adapt_body(a, accept_prob[draw], target, flags, step_sizes + draw + 1);      // (nobody reads the adaptation scalars in this launch)
+}
+__global__ void __launch_bounds__(BLOCK) k_hmc_window_metric(const Args a, double* minv, const double* samples, int w0, int w1) {
+    const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
+    if (i < a.P) window_metric_body(i, a, minv, samples, w0, w1);
+}
 inline void launch_momentum(const Args& a, const double* row, uint64_t seed, unsigned draw, plat_stream st) {
     hipLaunchKernelGGL(k_hmc_momentum, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, row, (unsigned)seed, (unsigned)(seed >> 32), draw);
 }
@@ -241,6 +330,20 @@ inline void launch_energy(const Args& a, int mode, const double* sse, plat_strea
 inline void launch_accept(const Args& a, int draw, const double* uniforms, uint64_t seed, unsigned ctr, double* samples, double* accept_prob, double* logp, plat_stream st) {
     hipLaunchKernelGGL(k_hmc_accept, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, draw, uniforms, (unsigned)seed, (unsigned)(seed >> 32), ctr,
                        samples, accept_prob, logp);
+}
+inline void launch_momentum_z(const Args& a, const double* z, uint64_t seed, unsigned draw, plat_stream st) {
+    hipLaunchKernelGGL(k_hmc_momentum_z, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, z, (unsigned)seed, (unsigned)(seed >> 32), draw);
+}
+template <class T> inline void launch_leap_dev(const Args& a, const T* ev, double kfac, int drift, plat_stream st) {
+    hipLaunchKernelGGL(k_hmc_leap_dev<T>, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, ev, kfac, drift);
+}
+inline void launch_accept_adapt(const Args& a, int draw, const double* uniforms, uint64_t seed, unsigned ctr, double* samples, double* accept_prob, double* logp,
+                                double target, int flags, double* step_sizes, plat_stream st) {
+    hipLaunchKernelGGL(k_hmc_accept_adapt, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, draw, uniforms, (unsigned)seed, (unsigned)(seed >> 32), ctr,
+                       samples, accept_prob, logp, target, flags, step_sizes);
+}
+inline void launch_window_metric(const Args& a, const double* samples, int w0, int w1, plat_stream st) {
+    hipLaunchKernelGGL(k_hmc_window_metric, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, const_cast<double*>(a.minv), samples, w0, w1);
 }
 #endif
 
