@@ -44,7 +44,7 @@ template <class S, int MODE, int ACTK>
 void run_emu(const GroupArgs& ga, int blocks) {
     std::vector<float> lds((size_t)S::LDS_WG);
     for (int b = 0; b < blocks; ++b) {
-        std::fill(lds.begin(), lds.end(), 0.f);
+        std::fill(lds.begin(), lds.end(), std::nanf(""));       // poison, as run_emu2 below: the GPU's LDS holds the previous kernel's bytes
         EmuBarrier bar;
         std::thread th[4];
         for (int w = 0; w < 4; ++w)
@@ -60,7 +60,7 @@ void run_emu(const GroupArgs& ga, int blocks) {
 // (wg_barrier) and one over all of them (grid_barrier)
 template <class S, int ACTK>
 void run_emu_train(const GroupArgs& ga, const TrainArgs& ta, int blocks) {
-    std::vector<std::vector<float>> lds((size_t)blocks, std::vector<float>((size_t)S::LDS_WG, 0.f));
+    std::vector<std::vector<float>> lds((size_t)blocks, std::vector<float>((size_t)S::LDS_WG, std::nanf("")));       // poisoned likewise
     std::vector<EmuBarrier> bars((size_t)blocks);
     EmuBarrier grid;
     grid.nwaves = 4 * blocks;
