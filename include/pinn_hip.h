@@ -400,6 +400,33 @@ int pinn_lbfgs_steps(pinn_handle h, int maxiters, int max_evals, double gtol, do
 int pinn_lbfgs_get(pinn_handle h, double* theta, int64_t p, double* f, double* grad);
 
 /*
+ * RESIDENT BFGS: the dense quasi-Newton finisher — `solve(prob, BFGS(); maxiters)` of the reference's scripts — with the
+ * iterate, the P x P inverse-Hessian approximation H (double, full symmetric storage) and the line search in HBM.  Opt-in; the L-BFGS routines are
+ * unchanged.  Same line search, constants, slots, chunks ("lbfgs_chunk") and statuses as the resident L-BFGS above; in place of the two-loop
+ * recursion, per accepted iteration, u = H y (one read pass over H by many workgroups, one wave per row) and the rank-two update
+ *     H[i][j] <- (H[i][j] - rho (s_i u_j + u_i s_j)) + c (s_i s_j),  rho = 1 / s.y,  c = rho (1 + rho y.u),
+ * fused with the next direction d = -H g (one read + write pass); every product is rounded on its own, so H stays bit-symmetric.  The update is
+ * skipped unless s.y > 1e-10 |s| |y|.  H starts as the identity (first step min(1, 1 / |g|_2)), is scaled to (s.y / y.y) I when the first update
+ * arrives, and returns to the identity when g.d >= 0 (restart); the identity costs no pass over the matrix.  Bit-reproducible from run to run and
+ * independent of "lbfgs_chunk".  A rejected trial costs a full evaluation; an accepted trial is never re-evaluated.
+ *   pinn_bfgs_init    uploads theta (p doubles), fixes the term weights (NULL: ones), evaluates f and g once, H = I.  A second call replaces the state.
+ *   pinn_bfgs_steps   as pinn_lbfgs_steps, argument by argument: at most `maxiters` further iterations and `max_evals` further trial evaluations from
+ *                     the stored state; loss_history padded with the last objective; *status 0 RUN, 1 RETRY, 2 CONVERGED, 3 STALLED, 4 MAXITER.  A
+ *                     terminal status ends the call, not the optimisation.  At STALLED a handle in "split" GEMM mode switches itself to "fp32" once
+ *                     per call, re-evaluates at x, resets H to the identity and goes on, and is switched back before the call returns
+ *                     ($PINN_LBFGS_KEEP_GEMM=1 disables that).
+ *   pinn_bfgs_get     the current iterate: theta (p doubles), *f (nullable), grad (p doubles, nullable), hinv (p x p doubles row-major, nullable):
+ *                     the inverse-Hessian approximation as it stands — at an optimum the covariance of a Laplace approximation.
+ * The state has buffers of its own: evaluations, pinn_adam_*, pinn_lbfgs_* and pinn_hmc_* between two calls leave it alone and vice versa.
+ * Refused, with the handle left as it was: pinn_bfgs_steps / _get before pinn_bfgs_init; a handle whose precision mode changed since (init again);
+ * a term with a device sampler; a handle on a communicator; p != ntheta; maxiters < 1; max_evals < 1; p above 32768 (the matrix is 8 p^2 bytes:
+ * 8 GiB there; $PINN_BFGS_MAX_P lowers the cap) or a matrix the device cannot allocate — the message names P and the bytes.
+ */
+int pinn_bfgs_init(pinn_handle h, const double* theta, int64_t p, const float* term_w);
+int pinn_bfgs_steps(pinn_handle h, int maxiters, int max_evals, double gtol, double* loss_history, int* iters_done, int* evals_done, int* status);
+int pinn_bfgs_get(pinn_handle h, double* theta, int64_t p, double* f, double* grad, double* hinv);
+
+/*
  * ENSEMBLE PREDICTION: the trial function of network `net` at `nsamples` parameter vectors and n points, and the mean and
  * standard deviation over the samples at every point, in one call — the prediction stage of a Bayesian PINN (ext/bpinn/PDE_BPINN.jl:254-302),
  * deep-ensemble or checkpoint prediction.  Opt-in: pinn_phi / pinn_phi_f64 are unchanged.

@@ -467,6 +467,45 @@ function lbfgs_resident!(e::HIPEngine, θ::AbstractVector{<:Real}; maxiters::Int
     return θ, hist
 end
 
+"""
+    bfgs_init(e, θ; weights = nothing)
+    bfgs_steps(e, maxiters; max_evals = 31 * maxiters, gtol = 1e-8) -> (loss_history, evals, status)
+    bfgs_get(e; hinv = false) -> (θ, f, ∇f, H⁻¹ or nothing)
+    bfgs_resident!(e, θ; maxiters, gtol = 1e-8, weights = nothing) -> (θ, loss_history)
+
+The resident dense BFGS finisher (`pinn_bfgs_init / _steps / _get`, DESIGN.md §4.12): `solve(prob, BFGS(); maxiters)` with the iterate, the
+P × P inverse-Hessian approximation and the line search on the device.  `status` as for `lbfgs_steps`.  The term weights are fixed at
+`bfgs_init`.  `bfgs_get(e; hinv = true)` also returns the inverse-Hessian approximation (row-major P × P; it is symmetric).
+"""
+function bfgs_init(e::HIPEngine, θ::AbstractVector{<:Real}; weights = nothing)
+    θ64 = Vector{Float64}(θ); w = weights === nothing ? Float32[] : Vector{Float32}(weights)
+    GC.@preserve θ64 w check(ccall(sym(:pinn_bfgs_init), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float32}),
+        e.h, θ64, e.P, weights === nothing ? Ptr{Float32}(C_NULL) : pointer(w)), "pinn_bfgs_init")
+    return nothing
+end
+
+function bfgs_steps(e::HIPEngine, maxiters::Integer; max_evals::Integer = 31 * maxiters, gtol::Real = 1e-8)
+    hist = zeros(Float64, maxiters); it = Ref{Cint}(0); ev = Ref{Cint}(0); st = Ref{Cint}(0)
+    GC.@preserve hist check(ccall(sym(:pinn_bfgs_steps), Cint, (Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Float64}, Ref{Cint}, Ref{Cint}, Ref{Cint}),
+        e.h, maxiters, max_evals, Float64(gtol), hist, it, ev, st), "pinn_bfgs_steps")
+    return hist[1:it[]], Int(ev[]), Int(st[])
+end
+
+function bfgs_get(e::HIPEngine; hinv::Bool = false)
+    θ = zeros(Float64, e.P); g = zeros(Float64, e.P); f = Ref{Float64}(0.0)
+    H = hinv ? zeros(Float64, e.P, e.P) : zeros(Float64, 0, 0)
+    GC.@preserve θ g H check(ccall(sym(:pinn_bfgs_get), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}, Ptr{Float64}, Ptr{Float64}),
+        e.h, θ, e.P, f, g, hinv ? pointer(H) : Ptr{Float64}(C_NULL)), "pinn_bfgs_get")
+    return θ, f[], g, hinv ? H : nothing
+end
+
+function bfgs_resident!(e::HIPEngine, θ::AbstractVector{<:Real}; maxiters::Integer, gtol::Real = 1e-8, weights = nothing)
+    bfgs_init(e, θ; weights = weights)
+    hist, _, _ = bfgs_steps(e, maxiters; gtol = gtol)
+    θ .= bfgs_get(e)[1]
+    return θ, hist
+end
+
 # ------------------------------------------------------------------------------------------------
 # 1. s-expression printer of the Julia Expr trees `toexpr` returns
 # ------------------------------------------------------------------------------------------------

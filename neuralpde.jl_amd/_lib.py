@@ -40,6 +40,7 @@ SYMBOLS = [
     "pinn_loss_grad_sharded_device_f64", "pinn_loss_grad_sharded_f64",
     "pinn_hmc_init", "pinn_hmc_set_metric", "pinn_hmc_draws", "pinn_hmc_get", "pinn_hmc_find_stepsize", "pinn_hmc_warmup",
     "pinn_lbfgs_init", "pinn_lbfgs_steps", "pinn_lbfgs_get",
+    "pinn_bfgs_init", "pinn_bfgs_steps", "pinn_bfgs_get",
     "pinn_phi_ensemble", "pinn_derivative_ensemble",
 ]
 
@@ -130,6 +131,12 @@ class Library:
             L.pinn_lbfgs_init.argtypes = [vp, dp, C.c_int64, C.c_int, fp]
             L.pinn_lbfgs_steps.argtypes = [vp, C.c_int, C.c_int, C.c_double, dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
             L.pinn_lbfgs_get.argtypes = [vp, dp, C.c_int64, dp, dp]
+        except AttributeError:
+            pass
+        try:                                     # (resident BFGS: variant libraries built before it still load)
+            L.pinn_bfgs_init.argtypes = [vp, dp, C.c_int64, fp]
+            L.pinn_bfgs_steps.argtypes = [vp, C.c_int, C.c_int, C.c_double, dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.pinn_bfgs_get.argtypes = [vp, dp, C.c_int64, dp, dp, dp]
         except AttributeError:
             pass
         try:                                     # (ensemble prediction: variant libraries built before it still load)
@@ -620,6 +627,37 @@ class Engine:
         f, dp = C.c_double(), C.POINTER(C.c_double)
         self.L.check(self.L.lib.pinn_lbfgs_get(self.h, th.ctypes.data_as(dp), th.size, C.byref(f), g.ctypes.data_as(dp) if g is not None else None), "pinn_lbfgs_get")
         return th, f.value, g
+
+    # ---- resident BFGS (include/pinn_hip.h: pinn_bfgs_init / _steps / _get) ----
+    BFGS_STATUS = LBFGS_STATUS
+
+    def bfgs_init(self, theta, weights=None):
+        """`pinn_bfgs_init`: put the device-resident dense BFGS state at theta with H = I; the term weights are fixed here."""
+        th = _f64(theta)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32)) if weights is not None else None
+        self.L.check(self.L.lib.pinn_bfgs_init(self.h, th.ctypes.data_as(C.POINTER(C.c_double)), th.size,
+                                               w.ctypes.data_as(C.POINTER(C.c_float)) if w is not None else None), "pinn_bfgs_init")
+
+    def bfgs_steps(self, maxiters: int, max_evals: int = None, gtol: float = 1e-8):
+        """`pinn_bfgs_steps`: at most `maxiters` further iterations / `max_evals` further trial evaluations (default: 31 per iteration, which
+        never binds) from the stored state.  Returns (objective after every performed iteration, evaluations, status name)."""
+        hist = np.zeros(max(int(maxiters), 1), dtype=np.float64)
+        it, ev, st = C.c_int(0), C.c_int(0), C.c_int(0)
+        me = 31 * max(int(maxiters), 1) if max_evals is None else int(max_evals)
+        self.L.check(self.L.lib.pinn_bfgs_steps(self.h, int(maxiters), me, float(gtol), hist.ctypes.data_as(C.POINTER(C.c_double)),
+                                                C.byref(it), C.byref(ev), C.byref(st)), "pinn_bfgs_steps")
+        return hist[:it.value], ev.value, self.BFGS_STATUS[st.value]
+
+    def bfgs_get(self, want_grad: bool = True, want_hinv: bool = False):
+        """`pinn_bfgs_get`: (theta, objective, gradient, inverse-Hessian approximation [P, P]) of the current iterate; what was not asked
+        for is None"""
+        th = np.zeros(self.P, dtype=np.float64)
+        g = np.zeros(self.P, dtype=np.float64) if want_grad else None
+        hinv = np.zeros((self.P, self.P), dtype=np.float64) if want_hinv else None
+        f, dp = C.c_double(), C.POINTER(C.c_double)
+        self.L.check(self.L.lib.pinn_bfgs_get(self.h, th.ctypes.data_as(dp), th.size, C.byref(f), g.ctypes.data_as(dp) if g is not None else None,
+                                              hinv.ctypes.data_as(dp) if hinv is not None else None), "pinn_bfgs_get")
+        return th, f.value, g, hinv
 
     # ---- resident HMC (include/pinn_hip.h: pinn_hmc_*) ----
     def hmc_init(self, theta, stds, nn_prior=(0.0, 2.0), param_priors=()):

@@ -541,6 +541,7 @@ int pinn_destroy(pinn_handle h) {
     plat_sync(E.stream);
     hmc_free(E);
     lbfgs_free(E);
+    bfgs_free(E);
     ens_free(E);
     f64_destroy(E);
     free_plan(E);
@@ -1318,7 +1319,8 @@ int pinn_describe(pinn_handle h, char* buf, int64_t buflen) {
     std::ostringstream os;
     os << "backend=" << plat_name() << " cus=" << h->ncu << " ntheta=" << h->ntheta << " terms=" << h->terms.size()
        << (h->f64 ? " precision=f64 (pinn_loss_grad*, pinn_lbfgs evaluate in double — matrix-pipe tile kernels where instantiated, one lane per point elsewhere; the plan below serves the fp32 entry points)" + pe::f64_describe(*h) : std::string())
-       << (h->lbfgs ? " lbfgs=resident(history=" + std::to_string(h->lbfgs_history) + ",chunk=" + std::to_string(h->lbfgs_chunk) + ")" : std::string()) << "\n";
+       << (h->lbfgs ? " lbfgs=resident(history=" + std::to_string(h->lbfgs_history) + ",chunk=" + std::to_string(h->lbfgs_chunk) + ")" : std::string())
+       << (h->bfgs ? " bfgs=resident(P=" + std::to_string(pe::bfgs_params(*h)) + ",chunk=" + std::to_string(h->lbfgs_chunk) + ")" : std::string()) << "\n";
     for (size_t n = 0; n < h->netplans.size(); ++n)
         if (h->netplans[n].spec && h->netplans[n].spec->family != 3)
             os << "net " << n << " weights=packed image (k_pack per evaluation)"

@@ -228,6 +228,7 @@ struct NetPlan {
 };
 struct HmcState;                     // hmc.cpp
 struct LbfgsState;                   // lbfgs.cpp
+struct BfgsState;                    // bfgs.cpp
 struct EnsState;                     // ensemble.cpp
 
 }  // namespace pe
@@ -326,7 +327,8 @@ struct pinn_engine {
     pe::HmcState* hmc = nullptr;     // resident HMC sampler state (hmc.cpp; pinn_hmc_init), nullptr = none
     pe::LbfgsState* lbfgs = nullptr; // resident L-BFGS state (lbfgs.cpp; pinn_lbfgs_init), nullptr = none
     int lbfgs_history = 0;           // its history length (pinn_describe)
-    int lbfgs_chunk = 8;             // option "lbfgs_chunk": slots pinn_lbfgs_steps queues between two downloads of the control block, 1..64
+    int lbfgs_chunk = 8;             // option "lbfgs_chunk": slots pinn_lbfgs_steps / pinn_bfgs_steps queue between two downloads of the control block, 1..64
+    pe::BfgsState* bfgs = nullptr;   // resident dense BFGS state (bfgs.cpp; pinn_bfgs_init), nullptr = none
     pe::EnsState* ens = nullptr;     // buffers of pinn_phi_ensemble (ensemble.cpp), nullptr = none yet
 };
 
@@ -402,9 +404,11 @@ public:
     }
 };
 template <class V, class T> As<V, T> as(T* x, size_t n) { return As<V, T>(x, n); }
-// hmc.cpp, lbfgs.cpp, ensemble.cpp: release the handle's resident solver state / ensemble buffers (nothing to do when there is none)
+// hmc.cpp, lbfgs.cpp, bfgs.cpp, ensemble.cpp: release the handle's resident solver state / ensemble buffers (nothing to do when there is none)
 void hmc_free(pinn_engine& E);
 void lbfgs_free(pinn_engine& E);
+void bfgs_free(pinn_engine& E);
+int bfgs_params(const pinn_engine& E);          // P of the resident BFGS state (pinn_describe), 0 = none
 void ens_free(pinn_engine& E);
 // ensemble.cpp: of the last pinn_derivative_ensemble call — 0: jet passes, 1: point passes, 2: jet passes on the scratch storage (0 before any call)
 int ens_counter(const pinn_engine& E, int which);

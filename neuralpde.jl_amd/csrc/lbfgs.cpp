@@ -1,42 +1,9 @@
 // lbfgs.cpp — the L-BFGS finishers of the C ABI: pinn_lbfgs (iteration on the host, evaluations on the device) and the resident loop
-// pinn_lbfgs_init / _steps / _get, with the noise-floor switch both share.
+// pinn_lbfgs_init / _steps / _get.  Both use the noise-floor switch of resident.hpp (GemmFloorSwitch).
 #include "resident.hpp"
 #include "lbfgs_kernels.hpp"
 
 using namespace pe;
-
-namespace {
-
-// The noise-floor switch of the L-BFGS routines (pinn_lbfgs, pinn_lbfgs_steps).  A line search that cannot decrease the objective along a descent
-// direction has reached the evaluation's noise floor; the split-operand GEMMs' floor is 2-4 x that of the fp32 MFMA kernels:
-// a handle in "split" mode is switched to them once per call and goes on from the same iterate.  The switch only changes arithmetic where a launch
-// group runs a family-2 kernel that exists as a split / fp32 twin; $PINN_LBFGS_KEEP_GEMM disables it; every exit path hands the handle back in the
-// mode it came in.
-struct GemmFloorSwitch {
-    pinn_engine& E;
-    bool switched = false, armed = false, has_twin = false;
-    explicit GemmFloorSwitch(pinn_engine& e) : E(e) {
-        for (const NetPlan& NP : E.netplans) has_twin = has_twin || (NP.spec && NP.spec->family == 2 && NP.spec->twin);
-    }
-    ~GemmFloorSwitch() { if (armed && E.gemm != pk::GEMM_SPLIT) { const std::string keep = g_err; replan_gemm(E, pk::GEMM_SPLIT); if (!keep.empty()) g_err = keep; } }
-    bool eligible() const { return !E.f64 && E.gemm == pk::GEMM_SPLIT && !switched && has_twin && std::getenv("PINN_LBFGS_KEEP_GEMM") == nullptr; }
-    // 0: done, `switched` says whether the handle now runs the fp32 kernels; 1: error; 2: the switch failed (the fp32 twin of a run-time specialised
-    // shape did not compile) and left the handle in split mode — replan_gemm restored the plan: the iterate reached so far is the answer, not an
-    // error
-    int engage() {
-        if (replan_gemm(E, pk::GEMM_FP32)) { if (E.gemm != pk::GEMM_SPLIT || E.groups.empty()) return 1; g_err.clear(); return 2; }
-        switched = E.gemm == pk::GEMM_FP32;
-        armed = switched;
-        return 0;
-    }
-    int finish() {                                       // the regular end of a call
-        if (!switched) return 0;
-        armed = false;
-        return replan_gemm(E, pk::GEMM_SPLIT) ? 1 : 0;
-    }
-};
-
-}  // namespace
 
 extern "C" {
 

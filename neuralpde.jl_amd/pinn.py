@@ -346,8 +346,12 @@ class Adam:
 class BFGS:
     """[3P] OptimizationOptimJL.BFGS() — the quasi-Newton finisher of the reference's tests (e.g. test/NNPDE1/nnpde__pde_ii_2d_poisson.jl:86).
     Mirror: scipy's BFGS on the HOST over the engine's fused `value_and_grad` (one device evaluation per objective call, float64 iterates,
-    fp32 evaluation); needs a fixed objective, i.e. fixed point sets — as the reference's own comments require (`resampling = false`)."""
+    fp32 evaluation); needs a fixed objective, i.e. fixed point sets — as the reference's own comments require (`resampling = false`).
+    `resident=True` (opt-in) runs the library's own dense BFGS with the iterate, the inverse-Hessian approximation and the line search on the
+    device (pinn_bfgs_init / pinn_bfgs_steps): no callback, no additional_loss, fixed weights — a ValueError names the condition that is
+    not met; this path never falls back to the host."""
     gtol: float = 1e-8
+    resident: bool = False
 
 
 @dataclass
@@ -458,6 +462,20 @@ def _host_quasi_newton(prob: OptimizationProblem, alg, maxiters: int, callback) 
             theta, hist = rep.engine.lbfgs(prob.u0, int(maxiters), rep._weights_now(), history=alg.m, gtol=alg.gtol)
         rep.iteration[0] += len(hist)
         final = float(hist[-1]) if len(hist) else float(prob.f.value_and_grad(np.asarray(prob.u0, dtype=np.float64))[0])
+        return OptimizationSolution(theta.astype(prob.u0.dtype), final, hist if len(hist) else np.array([final]))
+    if isinstance(alg, BFGS) and alg.resident:
+        # the library's own dense BFGS on the device (pinn_bfgs_init / pinn_bfgs_steps); never the host routine in its place
+        for unmet, why in ((callback is not None, "a callback needs the iterate on the host after every iteration"),
+                           (rep.additional_loss is not None, "additional_loss is a host function"),
+                           (rep.adaloss.reweight_every > 0, "adaptive reweighting changes the objective between iterations")):
+            if unmet:
+                raise ValueError(f"BFGS(resident=True): {why}; the resident loop needs no callback, no additional_loss and fixed weights "
+                                 "(use BFGS() for the host routine)")
+        rep.engine.bfgs_init(prob.u0, rep._weights_now())
+        hist = rep.engine.bfgs_steps(int(maxiters), gtol=alg.gtol)[0]
+        theta = rep.engine.bfgs_get(want_grad=False)[0]
+        rep.iteration[0] += len(hist)
+        final = float(hist[-1]) if len(hist) else float(rep.engine.bfgs_get(want_grad=False)[1])
         return OptimizationSolution(theta.astype(prob.u0.dtype), final, hist if len(hist) else np.array([final]))
     losses, it, last = [], [0], [None]
 
