@@ -427,6 +427,38 @@ int pinn_bfgs_steps(pinn_handle h, int maxiters, int max_evals, double gtol, dou
 int pinn_bfgs_get(pinn_handle h, double* theta, int64_t p, double* f, double* grad, double* hinv);
 
 /*
+ * ADAPTIVE CUBATURE: the reference's QuadratureTraining contract — a term's loss is (1 / area) int r^2 dx, integrated
+ * adaptively to reltol / abstol (src/training_strategies.jl:396-481) — as an h-adaptive refinement resident on the device.  Opt-in; nothing else
+ * changes.  At the given theta (p doubles; narrowed to float on an fp32 handle) the box [lb, ub] (d doubles each; a coordinate with lb == ub is
+ * held fixed at that value, 1..4 coordinates are free) is covered by a list of axis-aligned boxes.  Every new box is evaluated with the
+ * Genz-Malik degree-7 rule and its embedded degree-5 rule through the term's own residual kernel (7 / 17 / 33 / 57 nodes for 1..4 free axes):
+ * I7 and I5 as fractions of the mean, err = |I7 - I5|.  Per round I = sum I7, E = sum err, tau = max(abstol, reltol |I|); the refinement ends when
+ * E <= tau, otherwise every box with err > tau vol(box) / vol(domain) is bisected along its axis of largest fourth difference, all in one batch.
+ *   *status  0 converged; 1 the next split would exceed max_regions (the mesh before that split is kept); 2 max_rounds splits were made; 3 I or E is not finite
+ *            (a NaN / Inf residual at this theta: the mesh as it stands is emitted, nothing was compared).
+ *   *integral, *error  I and E of the last round; *nregions the boxes; *rounds the splits made; every output pointer is nullable.
+ * In every case the call then installs, as the term's point set, the tensor Gauss-Legendre rule with `nodes` (1..8) nodes per free axis on every
+ * box of the final mesh (*npoints = nregions x nodes^free points, box after box, the first free axis fastest) with per-point weights
+ * w = vol(box) / vol(domain) x the rule's weights (they sum to 1): exactly the state pinn_set_points[_f64](n_norm = npoints) followed by
+ * pinn_set_point_weights(float(w)) leaves.  Every evaluation, optimiser and pinn_term_grads then works on that set unchanged; its gradient is that of
+ * the emitted quadrature value on the mesh frozen at this theta.  Region list, nodes, estimates, decisions and the emitted set stay on the device;
+ * the host reads one 40-byte record per round.  While the call runs the term's point buffer holds the rule's nodes: after a call that fails
+ * half-way (a device allocation) install a point set before the next evaluation.
+ * With pinn_set_timing level 2, pinn_get_option(h, "cub_ms") = six times in ms of the last call, from HIP events at the phase boundaries, summed
+ * over its rounds: node generation (+ the installed node set's bookkeeping), evaluation, estimate, plan + read-back, split, emit.
+ *   pinn_cubature_get  the final mesh of the term's last refinement: boxes [nregions][2][d] (lo, then hi; fixed coordinates repeat their value) and
+ *                      est [nregions][2] (I7, err of each box); either may be NULL.  The list stays until the next refinement of the term.
+ * Refused, with the handle left as it was: a term with a device sampler; integral terms; terms with per-point data channels; terms behind a periodic
+ * embedding; the stencil derivative mode; a handle on a communicator; lb > ub; d != the term's coordinates; zero free axes (more than 4 cannot occur: a term has at most 4 coordinates); nodes
+ * outside 1..8; a negative tolerance; max_regions < 1; max_rounds < 0; max_regions x points per box beyond 32-bit indexing; p != ntheta;
+ * pinn_cubature_get before a refinement of the term, or with another nregions.
+ */
+int pinn_cubature_refine(pinn_handle h, int term, const double* theta, int64_t p, const double* lb, const double* ub, int d, double reltol, double abstol,
+                         int max_regions, int max_rounds, int nodes, double* integral, double* error, int64_t* nregions, int64_t* npoints, int* rounds,
+                         int* status);
+int pinn_cubature_get(pinn_handle h, int term, double* boxes, double* est, int64_t nregions);
+
+/*
  * ENSEMBLE PREDICTION: the trial function of network `net` at `nsamples` parameter vectors and n points, and the mean and
  * standard deviation over the samples at every point, in one call — the prediction stage of a Bayesian PINN (ext/bpinn/PDE_BPINN.jl:254-302),
  * deep-ensemble or checkpoint prediction.  Opt-in: pinn_phi / pinn_phi_f64 are unchanged.

@@ -506,6 +506,37 @@ function bfgs_resident!(e::HIPEngine, θ::AbstractVector{<:Real}; maxiters::Inte
     return θ, hist
 end
 
+"""
+    cubature_refine(e, term, θ, lb, ub; reltol = 1e-6, abstol = 1e-3, max_regions = 4096, max_rounds = 32, nodes = 4)
+        -> (integral, error, nregions, npoints, rounds, status)
+    cubature_get(e, term, nregions, d) -> (boxes, est)
+
+Adaptive cubature on the device (`pinn_cubature_refine / _get`, DESIGN.md §4.13): `QuadratureTraining`'s contract, the loss of term `term` (0-based)
+as (1 / area) ∫ r² dx integrated h-adaptively to `reltol` / `abstol` at θ over the box `[lb, ub]` (a coordinate with `lb == ub` is held fixed).  The
+call installs the composite Gauss-Legendre rule (`nodes` per free axis per box) on the final mesh as the term's weighted point set; `loss_grad`, the
+resident optimisers and `term_grads` then run on it unchanged.  `status`: 0 converged, 1 `max_regions` reached, 2 `max_rounds` reached, 3 integrand not finite.
+`cubature_get` returns the final mesh, `boxes[:, 1, i]` / `boxes[:, 2, i]` the lower / upper corner of box i (d × 2 × nregions in Julia's order),
+and `est[:, i]` = (I7, err) of box i.
+"""
+function cubature_refine(e::HIPEngine, term::Integer, θ::AbstractVector{<:Real}, lb::AbstractVector{<:Real}, ub::AbstractVector{<:Real};
+                         reltol::Real = 1e-6, abstol::Real = 1e-3, max_regions::Integer = 4096, max_rounds::Integer = 32, nodes::Integer = 4)
+    θ64 = Vector{Float64}(θ); lo = Vector{Float64}(lb); hi = Vector{Float64}(ub)
+    length(lo) == length(hi) || error("cubature_refine: lb and ub take one value per coordinate each")
+    I = Ref{Float64}(0.0); E = Ref{Float64}(0.0); nr = Ref{Int64}(0); np = Ref{Int64}(0); rd = Ref{Cint}(0); st = Ref{Cint}(0)
+    GC.@preserve θ64 lo hi check(ccall(sym(:pinn_cubature_refine), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Cint, Cdouble, Cdouble, Cint, Cint, Cint,
+         Ref{Float64}, Ref{Float64}, Ref{Int64}, Ref{Int64}, Ref{Cint}, Ref{Cint}),
+        e.h, term, θ64, e.P, lo, hi, length(lo), Float64(reltol), Float64(abstol), max_regions, max_rounds, nodes, I, E, nr, np, rd, st), "pinn_cubature_refine")
+    return I[], E[], Int(nr[]), Int(np[]), Int(rd[]), Int(st[])
+end
+
+function cubature_get(e::HIPEngine, term::Integer, nregions::Integer, d::Integer)
+    boxes = zeros(Float64, d, 2, nregions); est = zeros(Float64, 2, nregions)
+    GC.@preserve boxes est check(ccall(sym(:pinn_cubature_get), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Int64),
+        e.h, term, boxes, est, nregions), "pinn_cubature_get")
+    return boxes, est
+end
+
 # ------------------------------------------------------------------------------------------------
 # 1. s-expression printer of the Julia Expr trees `toexpr` returns
 # ------------------------------------------------------------------------------------------------

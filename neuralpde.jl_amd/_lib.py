@@ -42,6 +42,7 @@ SYMBOLS = [
     "pinn_lbfgs_init", "pinn_lbfgs_steps", "pinn_lbfgs_get",
     "pinn_bfgs_init", "pinn_bfgs_steps", "pinn_bfgs_get",
     "pinn_phi_ensemble", "pinn_derivative_ensemble",
+    "pinn_cubature_refine", "pinn_cubature_get",
 ]
 
 
@@ -145,6 +146,12 @@ class Library:
             pass
         try:                                     # (ensemble derivatives: variant libraries built before them still load)
             L.pinn_derivative_ensemble.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, dp, dp, dp]
+        except AttributeError:
+            pass
+        try:                                     # (adaptive cubature: variant libraries built before it still load)
+            L.pinn_cubature_refine.argtypes = [vp, C.c_int, dp, C.c_int64, dp, dp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                                               dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.pinn_cubature_get.argtypes = [vp, C.c_int, dp, dp, C.c_int64]
         except AttributeError:
             pass
         L.pinn_lbfgs.argtypes = [vp, C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_double, fp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -658,6 +665,30 @@ class Engine:
         self.L.check(self.L.lib.pinn_bfgs_get(self.h, th.ctypes.data_as(dp), th.size, C.byref(f), g.ctypes.data_as(dp) if g is not None else None,
                                               hinv.ctypes.data_as(dp) if hinv is not None else None), "pinn_bfgs_get")
         return th, f.value, g, hinv
+
+    # ---- adaptive cubature (include/pinn_hip.h: pinn_cubature_refine / _get) ----
+    CUBATURE_STATUS = ("CONVERGED", "MAX_REGIONS", "MAX_ROUNDS", "NONFINITE")
+
+    def cubature_refine(self, term: int, theta, lb, ub, reltol: float = 1e-6, abstol: float = 1e-3, max_regions: int = 4096, max_rounds: int = 32,
+                        nodes: int = 4):
+        """`pinn_cubature_refine`: refine term `term`'s mesh over [lb, ub] at theta on the device and install the composite Gauss-Legendre rule
+        (`nodes` per free axis per box) as its weighted point set.  Returns dict(integral, error, nregions, npoints, rounds, status)."""
+        th, lo, hi = _f64(theta), _f64(lb).reshape(-1), _f64(ub).reshape(-1)
+        if lo.size != hi.size:
+            raise ValueError("lb and ub: one value per coordinate each")
+        dp = C.POINTER(C.c_double)
+        I, Er, nr, npts, rd, st = C.c_double(), C.c_double(), C.c_int64(), C.c_int64(), C.c_int(), C.c_int()
+        self.L.check(self.L.lib.pinn_cubature_refine(self.h, int(term), th.ctypes.data_as(dp), th.size, lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), lo.size,
+                                                     float(reltol), float(abstol), int(max_regions), int(max_rounds), int(nodes), C.byref(I), C.byref(Er),
+                                                     C.byref(nr), C.byref(npts), C.byref(rd), C.byref(st)), "pinn_cubature_refine")
+        return dict(integral=I.value, error=Er.value, nregions=nr.value, npoints=npts.value, rounds=rd.value, status=st.value)
+
+    def cubature_get(self, term: int, nregions: int, d: int):
+        """`pinn_cubature_get`: (boxes [nregions, 2, d] — lo, hi —, est [nregions, 2] — I7, err) of the term's last refinement"""
+        boxes, est = np.zeros((int(nregions), 2, int(d)), dtype=np.float64), np.zeros((int(nregions), 2), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        self.L.check(self.L.lib.pinn_cubature_get(self.h, int(term), boxes.ctypes.data_as(dp), est.ctypes.data_as(dp), int(nregions)), "pinn_cubature_get")
+        return boxes, est
 
     # ---- resident HMC (include/pinn_hip.h: pinn_hmc_*) ----
     def hmc_init(self, theta, stds, nn_prior=(0.0, 2.0), param_priors=()):

@@ -543,6 +543,7 @@ int pinn_destroy(pinn_handle h) {
     lbfgs_free(E);
     bfgs_free(E);
     ens_free(E);
+    cub_free(E);
     f64_destroy(E);
     free_plan(E);
     for (auto& T : E.terms) { plat_free(T.d_pts); plat_free(T.d_upts); plat_free(T.d_resid); plat_free(T.d_lb); plat_free(T.d_ub); plat_free(T.d_data); plat_free(T.d_pw); }
@@ -577,6 +578,16 @@ static int set_points_impl(pinn_handle h, int term, const float* pts, int64_t n,
         return fail("pinn_set_points: the site set of integral term " + std::to_string(term) + " (" + std::to_string(n) + " points x (1 + " +
                     std::to_string(T.inodes.size()) + " integral node(s) x " + std::to_string(T.int_q) + " quadrature nodes) = " + std::to_string(n * S) +
                     " sites) exceeds what one launch group takes (32-bit indexing of its jet channels); shard the point set or lower integral_nodes");
+    if (points_reserve(E, term, n)) return 1;
+    int rc = device ? plat_d2d(user_pts(T), pts, sizeof(float) * n * T.d_user, E.stream) : plat_h2d(user_pts(T), pts, sizeof(float) * n * T.d_user, E.stream);
+    if (rc) return fail(std::string("copy of points failed: ") + plat_last_error());
+    if (points_written(E, term, n, n_norm)) return 1;
+    return f64_points_changed(E, term);                  // (float64 mode: the double copy follows)
+}
+// room for n points in the term's point buffer (the contents do not survive a growth)
+extern "C++" int pe::points_reserve(pinn_engine& E, int term, int64_t n) {
+    Term& T = E.terms[term];
+    const int64_t S = T.sites();
     if (n > T.pts_cap || !T.d_pts) {                     // grow only: a resampled set of another size reuses the buffer
         plat_sync(E.stream);                             // (an evaluation in flight may still read the old buffer)
         plat_free(T.d_pts);
@@ -588,16 +599,19 @@ static int set_points_impl(pinn_handle h, int term, const float* pts, int64_t n,
         if (!T.d_pts || (!T.emb_cols.empty() && !T.d_upts)) return fail("device allocation failed (points)");
         T.pts_cap = n;
     }
-    int rc = device ? plat_d2d(user_pts(T), pts, sizeof(float) * n * T.d_user, E.stream) : plat_h2d(user_pts(T), pts, sizeof(float) * n * T.d_user, E.stream);
-    if (rc) return fail(std::string("copy of points failed: ") + plat_last_error());
+    return 0;
+}
+// the term's point buffer holds a new set of n points (a copy, or a kernel's stores queued on the stream): the bookkeeping that follows.  The
+// double copy of the float64 mode is the caller's
+extern "C++" int pe::points_written(pinn_engine& E, int term, int64_t n, int64_t n_norm) {
+    Term& T = E.terms[term];
     T.n = n;
     embed_points(E, T);
     plat_sync(E.stream);
     T.n_norm = n_norm > 0 ? n_norm : n;
     T.data_n = 0;                                        // per-point data and weights belong to the previous set
     T.pw_n = 0;
-    if (term_installed(E, term)) return 1;
-    return f64_points_changed(E, term);                  // (float64 mode: the double copy follows)
+    return term_installed(E, term);
 }
 
 // what follows the installation of a term's point set (also after a re-plan, pinn_set_option): source channels, tile tables, the buffers of
@@ -835,6 +849,17 @@ static int residual_f32(pinn_engine& E, int term, const float* theta, float* r) 
     if (upload_theta(E, theta, E.ntheta)) return 1;
     pack_all(E);
     jit_take_launch_error();                             // (a stale message of an earlier call must not fail this one)
+    if (residual_device(E, term)) return 1;
+    if (plat_d2h(r, T.d_resid, sizeof(float) * T.n, E.stream)) return fail("D2H copy failed");
+    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    // a run-time specialised kernel whose (mode, activation) member could not be compiled at this, its first, launch leaves r unwritten (ADVICE r05)
+    { const std::string le = jit_take_launch_error(); if (!le.empty()) return fail("pinn_residual: " + le); }
+    return 0;
+}
+// its device part: the term's residual at every point of its installed set into T.d_resid, with the parameters the packed weight images hold; queued
+// on the stream, nothing is downloaded
+extern "C++" int pe::residual_device(pinn_engine& E, int term) {
+    Term& T = E.terms[term];
     if (T.resid_cap < T.n) {
         plat_free(T.d_resid);
         T.d_resid = (float*)plat_malloc(sizeof(float) * T.n);
@@ -856,9 +881,6 @@ static int residual_f32(pinn_engine& E, int term, const float* theta, float* r) 
         }
         if (!T.inodes.empty()) aux::launch_int_expr(int_expr_args(E, Cp, 0.f, T.d_resid), Cp.blocks, E.stream);
         else aux::launch_expr(expr_args(E, Cp, 0.f, T.d_resid), Cp.blocks, E.stream);
-        if (plat_d2h(r, T.d_resid, sizeof(float) * T.n, E.stream)) return fail("D2H copy failed");
-        if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-        { const std::string le = jit_take_launch_error(); if (!le.empty()) return fail("pinn_residual: " + le); }
         return 0;
     }
     Group& G = E.groups[T.group];
@@ -870,10 +892,6 @@ static int residual_f32(pinn_engine& E, int term, const float* theta, float* r) 
     ga.ntiles = ga.terms[0].ntiles;
     const int blocks = std::max(1, std::min(E.ncu * G.spec->WG_FWD, G.spec->family == 1 ? (ga.ntiles + 3) / 4 : ga.ntiles));
     G.spec->launch(ga, pk::MODE_RESID, blocks, E.stream);
-    if (plat_d2h(r, T.d_resid, sizeof(float) * T.n, E.stream)) return fail("D2H copy failed");
-    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-    // a run-time specialised kernel whose (mode, activation) member could not be compiled at this, its first, launch leaves r unwritten (ADVICE r05)
-    { const std::string le = jit_take_launch_error(); if (!le.empty()) return fail("pinn_residual: " + le); }
     return 0;
 }
 
@@ -1032,9 +1050,7 @@ int pinn_set_point_weights(pinn_handle h, int term, const float* w, int64_t n) {
     if (term < 0 || term >= (int)E.terms.size()) return fail("pinn_set_point_weights: term index out of range");
     Term& T = E.terms[term];
     plat_sync(E.stream);
-    if (!w) {                                            // back to the plain mean
-        T.pw_n = 0;
-    } else {
+    if (w) {
         if (!T.d_pts || n != T.n) return fail("pinn_set_point_weights: the term holds " + std::to_string(T.n) + " points (install the point set first)");
         if (T.sampler != 0) return fail("pinn_set_point_weights: weights cannot follow a resampled point set");
         std::vector<float> s((size_t)n);
@@ -1042,19 +1058,29 @@ int pinn_set_point_weights(pinn_handle h, int term, const float* w, int64_t n) {
             if (!(w[i] >= 0.f)) return fail("pinn_set_point_weights: weights must be non-negative");
             s[i] = (float)std::sqrt((double)w[i] * (double)T.n_norm);
         }
-        if (T.pw_cap < n) {
-            plat_free(T.d_pw);
-            T.d_pw = (float*)plat_malloc(sizeof(float) * (size_t)n);
-            if (!T.d_pw) return fail("device allocation failed (point weights)");
-            T.pw_cap = n;
-        }
+        if (weights_reserve(E, term, n)) return 1;
         if (plat_h2d(T.d_pw, s.data(), sizeof(float) * (size_t)n, E.stream)) return fail("H2D copy of point weights failed");
         if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-        T.pw_n = n;
     }
+    weights_written(E, term, w ? n : 0);
+    return 0;
+}
+extern "C++" int pe::weights_reserve(pinn_engine& E, int term, int64_t n) {
+    Term& T = E.terms[term];
+    if (T.pw_cap < n) {
+        plat_free(T.d_pw);
+        T.d_pw = (float*)plat_malloc(sizeof(float) * (size_t)n);
+        if (!T.d_pw) { T.pw_cap = 0; return fail("device allocation failed (point weights)"); }
+        T.pw_cap = n;
+    }
+    return 0;
+}
+// the term's weight buffer holds the factors of its current n points (n == 0: back to the plain mean)
+extern "C++" void pe::weights_written(pinn_engine& E, int term, int64_t n) {
+    Term& T = E.terms[term];
+    T.pw_n = n;
     if (T.coupled < 0) retile(E, T.group);
     else for (int gi : E.coupled[T.coupled].groups) retile(E, gi);
-    return 0;
 }
 
 int pinn_get_points(pinn_handle h, int term, float* pts, int64_t n) {
@@ -1250,7 +1276,12 @@ int pinn_get_option(pinn_handle h, const char* name, char* buf, int64_t buflen) 
     if (k == "ens_passes") { std::snprintf(buf, (size_t)buflen, "%d", pe::ens_counter(*h, 0)); return 0; }            // jet passes of the last pinn_derivative_ensemble call
     if (k == "ens_point_passes") { std::snprintf(buf, (size_t)buflen, "%d", pe::ens_counter(*h, 1)); return 0; }      // ... its point passes
     if (k == "ens_scratch_passes") { std::snprintf(buf, (size_t)buflen, "%d", pe::ens_counter(*h, 2)); return 0; }    // ... its jet passes with the images in device scratch
-    return fail("pinn_get_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, lbfgs_chunk, grad_health, gemm_delta, adam_path, eval_path, f64_path, f64_merged, f64_chunks, f64_affine, ens_passes, ens_point_passes, ens_scratch_passes)");
+    if (k == "cub_ms") {     // phases of the last pinn_cubature_refine under pinn_set_timing level 2: nodes, evaluation, estimate, plan + read-back, split, emit (ms)
+        const float* ms = pe::cub_phase_ms(*h);
+        std::snprintf(buf, (size_t)buflen, "%.4f %.4f %.4f %.4f %.4f %.4f", ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
+        return 0;
+    }
+    return fail("pinn_get_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, lbfgs_chunk, grad_health, gemm_delta, adam_path, eval_path, f64_path, f64_merged, f64_chunks, f64_affine, ens_passes, ens_point_passes, ens_scratch_passes, cub_ms)");
 }
 
 int pinn_set_timing(pinn_handle h, int level, int group) {

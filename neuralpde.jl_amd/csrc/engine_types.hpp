@@ -230,6 +230,7 @@ struct HmcState;                     // hmc.cpp
 struct LbfgsState;                   // lbfgs.cpp
 struct BfgsState;                    // bfgs.cpp
 struct EnsState;                     // ensemble.cpp
+struct CubState;                     // cubature.cpp
 
 }  // namespace pe
 
@@ -330,6 +331,7 @@ struct pinn_engine {
     int lbfgs_chunk = 8;             // option "lbfgs_chunk": slots pinn_lbfgs_steps / pinn_bfgs_steps queue between two downloads of the control block, 1..64
     pe::BfgsState* bfgs = nullptr;   // resident dense BFGS state (bfgs.cpp; pinn_bfgs_init), nullptr = none
     pe::EnsState* ens = nullptr;     // buffers of pinn_phi_ensemble (ensemble.cpp), nullptr = none yet
+    pe::CubState* cub = nullptr;     // region lists of pinn_cubature_refine (cubature.cpp), nullptr = none yet
 };
 
 namespace pe {
@@ -353,6 +355,15 @@ int run_loss_grad(pinn_engine& E, const float* d_theta, float* d_out, const floa
 int upload_theta(pinn_engine& E, const float* theta, int64_t p);
 void sums_from_double(float* d_out_sums, const double* d_raw, int K, plat_stream st);      // (float)raw[k] -> out_sums[k], on the stream
 int ensure_points(pinn_engine& E);              // every term has its point set (and per-point data) installed, or the reason in g_err
+// the steps of pinn_set_points / pinn_set_point_weights / pinn_residual around their copies, for a unit whose kernels write a term's points and
+// weight factors on the device (cubature.cpp): room for n points; the bookkeeping after n points were written (sources, tile tables; per-point
+// data and weights of the previous set are dropped); room for n weight factors; the bookkeeping after they were written (n == 0: none); the
+// term's residual at its installed set into Term::d_resid with the uploaded, packed parameters — queued, nothing downloaded
+int points_reserve(pinn_engine& E, int term, int64_t n);
+int points_written(pinn_engine& E, int term, int64_t n, int64_t n_norm);
+int weights_reserve(pinn_engine& E, int term, int64_t n);
+void weights_written(pinn_engine& E, int term, int64_t n);
+int residual_device(pinn_engine& E, int term);
 // loss + gradient for a host entry point that synchronises right after: small problems in ONE launch (eval_fused), everything else by
 // run_loss_grad; results in d_out / lossraw either way.  Synchronises.
 int eval_and_sync(pinn_engine& E, float* d_out, const float* term_w, double* lossraw, bool timing);
@@ -410,6 +421,8 @@ void lbfgs_free(pinn_engine& E);
 void bfgs_free(pinn_engine& E);
 int bfgs_params(const pinn_engine& E);          // P of the resident BFGS state (pinn_describe), 0 = none
 void ens_free(pinn_engine& E);
+void cub_free(pinn_engine& E);
+const float* cub_phase_ms(const pinn_engine& E);      // cubature.cpp: [6] phase times of the last pinn_cubature_refine at timing level 2 (zeros otherwise)
 // ensemble.cpp: of the last pinn_derivative_ensemble call — 0: jet passes, 1: point passes, 2: jet passes on the scratch storage (0 before any call)
 int ens_counter(const pinn_engine& E, int which);
 // comm.cpp: sum vec[i] ([P + K] floats) and raw[i] (K doubles) of the ndev handles' ranks over their communicator, in place, each on its
@@ -436,6 +449,12 @@ int f64_set_points(pinn_engine& E, int term, const double* pts, int64_t n);
 int f64_set_point_data(pinn_engine& E, int term, const double* data);      // nullptr: convert the float rows just installed
 int f64_eval(pinn_engine& E, const double* theta, const double* term_w, double* term_losses, double* grad);
 int f64_residual(pinn_engine& E, int term, const double* theta, double* r);      // host theta, host r[n_term]
+// the same in pieces, for kernels that write a term's double point set on the device (cubature.cpp): the evaluation's parameters; room for n points
+// (the buffer); the bookkeeping after n points were written; the residual at the installed set, queued, *d_r the device array it lands in
+int f64_upload_theta(pinn_engine& E, const double* theta);
+double* f64_points_reserve(pinn_engine& E, int term, int64_t n);
+int f64_points_written(pinn_engine& E, int term, int64_t n);
+int f64_residual_device(pinn_engine& E, int term, const double** d_r);
 int f64_net_eval(pinn_engine& E, int net, const double* theta, const double* pts, int64_t n, int order, const int* axes, double* out);      // d^order phi_net / dx_axes at host points
 int f64_adam_apply(pinn_engine& E, const double* grad_and_sums, double lr, double beta1, double beta2, double eps, const float* term_w, double* loss);
 int f64_stencil_enable(pinn_engine& E, bool on);      // pinn_set_option "derivative" = "stencil" | "exact"

@@ -382,17 +382,32 @@ int f64_points_changed(pinn_engine& E, int term) {
     return f64_convert_points(E, S.terms[term], E.terms[term]);
 }
 
+double* f64_points_reserve(pinn_engine& E, int term, int64_t n) {
+    F64State& S = *(F64State*)E.f64;
+    F64Term& F = S.terms[term];
+    if (F.cap < n) {
+        plat_sync(E.stream);
+        plat_free(F.d_pts);
+        F.d_pts = (double*)plat_malloc(sizeof(double) * (size_t)n * E.terms[term].d);
+        if (!F.d_pts) { F.cap = 0; fail("device allocation failed (float64 points)"); return nullptr; }
+        F.cap = n;
+    }
+    return F.d_pts;
+}
+// the term's double point buffer holds a new set of n points, as given in double
+int f64_points_written(pinn_engine& E, int term, int64_t n) {
+    F64State& S = *(F64State*)E.f64;
+    F64Term& F = S.terms[term];
+    F.n = n;
+    F.exact_pts = true;
+    return f64_lin_install(E, F, E.terms[term]);
+}
+
 int f64_set_points(pinn_engine& E, int term, const double* pts, int64_t n) {
     F64State& S = *(F64State*)E.f64;
     F64Term& F = S.terms[term];
     const Term& T = E.terms[term];
-    if (F.cap < n) {
-        plat_sync(E.stream);
-        plat_free(F.d_pts);
-        F.d_pts = (double*)plat_malloc(sizeof(double) * (size_t)n * T.d);
-        if (!F.d_pts) { F.cap = 0; return fail("device allocation failed (float64 points)"); }
-        F.cap = n;
-    }
+    if (!f64_points_reserve(E, term, n)) return 1;
     if (T.emb_cols.empty()) {
         if (plat_h2d(F.d_pts, pts, sizeof(double) * (size_t)n * T.d, E.stream) || plat_sync(E.stream)) return fail("H2D copy of points failed");
     } else {                                             // the caller's [n][d_user] coordinates + the feature rows
@@ -402,9 +417,7 @@ int f64_set_points(pinn_engine& E, int term, const double* pts, int64_t n) {
         f64_embed_host(T, hd, n);
         if (plat_h2d(F.d_pts, hd.data(), sizeof(double) * hd.size(), E.stream) || plat_sync(E.stream)) return fail("H2D copy of points failed");
     }
-    F.n = n;
-    F.exact_pts = true;
-    return f64_lin_install(E, F, T);
+    return f64_points_written(E, term, n);
 }
 
 // pinn_set_point_data while the mode is on: the double rows follow (data == nullptr: converted from the float rows just installed)
@@ -1054,7 +1067,19 @@ int f64_residual(pinn_engine& E, int term, const double* theta, double* r) {
     F64Term& F = S.terms[term];
     if (F.n <= 0 || F.n != E.terms[term].n) return fail("pinn_residual: term has no points");
     if (F.ndata > 0 && F.data_n != F.n) return fail("pinn_residual: the term uses per-point data channels but none are installed for its current point set");
-    if (plat_h2d(S.d_theta, theta, sizeof(double) * E.ntheta, E.stream)) return fail("H2D copy of theta failed");
+    const double* d_r = nullptr;
+    if (f64_upload_theta(E, theta) || f64_residual_device(E, term, &d_r)) return 1;
+    if (plat_d2h(r, d_r, sizeof(double) * (size_t)F.n, E.stream) || plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    return 0;
+}
+int f64_upload_theta(pinn_engine& E, const double* theta) {
+    F64State& S = *(F64State*)E.f64;
+    return plat_h2d(S.d_theta, theta, sizeof(double) * E.ntheta, E.stream) ? fail("H2D copy of theta failed") : 0;
+}
+// its device part: the values-only launches over the term's double point set at the uploaded parameters, queued on the stream
+int f64_residual_device(pinn_engine& E, int term, const double** d_r) {
+    F64State& S = *(F64State*)E.f64;
+    F64Term& F = S.terms[term];
     if (!dev_grow(S.d_aux_out, S.aux_out_cap, (size_t)F.n, E.stream)) return fail("device allocation failed (float64 residuals)");
     S.path = 0;
     S.max_chunks = 0;
@@ -1067,7 +1092,7 @@ int f64_residual(pinn_engine& E, int term, const double* theta, double* r) {
         L.a.theta = S.d_theta;
         if (f64_values(E, S, F, L, F.n, S.d_aux_out)) return 1;
     }
-    if (plat_d2h(r, S.d_aux_out, sizeof(double) * (size_t)F.n, E.stream) || plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    *d_r = S.d_aux_out;
     return 0;
 }
 // d^order phi_net / dx_axes (order 0: the trial function itself) at n caller-supplied points (pinn_phi[_f64], pinn_derivative[_f64] in float64 mode;

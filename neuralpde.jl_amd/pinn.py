@@ -397,6 +397,10 @@ def solve(prob: OptimizationProblem, alg: Adam, maxiters: int = 1000, callback: 
     chunk = maxiters if callback is None else 50
     if ada.reweight_every > 0:                     # adaptive weights: reweight on the host between chunks of device steps
         chunk = min(chunk, ada.reweight_every)
+    refine = getattr(rep, "_refine", None)
+    refresh = int(getattr(rep.strategy, "refresh", 0)) if refine is not None else 0
+    if refresh > 0:                                # adaptive cubature: a new mesh at the iterate every `refresh` steps, between chunks as well
+        chunk = min(chunk, refresh)
     # precision = "f64": theta crosses the ABI in double (pinn_adam_init_f64 / pinn_adam_get_f64), so a chunked run continues from the
     # exact state; otherwise float32, the device dtype of the north star
     f64 = eng.get_option("precision") == "f64"
@@ -407,10 +411,14 @@ def solve(prob: OptimizationProblem, alg: Adam, maxiters: int = 1000, callback: 
         if ada.reweight_every > 0:                 # end the chunk where the iteration counter hits a multiple of reweight_every
             it = rep.iteration[0] + done
             n = min(n, ada.reweight_every - (it % ada.reweight_every))
+        if refresh > 0:
+            n = min(n, refresh - (done % refresh))
         th32, hist = step(th32, n, alg.eta, rep._weights_now(), alg.beta[0], alg.beta[1], alg.epsilon, init=init)
         init = False
         losses.append(hist)
         done += n
+        if refresh > 0 and done % refresh == 0:
+            refine(th32)
         if ada.reweight_every > 0:
             tl, _ = (eng.loss_grad_f64 if f64 else eng.loss_grad)(th32, None, want_grad=False)
             ada.reweight(th32, tl[:n_pde], tl[n_pde:n_pde + len(rep.bcs)], rep.iteration[0] + done,
@@ -451,6 +459,8 @@ def _host_quasi_newton(prob: OptimizationProblem, alg, maxiters: int, callback) 
     if getattr(rep, "_device_samplers", None) or rep._state.get("resample") is not None:
         raise ValueError("BFGS / LBFGS need a fixed objective: use GridTraining, QuadratureTraining or QuasiRandomTraining(...; resampling = false, "
                          "minibatch = 1) (the reference's tests say the same, e.g. test/NNPDE1/nnpde__pde_vi_pde_with_mixed_derivative.jl:76)")
+    if getattr(rep, "_refine", None) is not None:       # QuadratureTraining(adaptive = True): one mesh, at the start, for the whole run
+        rep._refine(prob.u0)
     if isinstance(alg, LBFGS) and callback is None and rep.additional_loss is None and rep.adaloss.reweight_every <= 0:
         # the library's own L-BFGS (pinn_lbfgs): same recursion, no Python in the loop; resident = True: the same iteration with the iterate,
         # the curvature pairs and the line search on the device (pinn_lbfgs_init / pinn_lbfgs_steps)
@@ -646,6 +656,23 @@ def symbolic_discretize(pde_system: PDESystem, discretization: PhysicsInformedNN
         (engine.set_point_data_f64 if f64 else engine.set_point_data)(n_pde + n_bc + j, np.asarray(dl.values, dtype=np.float64).reshape(1, -1))
     state = {"pde_sets": pde_sets, "bc_sets": bc_sets, "cache_theta": None, "cache": None, "resample": resample}
 
+    # QuadratureTraining(adaptive = True): the terms' sets come from the device refinement (pinn_cubature_refine) at a given theta; the fixed
+    # rule installed above only serves the terms without a free axis (point conditions)
+    adaptive = bool(getattr(strategy, "adaptive", False)) and getattr(strategy, "_bounds", None) is not None
+    cubature = {}
+
+    def refine(theta, count=True):
+        th = np.asarray(theta, dtype=np.float64)
+        for k, (lb, ub) in enumerate(strategy._bounds):
+            if np.any(ub > lb):
+                cubature[k] = engine.cubature_refine(k, th, lb, ub, reltol=strategy.reltol, abstol=strategy.abstol, max_regions=strategy.max_regions,
+                                                     max_rounds=strategy.max_rounds, nodes=strategy.nodes or 4)
+        state["cache_theta"], state["cub_theta"] = None, th.copy()
+        state["refines"] = state.get("refines", 0) + (1 if count else 0)
+
+    if adaptive:
+        refine(flat)
+
     adaloss = discretization.adaptive_loss or NonAdaptiveLoss()
     if not isinstance(adaloss, AbstractAdaptiveLoss):
         raise TypeError("adaptive_loss must be an AbstractAdaptiveLoss (src/adaptive_losses.jl)")
@@ -692,6 +719,8 @@ def symbolic_discretize(pde_system: PDESystem, discretization: PhysicsInformedNN
             if getattr(strategy, "point_weights", None) is not None and strategy.point_weights() is not None:
                 engine.set_point_weights(k, strategy.point_weights()[k])
             state["cache_theta"] = None
+            if adaptive:                                # (the emitted sets live on the device only: the same refinement again)
+                refine(state["cub_theta"], count=False)
             return r
         return f
 
@@ -787,6 +816,8 @@ def symbolic_discretize(pde_system: PDESystem, discretization: PhysicsInformedNN
             rep._device_samplers[k] = (lb, ub, strategy.points if k < n_pde else strategy.bcs_points, seed, kind)
     rep._state = state
     rep._pde_system, rep._vi = pde_system, vi
+    rep.cubature = cubature                             # QuadratureTraining(adaptive = True): per refined term, the last refinement's summary
+    rep._refine = refine if adaptive else None
     return rep
 
 

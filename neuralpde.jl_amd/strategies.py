@@ -200,12 +200,26 @@ class QuadratureTraining(AbstractTrainingStrategy):
     HCubatureJL by default) to `reltol`/`abstol`; here the integral is a FIXED tensor Gauss-Legendre rule with `nodes` points per free
     axis (default: 32 in 1-D, 24 in 2-D, 12 in 3-D, 8 in 4-D), evaluated with the other terms in one fused device call
     (`pinn_set_point_weights`).  Same objective, different (non-adaptive) quadrature error; `quadrature_alg`, `reltol`, `abstol`,
-    `maxiters`, `batch` are accepted for source compatibility and ignored."""
+    `maxiters`, `batch` are accepted for source compatibility and ignored.
 
-    def __init__(self, quadrature_alg=None, reltol=1e-6, abstol=1e-3, maxiters=1000, batch=100, nodes: int = None):
+    `adaptive=True` (opt-in) honours the contract on the device (`pinn_cubature_refine`): every term with at least one free
+    axis is integrated h-adaptively — Genz-Malik degree-7 / degree-5 estimates, every box whose error exceeds its volume share of
+    max(abstol, reltol |I|) bisected per round — to `reltol` / `abstol`, and the composite Gauss-Legendre rule with `nodes` points per free
+    axis PER LEAF (default 4, the estimate's degree) on the final mesh becomes the term's weighted point set.  `symbolic_discretize` refines
+    once at `init_params`; `solve` refines again every `refresh` Adam steps (0: never) at the iterate reached, and BFGS / LBFGS refine once
+    at their start; between two refinements the mesh is frozen and the gradient is that of the emitted rule.  `rep.cubature[k]` holds term
+    k's last `dict(integral, error, nregions, npoints, rounds, status)` (status 0 converged, 1 `max_regions` reached, 2 `max_rounds`
+    reached, 3 the integrand is not finite at that theta).  The cap of the refinement is `max_regions` boxes per term (and `max_rounds` bisection rounds): `maxiters` and `batch`, the
+    reference's caps of its integrand-evaluation count, stay accepted and ignored, and so does `quadrature_alg`.  `refresh` acts in the resident Adam loop of `solve`; a run that
+    `solve` routes through the host Adam loop (a Python `additional_loss`) keeps the mesh of `init_params`."""
+
+    def __init__(self, quadrature_alg=None, reltol=1e-6, abstol=1e-3, maxiters=1000, batch=100, nodes: int = None, adaptive: bool = False,
+                 refresh: int = 0, max_regions: int = 4096, max_rounds: int = 32):
         self.quadrature_alg, self.reltol, self.abstol, self.maxiters, self.batch = quadrature_alg, reltol, abstol, maxiters, batch
         self.nodes = nodes
+        self.adaptive, self.refresh, self.max_regions, self.max_rounds = bool(adaptive), int(refresh), int(max_regions), int(max_rounds)
         self._weights = None
+        self._bounds = None
 
     def _rule(self, lb, ub, dtype):
         free = [i for i in range(len(lb)) if ub[i] > lb[i]]
@@ -229,14 +243,15 @@ class QuadratureTraining(AbstractTrainingStrategy):
         # integration domains = the full variable ranges (no 1/points inset: src/discretize.jl get_bounds for QuadratureTraining)
         dom = {str(d.variable): (float(d.domain.lo), float(d.domain.hi)) for d in pde_system.domain}
         args = get_argument(list(pde_system.eqs) + list(pde_system.bcs), vi)
-        sets, weights = [], []
+        sets, weights, bounds = [], [], []
         for a in args:
             lb = np.array([float(v) if isinstance(v, (int, float)) else dom[str(v)][0] for v in a])
             ub = np.array([float(v) if isinstance(v, (int, float)) else dom[str(v)][1] for v in a])
             p, w = self._rule(lb, ub, dtype)
-            sets.append(p); weights.append(w)
+            sets.append(p); weights.append(w); bounds.append((lb, ub))
         n_pde = len(pde_system.eqs)
         self._weights = weights
+        self._bounds = bounds                                          # (adaptive = True: the boxes pinn_cubature_refine starts from)
         return sets[:n_pde], sets[n_pde:], None
 
     def point_weights(self):
