@@ -610,22 +610,30 @@ class Engine:
     # ---- resident L-BFGS (include/pinn_hip.h: pinn_lbfgs_init / _steps / _get) ----
     LBFGS_STATUS = ("RUN", "RETRY", "CONVERGED", "STALLED", "MAXITER")
 
-    def lbfgs_init(self, theta, weights=None, history: int = 10):
-        """`pinn_lbfgs_init`: put the device-resident L-BFGS state at theta; the term weights are fixed here."""
+    def _qn_init(self, symbol, theta, weights, *history):
+        """the _init call of a resident quasi-Newton solver: theta in double, the term weights as floats (or none), L-BFGS's history between"""
         th = _f64(theta)
         w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32)) if weights is not None else None
-        self.L.check(self.L.lib.pinn_lbfgs_init(self.h, th.ctypes.data_as(C.POINTER(C.c_double)), th.size, int(history),
-                                                w.ctypes.data_as(C.POINTER(C.c_float)) if w is not None else None), "pinn_lbfgs_init")
+        self.L.check(getattr(self.L.lib, symbol)(self.h, th.ctypes.data_as(C.POINTER(C.c_double)), th.size, *history,
+                                                 w.ctypes.data_as(C.POINTER(C.c_float)) if w is not None else None), symbol)
+
+    def _qn_steps(self, symbol, maxiters, max_evals, gtol):
+        """the _steps call of a resident quasi-Newton solver -> (objective after every performed iteration, evaluations, status name)"""
+        hist = np.zeros(max(int(maxiters), 1), dtype=np.float64)
+        it, ev, st = C.c_int(0), C.c_int(0), C.c_int(0)
+        me = 31 * max(int(maxiters), 1) if max_evals is None else int(max_evals)
+        self.L.check(getattr(self.L.lib, symbol)(self.h, int(maxiters), me, float(gtol), hist.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 C.byref(it), C.byref(ev), C.byref(st)), symbol)
+        return hist[:it.value], ev.value, self.LBFGS_STATUS[st.value]
+
+    def lbfgs_init(self, theta, weights=None, history: int = 10):
+        """`pinn_lbfgs_init`: put the device-resident L-BFGS state at theta; the term weights are fixed here."""
+        self._qn_init("pinn_lbfgs_init", theta, weights, int(history))
 
     def lbfgs_steps(self, maxiters: int, max_evals: int = None, gtol: float = 1e-8):
         """`pinn_lbfgs_steps`: at most `maxiters` further iterations / `max_evals` further trial evaluations (default: 31 per iteration, which
         never binds) from the stored state.  Returns (objective after every performed iteration, evaluations, status name)."""
-        hist = np.zeros(max(int(maxiters), 1), dtype=np.float64)
-        it, ev, st = C.c_int(0), C.c_int(0), C.c_int(0)
-        me = 31 * max(int(maxiters), 1) if max_evals is None else int(max_evals)
-        self.L.check(self.L.lib.pinn_lbfgs_steps(self.h, int(maxiters), me, float(gtol), hist.ctypes.data_as(C.POINTER(C.c_double)),
-                                                 C.byref(it), C.byref(ev), C.byref(st)), "pinn_lbfgs_steps")
-        return hist[:it.value], ev.value, self.LBFGS_STATUS[st.value]
+        return self._qn_steps("pinn_lbfgs_steps", maxiters, max_evals, gtol)
 
     def lbfgs_get(self, want_grad: bool = True):
         """`pinn_lbfgs_get`: (theta, objective, gradient) of the current iterate"""
@@ -640,20 +648,12 @@ class Engine:
 
     def bfgs_init(self, theta, weights=None):
         """`pinn_bfgs_init`: put the device-resident dense BFGS state at theta with H = I; the term weights are fixed here."""
-        th = _f64(theta)
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32)) if weights is not None else None
-        self.L.check(self.L.lib.pinn_bfgs_init(self.h, th.ctypes.data_as(C.POINTER(C.c_double)), th.size,
-                                               w.ctypes.data_as(C.POINTER(C.c_float)) if w is not None else None), "pinn_bfgs_init")
+        self._qn_init("pinn_bfgs_init", theta, weights)
 
     def bfgs_steps(self, maxiters: int, max_evals: int = None, gtol: float = 1e-8):
         """`pinn_bfgs_steps`: at most `maxiters` further iterations / `max_evals` further trial evaluations (default: 31 per iteration, which
         never binds) from the stored state.  Returns (objective after every performed iteration, evaluations, status name)."""
-        hist = np.zeros(max(int(maxiters), 1), dtype=np.float64)
-        it, ev, st = C.c_int(0), C.c_int(0), C.c_int(0)
-        me = 31 * max(int(maxiters), 1) if max_evals is None else int(max_evals)
-        self.L.check(self.L.lib.pinn_bfgs_steps(self.h, int(maxiters), me, float(gtol), hist.ctypes.data_as(C.POINTER(C.c_double)),
-                                                C.byref(it), C.byref(ev), C.byref(st)), "pinn_bfgs_steps")
-        return hist[:it.value], ev.value, self.BFGS_STATUS[st.value]
+        return self._qn_steps("pinn_bfgs_steps", maxiters, max_evals, gtol)
 
     def bfgs_get(self, want_grad: bool = True, want_hinv: bool = False):
         """`pinn_bfgs_get`: (theta, objective, gradient, inverse-Hessian approximation [P, P]) of the current iterate; what was not asked

@@ -1,8 +1,8 @@
-// bfgs_kernels.hpp — the device-resident dense BFGS finisher (pinn_bfgs_init / _steps / _get): everything of the
-// quasi-Newton iteration that is not the evaluation of the objective.  The iterate x, its gradient g, the trial point xn, the direction d, the
-// last step s = xn - x, the gradient difference y, u = H y, the inverse-Hessian approximation H[P][ld] (full symmetric storage, row-major) and a
-// small control block live on the device in double.  The pair (ident, gamma) of the control block stands for H = gamma I without touching the
-// matrix: neither the start nor a restart costs a pass over it.
+// bfgs_kernels.hpp — the device-resident dense BFGS finisher (pinn_bfgs_init / _steps / _get).  The state machine, the
+// line search, the reductions and their fixed order are qn_kernels.hpp's; this header adds the dense curvature: the last step s = xn - x, the
+// gradient difference y, u = H y, the inverse-Hessian approximation H[P][ld] (full symmetric storage, row-major) and the two matrix kernels.
+// The pair (ident, gamma) of the control block stands for H = gamma I without touching the matrix: neither the start nor a restart costs a
+// pass over it.
 // LEADING DIMENSION.  ld = P rounded up to a multiple of 128 = 64 lanes x 2 doubles: every row starts on a 16-byte boundary for any P (odd P
 // included), and every lane of a wave makes the same ld / 128 unconditional 16-byte loads per row.  The vectors are [ld] too.  The pad entries of
 // the vectors are zero from pinn_bfgs_init on and never written; the pad columns of H are written by k_bfgs_update only, as products with those
@@ -10,18 +10,12 @@
 // The host queues SLOTS back to back and reads nothing inside a chunk of them:
 //     one slot = k_bfgs_ctl<T>(JUDGE), k_bfgs_matvec, k_bfgs_ctl<T>(MID), k_bfgs_update, k_bfgs_ctl<T>(PROPOSE), ONE full evaluation
 // (T = the evaluation's element type: double in float64 mode, float otherwise; the evaluation is the handle's resident path, untouched).
-// k_bfgs_ctl<T> is one workgroup of 256 threads and a state machine on the control block:
-//   JUDGE (when an evaluation is pending)   fn = sum_k w_k sums_k / n_norm_k; Armijo: isfinite(fn) && fn <= f + 1e-4 t gd.
-//       accept: s = xn - x, y = gn - g, x <- xn, g <- gn, f <- fn, loss_hist[it++] = f; the update is due iff s.y > 1e-10 sqrt(s.s y.y):
-//               rho = 1 / s.y.  H a matrix: mv = MV_U, upd = UPD_MATRIX.  H = gamma I: gamma = s.y / y.y (Nocedal-Wright 6.20), u = gamma y,
-//               c = rho (1 + rho y.u) at once, upd = UPD_IDENT, ident = 0.  Update skipped and H a matrix: mv = MV_D (d = -H g).
-//       reject: t *= 0.5; after 30 trials status STALLED (terminal), otherwise status RETRY
+//   JUDGE, on acceptance: s and y are stored; when the pair passes qn::curvature the update is due: rho = 1 / s.y.  H a matrix: mv = MV_U,
+//             upd = UPD_MATRIX.  H = gamma I: gamma = s.y / y.y (Nocedal-Wright 6.20), u = gamma y, c = rho (1 + rho y.u) at once,
+//             upd = UPD_IDENT, ident = 0.  Update skipped and H a matrix: mv = MV_D (d = -H g).
 //   MID       mv == MV_U: c = rho (1 + rho y.u) from the u the matrix-vector kernel has just written
-//   PROPOSE   clears mv and upd.  RETRY: only xn = x + t d and the evaluation's copy.  RUN: max |g_i| > gtol or CONVERGED (a NaN entry is
-//             skipped); it < the call's limit or MAXITER; d = -gamma g while ident (a matrix H: d is what the matrix kernels left);
-//             gd = g.d; not gd < 0: restart, ident = 1, gamma = 1, d = -g; t = 1, or min(1, 1 / sqrt(g.g)) while H is the unscaled identity;
-//             xn and the evaluation's copy.
-//   In a terminal state (CONVERGED / STALLED / MAXITER) the launch does nothing.
+//   PROPOSE   clears mv and upd.  RUN: d = -gamma g while ident (a matrix H: d is what the matrix kernels left); a restart sets ident = 1,
+//             gamma = 1; the first step is scaled while H is the unscaled identity.
 // THE MATRIX KERNELS are launched in every slot.  Each reads ONE word of the control block first (mv / upd) and returns at once when it is 0
 // (a rejected trial, a terminal state, H = gamma I).  That word was written by a k_bfgs_ctl of an EARLIER launch: kernel boundaries on the one
 // stream are the only ordering — no grid barrier, no spin-wait, no atomics, no cooperative launch.
@@ -34,62 +28,37 @@
 //                   The wave that holds the new row multiplies it by the new g and reduces in the order above: d_i = -sum_j H[i][j] g_j in the
 //                   same pass.  An accepted, updated iteration is one read pass (u = H y) and one read + write pass.  UPD_IDENT reads nothing
 //                   of H: the old entry is gamma delta_ij.
-// Every dot product of k_bfgs_ctl has the fixed order of lbfgs::k_lbfgs_step: thread t takes elements t, t + 256, ...; per-wave butterfly; the
-// four waves in order.  Every thread only ever touches the elements i = t (mod 256) of the vectors, so its vector passes need no barrier.
 // Indexing into H is size_t; addresses in the column loops are affine and the loads unconditional.
-// Each body exists once, over a device context and a serial emulation context; the PINN_EMU build runs them with the sums in the device's order.
 #pragma once
-#include <cmath>
-#include <cstdint>
-#include "plat.hpp"
+#include "qn_kernels.hpp"
 
 namespace bfgs {
 
-#if defined(__clang__)
-#define BFGS_NO_CONTRACT _Pragma("clang fp contract(off)")
-#else
-#define BFGS_NO_CONTRACT
-#endif
-#ifdef PINN_EMU
-#define BFGS_DEV inline
-#else
-#define BFGS_DEV __device__ __forceinline__
-#endif
+using namespace qn;
 
-enum { ST_RUN = 0, ST_RETRY = 1, ST_CONVERGED = 2, ST_STALLED = 3, ST_MAXITER = 4 };      // (the numbering of lbfgs_kernels.hpp)
 enum { PH_JUDGE = 0, PH_MID = 1, PH_PROPOSE = 2, PH_LOAD = 3, PH_ADOPT = 4 };
 enum { MV_NONE = 0, MV_U = 1, MV_D = 2 };                // k_bfgs_matvec: nothing | u = H y | d = -H g
 enum { UPD_NONE = 0, UPD_MATRIX = 1, UPD_IDENT = 2 };    // k_bfgs_update: nothing | H a matrix | H = gamma I (write only)
-constexpr int BLOCK = 256;
-constexpr int WAVE = 64;
 constexpr int ROWS_PER_BLOCK = BLOCK / WAVE;
 constexpr int LD_ALIGN = 2 * WAVE;                       // doubles one wave takes per step of the column loop
-constexpr int MAX_TRIALS = 30;
 constexpr int MAX_P = 32768;                             // H = 8 GiB there
 
-struct Ctl {                             // the control block: all the host ever downloads inside pinn_bfgs_steps
-    double f, t, gd;                     // objective at x; step and g.d of the running line search
+struct Ctl : qn::Ctl {
+    int ident, mv, upd;                  // H = gamma I; what the matrix kernels of this slot do
     double gamma, rho, c;                // H = gamma I while ident; the scalars of the pending rank-two update
-    int status, ls, it, evals;           // ST_*; trials of the running line search; iterations / trial evaluations since pinn_bfgs_init
-    int pending, ident, mv, upd;         // an evaluation at xn awaits its judgement; H = gamma I; what the matrix kernels of this slot do
 };
 
-struct Args {
-    int P, K, ld;
-    int f64form;                         // objective formed as w_k * (sums_k / n_k) (float64 mode's eval) or (w_k * sums_k) / n_k (fp32 mode's)
-    double* x; double* g; double* xn; double* d; double* s; double* y; double* u;      // [ld], pads zero
+struct Args : qn::Args {
+    int ld;
+    double* s; double* y; double* u;     // [ld] like x, g, xn, d; pads zero
     double* H;                           // [P][ld]
     Ctl* ctl;
-    double* loss_hist;                   // objective after iteration it0 + i of the running call
-    const double* w; const double* nrm;  // [K] term weights, n_norm
-    const double* sums;                  // [K] raw sums of the evaluation, double
-    double* th_eval64; float* th_eval32; // where the next evaluation reads theta (one of them is null)
 };
 
 inline int padded_ld(int P) { return (P + LD_ALIGN - 1) / LD_ALIGN * LD_ALIGN; }
 
 struct dbl2 { double x, y; };
-BFGS_DEV dbl2 load2(const double* p) {
+QN_DEV dbl2 load2(const double* p) {
 #ifdef PINN_EMU
     return dbl2{p[0], p[1]};
 #else
@@ -97,7 +66,7 @@ BFGS_DEV dbl2 load2(const double* p) {
     return dbl2{v.x, v.y};
 #endif
 }
-BFGS_DEV void store2(double* p, dbl2 v) {
+QN_DEV void store2(double* p, dbl2 v) {
 #ifdef PINN_EMU
     p[0] = v.x; p[1] = v.y;
 #else
@@ -105,33 +74,18 @@ BFGS_DEV void store2(double* p, dbl2 v) {
 #endif
 }
 
-BFGS_DEV bool is_finite(double v) { return __builtin_fabs(v) <= 1.7976931348623157e308; }      // (false for NaN)
-
-// ---- the control kernel's body.  C: each(n, f): f(i) for the elements of this thread; sum(n, f) / amax(n, f): workgroup-uniform reductions of
-// f(i); lead(): the one thread that writes scalars; sync(): workgroup barrier
-template <class T, class C> BFGS_DEV void ctl_body(C& c, const Args& a, const T* ev, int phase, int it0, int it_end, double gtol) {
-    BFGS_NO_CONTRACT
+// ---- the control kernel's body
+template <class T, class C> QN_DEV void ctl_body(C& c, const Args& a, const T* ev, int phase, int it0, int it_end, double gtol) {
+    QN_NO_CONTRACT
     const int P = a.P;
     Ctl k = *a.ctl;
     c.sync();                                            // every thread has read the block before anyone writes it
-    auto store_eval = [&](int i, double v) {
-        if (a.th_eval64) a.th_eval64[i] = v;
-        if (a.th_eval32) a.th_eval32[i] = (float)v;
-    };
-    auto objective = [&]() {
-        BFGS_NO_CONTRACT
-        double fn = 0.0;
-        for (int q = 0; q < a.K; ++q) fn += a.f64form ? a.w[q] * (a.sums[q] / a.nrm[q]) : a.w[q] * a.sums[q] / a.nrm[q];
-        return fn;
-    };
-    if (phase == PH_LOAD) {                              // the evaluation's copy <- x
-        c.each(P, [&](int i) { store_eval(i, a.x[i]); });
+    if (phase == PH_LOAD) {
+        load(c, a);
         return;
     }
-    if (phase == PH_ADOPT) {                             // (f, g) <- the evaluation at x; H = I; nothing pending
-        c.each(P, [&](int i) { a.g[i] = (double)ev[i]; });
-        k.f = objective();
-        k.status = ST_RUN; k.ls = 0; k.pending = 0; k.t = 0.0; k.gd = 0.0;
+    if (phase == PH_ADOPT) {                             // H = I
+        adopt(c, a, k, ev);
         k.ident = 1; k.gamma = 1.0; k.rho = 0.0; k.c = 0.0; k.mv = MV_NONE; k.upd = UPD_NONE;
         if (c.lead()) *a.ctl = k;
         return;
@@ -140,23 +94,21 @@ template <class T, class C> BFGS_DEV void ctl_body(C& c, const Args& a, const T*
     if (phase == PH_JUDGE) {
         if (!k.pending) return;
         k.pending = 0;
-        const double fn = objective();
-        if (is_finite(fn) && fn <= k.f + 1e-4 * k.t * k.gd) {
+        const double fn = objective(a);
+        if (armijo(k, fn)) {
             c.each(P, [&](int i) {
                 const double xi = a.xn[i], gi = (double)ev[i];
                 a.s[i] = xi - a.x[i]; a.y[i] = gi - a.g[i];
                 a.x[i] = xi; a.g[i] = gi;
             });
-            const double sy = c.sum(P, [&](int i) { BFGS_NO_CONTRACT return a.s[i] * a.y[i]; });
-            const double ss = c.sum(P, [&](int i) { BFGS_NO_CONTRACT return a.s[i] * a.s[i]; });
-            const double yy = c.sum(P, [&](int i) { BFGS_NO_CONTRACT return a.y[i] * a.y[i]; });
-            if (sy > 1e-10 * sqrt(ss * yy)) {
+            double sy, yy;
+            if (curvature(c, P, [&](int i) { return a.s[i]; }, [&](int i) { return a.y[i]; }, sy, yy)) {
                 k.rho = 1.0 / sy;
                 if (k.ident) {                           // leaving H = gamma I: u and c need no matrix pass
                     const double gamma = sy / yy;
                     k.gamma = gamma;
-                    c.each(P, [&](int i) { BFGS_NO_CONTRACT a.u[i] = gamma * a.y[i]; });
-                    const double yu = c.sum(P, [&](int i) { BFGS_NO_CONTRACT return a.y[i] * a.u[i]; });
+                    c.each(P, [&](int i) { QN_NO_CONTRACT a.u[i] = gamma * a.y[i]; });
+                    const double yu = c.sum(P, [&](int i) { QN_NO_CONTRACT return a.y[i] * a.u[i]; });
                     k.c = k.rho * (1.0 + k.rho * yu);
                     k.ident = 0;
                     k.upd = UPD_IDENT;
@@ -165,73 +117,40 @@ template <class T, class C> BFGS_DEV void ctl_body(C& c, const Args& a, const T*
                     k.upd = UPD_MATRIX;
                 }
             } else if (!k.ident) k.mv = MV_D;            // update skipped: the next direction from the matrix as it is
-            k.f = fn;
-            if (c.lead()) a.loss_hist[k.it - it0] = fn;
-            ++k.it;
-            k.status = ST_RUN;
-        } else {
-            k.t *= 0.5;
-            ++k.ls;
-            k.status = k.ls >= MAX_TRIALS ? ST_STALLED : ST_RETRY;
-        }
+            accepted(c, a, k, fn, it0);
+        } else reject(k);
         if (c.lead()) *a.ctl = k;
         return;
     }
     if (phase == PH_MID) {
         if (k.mv != MV_U) return;
-        const double yu = c.sum(P, [&](int i) { BFGS_NO_CONTRACT return a.y[i] * a.u[i]; });
+        const double yu = c.sum(P, [&](int i) { QN_NO_CONTRACT return a.y[i] * a.u[i]; });
         k.c = k.rho * (1.0 + k.rho * yu);
         if (c.lead()) *a.ctl = k;
         return;
     }
     // PH_PROPOSE
     k.mv = MV_NONE; k.upd = UPD_NONE;
-    if (k.status == ST_RUN) {
-        const double gmax = c.amax(P, [&](int i) { return a.g[i]; });
-        if (!(gmax > gtol)) k.status = ST_CONVERGED;
-        else if (!(k.it < it_end)) k.status = ST_MAXITER;
-        else {
-            if (k.ident) {
-                const double gamma = k.gamma;
-                c.each(P, [&](int i) { BFGS_NO_CONTRACT a.d[i] = -(gamma * a.g[i]); });
-            }
-            k.gd = c.sum(P, [&](int i) { BFGS_NO_CONTRACT return a.g[i] * a.d[i]; });
-            if (!(k.gd < 0.0)) {                         // not a descent direction: restart from steepest descent, H = I
-                k.ident = 1; k.gamma = 1.0;
-                c.each(P, [&](int i) { a.d[i] = -a.g[i]; });
-                k.gd = c.sum(P, [&](int i) { BFGS_NO_CONTRACT return a.g[i] * a.d[i]; });
-            }
-            k.t = 1.0;
-            if (k.ident && k.gamma == 1.0) {
-                const double gg = c.sum(P, [&](int i) { BFGS_NO_CONTRACT return a.g[i] * a.g[i]; });
-                const double r = 1.0 / sqrt(gg);
-                k.t = r < 1.0 ? r : 1.0;                 // std::min(1.0, r)
-            }
-            k.ls = 0;
+    if (k.status == ST_RUN && go_on(c, a, k, it_end, gtol)) {
+        if (k.ident) {
+            const double gamma = k.gamma;
+            c.each(P, [&](int i) { QN_NO_CONTRACT a.d[i] = -(gamma * a.g[i]); });
         }
+        if (restart_if_uphill(c, a, k)) { k.ident = 1; k.gamma = 1.0; }
+        first_step(c, a, k, k.ident && k.gamma == 1.0);
     }
-    if (k.status == ST_RUN || k.status == ST_RETRY) {
-        const double t = k.t;
-        c.each(P, [&](int i) {
-            BFGS_NO_CONTRACT
-            const double v = a.x[i] + t * a.d[i];
-            a.xn[i] = v;
-            store_eval(i, v);
-        });
-        k.pending = 1;
-        ++k.evals;
-    }
+    if (k.status == ST_RUN || k.status == ST_RETRY) propose(c, a, k);
     if (c.lead()) *a.ctl = k;
 }
 
 // ---- the matrix kernels' bodies, one row each.  W: wave_sum(f): the sum of f(lane) over the 64 lanes by the xor butterfly, in every lane;
 // lane0(): the lane that writes the row's scalar
-template <class W> BFGS_DEV void matvec_row(W& w, const Args& a, int row, int mode) {
+template <class W> QN_DEV void matvec_row(W& w, const Args& a, int row, int mode) {
     const double* Hr = a.H + (size_t)row * (size_t)a.ld;
     const double* v = mode == MV_U ? a.y : a.g;
     const int nstep = a.ld / LD_ALIGN;
     const double r = w.wave_sum([&](int lane) {
-        BFGS_NO_CONTRACT
+        QN_NO_CONTRACT
         const double* hp = Hr + 2 * lane;
         const double* vp = v + 2 * lane;
         double a0 = 0.0, a1 = 0.0;
@@ -248,12 +167,12 @@ template <class W> BFGS_DEV void matvec_row(W& w, const Args& a, int row, int mo
     }
 }
 
-template <bool FROM_IDENT, class W> BFGS_DEV void update_row(W& w, const Args& a, int row, double gamma, double rho, double cc) {
+template <bool FROM_IDENT, class W> QN_DEV void update_row(W& w, const Args& a, int row, double gamma, double rho, double cc) {
     double* Hr = a.H + (size_t)row * (size_t)a.ld;
     const double si = a.s[row], ui = a.u[row];
     const int nstep = a.ld / LD_ALIGN;
     const double r = w.wave_sum([&](int lane) {
-        BFGS_NO_CONTRACT
+        QN_NO_CONTRACT
         double* hp = Hr + 2 * lane;
         const double* sp = a.s + 2 * lane;
         const double* up = a.u + 2 * lane;
@@ -279,47 +198,13 @@ template <bool FROM_IDENT, class W> BFGS_DEV void update_row(W& w, const Args& a
 }
 
 #ifdef PINN_EMU
-struct EmuCtx {
-    bool lead() const { return true; }
-    void sync() {}
-    template <class F> void each(int n, F f) { for (int i = 0; i < n; ++i) f(i); }
-    template <class F> double sum(int n, F f) {          // the device's order: strided partials, per-wave butterfly, the waves in order
-        BFGS_NO_CONTRACT
-        double tot = 0.0;
-        for (int w = 0; w < BLOCK / WAVE; ++w) {
-            double v[WAVE];
-            for (int l = 0; l < WAVE; ++l) {
-                double s = 0.0;
-                for (int i = w * WAVE + l; i < n; i += BLOCK) s += f(i);
-                v[l] = s;
-            }
-            for (int msk = 32; msk >= 1; msk >>= 1) {
-                double nx[WAVE];
-                for (int l = 0; l < WAVE; ++l) nx[l] = v[l] + v[l ^ msk];
-                for (int l = 0; l < WAVE; ++l) v[l] = nx[l];
-            }
-            tot = w == 0 ? v[0] : tot + v[0];
-        }
-        return tot;
-    }
-    template <class F> double amax(int n, F f) {
-        double mx = 0.0;
-        for (int i = 0; i < n; ++i) mx = fmax(mx, fabs(f(i)));
-        return mx;
-    }
-};
 struct EmuWave {
     bool lane0() const { return true; }
     template <class F> double wave_sum(F f) {
-        BFGS_NO_CONTRACT
+        QN_NO_CONTRACT
         double v[WAVE];
         for (int l = 0; l < WAVE; ++l) v[l] = f(l);
-        for (int msk = 32; msk >= 1; msk >>= 1) {
-            double nx[WAVE];
-            for (int l = 0; l < WAVE; ++l) nx[l] = v[l] + v[l ^ msk];
-            for (int l = 0; l < WAVE; ++l) v[l] = nx[l];
-        }
-        return v[0];
+        return butterfly(v);
     }
 };
 template <class T> inline void launch_ctl(const Args& a, const T* ev, int phase, int it0, int it_end, double gtol, plat_stream) {
@@ -343,41 +228,11 @@ inline void launch_update(const Args& a, plat_stream) {
     }
 }
 #else
-struct DevCtx {
-    double* sh;
-    int t;
-    __device__ __forceinline__ bool lead() const { return t == 0; }
-    __device__ __forceinline__ void sync() { __syncthreads(); }
-    template <class F> __device__ __forceinline__ void each(int n, F f) { for (int i = t; i < n; i += BLOCK) f(i); }
-    template <class F> __device__ __forceinline__ double sum(int n, F f) {
-        BFGS_NO_CONTRACT
-        double v = 0.0;
-        for (int i = t; i < n; i += BLOCK) v += f(i);
-        for (int msk = 32; msk >= 1; msk >>= 1) v += __shfl_xor(v, msk, WAVE);
-        if ((t & 63) == 0) sh[t >> 6] = v;
-        __syncthreads();
-        v = sh[0];
-        for (int w = 1; w < BLOCK / WAVE; ++w) v += sh[w];
-        __syncthreads();                                 // (sh is free for the next reduction)
-        return v;
-    }
-    template <class F> __device__ __forceinline__ double amax(int n, F f) {
-        double v = 0.0;
-        for (int i = t; i < n; i += BLOCK) v = fmax(v, fabs(f(i)));
-        for (int msk = 32; msk >= 1; msk >>= 1) v = fmax(v, __shfl_xor(v, msk, WAVE));
-        if ((t & 63) == 0) sh[t >> 6] = v;
-        __syncthreads();
-        v = sh[0];
-        for (int w = 1; w < BLOCK / WAVE; ++w) v = fmax(v, sh[w]);
-        __syncthreads();
-        return v;
-    }
-};
 struct DevWave {
     int lane;
     __device__ __forceinline__ bool lane0() const { return lane == 0; }
     template <class F> __device__ __forceinline__ double wave_sum(F f) {
-        BFGS_NO_CONTRACT
+        QN_NO_CONTRACT
         double v = f(lane);
         for (int msk = 32; msk >= 1; msk >>= 1) v += __shfl_xor(v, msk, WAVE);
         return v;

@@ -1,6 +1,6 @@
 // lbfgs.cpp — the L-BFGS finishers of the C ABI: pinn_lbfgs (iteration on the host, evaluations on the device) and the resident loop
 // pinn_lbfgs_init / _steps / _get.  Both use the noise-floor switch of resident.hpp (GemmFloorSwitch).
-#include "resident.hpp"
+#include "qn_host.hpp"
 #include "lbfgs_kernels.hpp"
 
 using namespace pe;
@@ -129,55 +129,21 @@ int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int histor
 
 // Resident L-BFGS (pinn_lbfgs_init / _steps / _get): pinn_lbfgs's iteration with the iterate, the curvature rings and the
 // line search on the device.  A SLOT = one lbfgs::k_lbfgs_step launch (judge the evaluation just finished, propose the next point) + one full
-// resident evaluation (resident.hpp: ResidentEval).
-// Slots are queued in chunks of "lbfgs_chunk"; the host reads the control block after a chunk and nothing else before the call's end.
+// resident evaluation (resident.hpp: ResidentEval).  The driver is qn_host.hpp's; this unit adds the rings' buffer and the slot's launch.
 // The state has buffers of its own: evaluations, optimiser runs and HMC draws between two calls do not touch it, and it does not touch them.
-struct pe::LbfgsState {
-    lbfgs::Args a;
-    lbfgs::Ctl ctl;                      // host mirror of the control block as of the last download
-    ResidentEval ev;                     // the term weights, fixed at init (the curvature pairs belong to one objective)
+struct pe::LbfgsState : QnState<lbfgs::Args, lbfgs::Ctl> {
+    static constexpr const char *NAME = "L-BFGS", *INIT = "pinn_lbfgs_init";
+    static constexpr int LOAD = lbfgs::MODE_LOAD, ADOPT = lbfgs::MODE_ADOPT;
     double* d_state = nullptr;           // [4 P + 2 m P + m]: x | g | xn | d | S | Y | rho
-    lbfgs::Ctl* d_ctl = nullptr;
-    double* d_tab = nullptr;             // [2 K]: weights | n_norm
-    double* d_hist = nullptr;
-    size_t hist_cap = 0;
+    ~LbfgsState() { plat_free(d_state); }
+    void launch(pinn_engine& E, int mode, int it0, int it_end, double gtol) {
+        typed([&](auto* out) { lbfgs::launch_step(a, out, mode, it0, it_end, gtol, E.stream); });
+    }
+    void slot(pinn_engine& E, int it0, int it_end, double gtol) { launch(E, lbfgs::MODE_SLOT, it0, it_end, gtol); }
 };
 
-namespace {
-
-void lbfgs_release(LbfgsState* H) {
-    if (!H) return;
-    H->ev.release();
-    plat_free(H->d_state); plat_free(H->d_ctl); plat_free(H->d_tab); plat_free(H->d_hist);
-    delete H;
-}
-
-// what pinn_lbfgs_steps / _get check first; leaves the handle as it is
-int lbfgs_ready(pinn_engine& E, const char* who) {
-    if (!E.lbfgs) return fail(std::string(who) + ": no optimiser state (call pinn_lbfgs_init first)");
-    return E.lbfgs->ev.ready(E, who, "pinn_lbfgs_init");
-}
-int lbfgs_refuse_target(pinn_engine& E, const char* who) {
-    return resident_refuse_target(E, who, "the resident L-BFGS loop runs on a single device only", "L-BFGS needs a fixed objective");
-}
-void lbfgs_step(pinn_engine& E, LbfgsState& H, int mode, int it0, int it_end, double gtol) {
-    if (H.ev.f64) lbfgs::launch_step<double>(H.a, H.ev.out<double>(), mode, it0, it_end, gtol, E.stream);
-    else lbfgs::launch_step<float>(H.a, H.ev.out<float>(), mode, it0, it_end, gtol, E.stream);
-}
-// (f, g) at x from one evaluation; rings cleared, nothing pending (init, and after the noise-floor switch); downloads the control block
-int lbfgs_adopt(pinn_engine& E, LbfgsState& H) {
-    lbfgs_step(E, H, lbfgs::MODE_LOAD, 0, 0, 0.0);
-    if (H.ev.eval(E)) return 1;
-    lbfgs_step(E, H, lbfgs::MODE_ADOPT, 0, 0, 0.0);
-    if (plat_d2h(&H.ctl, H.d_ctl, sizeof(lbfgs::Ctl), E.stream)) return fail("D2H copy failed");
-    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-    return 0;
-}
-
-}  // namespace
-
 void pe::lbfgs_free(pinn_engine& E) {
-    lbfgs_release(E.lbfgs);
+    delete E.lbfgs;
     E.lbfgs = nullptr;
     E.lbfgs_history = 0;
 }
@@ -190,38 +156,19 @@ int pinn_lbfgs_init(pinn_handle h, const double* theta, int64_t p, int history, 
     pinn_engine& E = *h;
     if (check_theta(E, who, p)) return 1;
     if (history < 1 || history > lbfgs::MAX_HISTORY) return fail(std::string(who) + ": history must be in 1.." + std::to_string(lbfgs::MAX_HISTORY));
-    if (lbfgs_refuse_target(E, who)) return 1;
+    if (qn_refuse_target<LbfgsState>(E, who)) return 1;
     DeviceScope scope(E.device);
     if (!E.f64 && ensure_points(E)) return 1;
     const size_t P = (size_t)p, m = (size_t)history;
-    const int K = (int)E.terms.size();
-    std::unique_ptr<LbfgsState, void (*)(LbfgsState*)> H(new LbfgsState, lbfgs_release);
+    std::unique_ptr<LbfgsState> H(new LbfgsState);
     const size_t nstate = 4 * P + 2 * m * P + m;
     H->d_state = (double*)plat_malloc(sizeof(double) * nstate);
-    H->d_ctl = (lbfgs::Ctl*)plat_malloc(sizeof(lbfgs::Ctl));
-    H->d_tab = (double*)plat_malloc(sizeof(double) * (size_t)(2 * K));
-    if (!H->d_state || !H->d_ctl || !H->d_tab) return fail(std::string(who) + ": device allocation failed");
-    std::vector<double> tb((size_t)(2 * K));             // weights (the caller's floats, widened) | n_norm
-    for (int k = 0; k < K; ++k) {
-        tb[k] = term_w ? (double)term_w[k] : 1.0;
-        tb[K + k] = (double)E.terms[k].n_norm;
-    }
-    if (H->ev.init(E, who, tb.data(), K)) return 1;
+    if (!H->d_state) return fail(std::string(who) + ": device allocation failed");
     lbfgs::Args& a = H->a;
-    std::memset(&a, 0, sizeof a);
-    a.P = (int)p; a.K = K; a.m = history; a.f64form = H->ev.f64 ? 1 : 0;
+    a.m = history;
     a.x = H->d_state; a.g = a.x + P; a.xn = a.g + P; a.d = a.xn + P; a.S = a.d + P; a.Y = a.S + m * P; a.rho = a.Y + m * P;
-    a.ctl = H->d_ctl;
-    a.w = H->d_tab; a.nrm = H->d_tab + K;
-    a.sums = H->ev.sums(P);
-    a.th_eval64 = H->ev.theta64(E);
-    a.th_eval32 = H->ev.theta32();
-    std::memset(&H->ctl, 0, sizeof H->ctl);
     plat_memset(H->d_state, 0, sizeof(double) * nstate, E.stream);
-    if (plat_h2d(a.x, theta, sizeof(double) * P, E.stream) || plat_h2d(H->d_tab, tb.data(), sizeof(double) * tb.size(), E.stream) ||
-        plat_h2d(H->d_ctl, &H->ctl, sizeof(lbfgs::Ctl), E.stream) || plat_sync(E.stream))
-        return fail(std::string(who) + ": H2D copy failed");
-    if (lbfgs_adopt(E, *H)) return 1;
+    if (qn_init(E, *H, who, theta, term_w)) return 1;
     lbfgs_free(E);
     E.lbfgs = H.release();
     E.lbfgs_history = history;
@@ -231,64 +178,13 @@ int pinn_lbfgs_init(pinn_handle h, const double* theta, int64_t p, int history, 
 int pinn_lbfgs_steps(pinn_handle h, int maxiters, int max_evals, double gtol, double* loss_history, int* iters_done, int* evals_done, int* status) {
     const char* who = "pinn_lbfgs_steps";
     if (!h) return fail(std::string(who) + ": null argument");
-    pinn_engine& E = *h;
-    if (lbfgs_ready(E, who) || lbfgs_refuse_target(E, who)) return 1;
-    if (maxiters < 1) return fail(std::string(who) + ": maxiters must be at least 1");
-    if (max_evals < 1) return fail(std::string(who) + ": max_evals must be at least 1");
-    LbfgsState& H = *E.lbfgs;
-    DeviceScope scope(E.device);
-    H.a.th_eval64 = H.ev.theta64(E);
-    if (!dev_grow(H.d_hist, H.hist_cap, (size_t)maxiters, E.stream)) return fail(std::string(who) + ": device allocation failed");
-    H.a.loss_hist = H.d_hist;
-    if (H.ctl.status >= lbfgs::ST_CONVERGED) {           // a terminal state ends a call, not the optimisation: the next call tests again
-        H.ctl.status = lbfgs::ST_RUN;
-        if (plat_h2d(H.d_ctl, &H.ctl, sizeof(lbfgs::Ctl), E.stream) || plat_sync(E.stream)) return fail(std::string(who) + ": H2D copy failed");
-    }
-    const int it0 = H.ctl.it, it_end = it0 + maxiters, ev0 = H.ctl.evals;
-    GemmFloorSwitch floor_switch(E);
-    for (;;) {
-        const int left = max_evals - (H.ctl.evals - ev0);
-        if (left <= 0) break;
-        const int n = std::min(E.lbfgs_chunk, left);     // (a slot proposes at most one trial point)
-        for (int s = 0; s < n; ++s) {
-            lbfgs_step(E, H, lbfgs::MODE_SLOT, it0, it_end, gtol);
-            if (H.ev.eval(E)) return 1;
-        }
-        if (plat_d2h(&H.ctl, H.d_ctl, sizeof(lbfgs::Ctl), E.stream)) return fail(std::string(who) + ": D2H copy failed");
-        if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
-        if (H.ctl.status < lbfgs::ST_CONVERGED) continue;
-        if (H.ctl.status == lbfgs::ST_STALLED && floor_switch.eligible()) {
-            const int sw = floor_switch.engage();
-            if (sw == 1) return 1;
-            if (sw == 0 && floor_switch.switched) {      // go on from the same iterate; curvature pairs carry the other arithmetic's gradient noise
-                if (lbfgs_adopt(E, H)) return 1;
-                continue;
-            }
-        }
-        break;
-    }
-    const int done = H.ctl.it - it0;
-    if (loss_history) {
-        if (done > 0 && (plat_d2h(loss_history, H.d_hist, sizeof(double) * (size_t)done, E.stream) || plat_sync(E.stream))) return fail(std::string(who) + ": D2H copy failed");
-        for (int i = done; i < maxiters; ++i) loss_history[i] = H.ctl.f;
-    }
-    if (iters_done) *iters_done = done;
-    if (evals_done) *evals_done = H.ctl.evals - ev0;
-    if (status) *status = H.ctl.status;
-    return floor_switch.finish();
+    return qn_steps(*h, h->lbfgs, who, maxiters, max_evals, gtol, loss_history, iters_done, evals_done, status);
 }
 
 int pinn_lbfgs_get(pinn_handle h, double* theta, int64_t p, double* f, double* grad) {
     const char* who = "pinn_lbfgs_get";
     if (!h || !theta) return fail(std::string(who) + ": null argument");
-    pinn_engine& E = *h;
-    if (lbfgs_ready(E, who) || check_theta(E, who, p)) return 1;
-    LbfgsState& H = *E.lbfgs;
-    DeviceScope scope(E.device);
-    if (plat_d2h(theta, H.a.x, sizeof(double) * (size_t)p, E.stream) || (grad && plat_d2h(grad, H.a.g, sizeof(double) * (size_t)p, E.stream)) || plat_sync(E.stream))
-        return fail(std::string(who) + ": D2H copy failed");
-    if (f) *f = H.ctl.f;
-    return 0;
+    return qn_get(*h, h->lbfgs, who, theta, p, f, grad);
 }
 
 }  // extern "C"
