@@ -392,6 +392,25 @@ function hmc_draws(e::HIPEngine, ndraws::Integer, n_leapfrog::Integer, ϵ::Real;
     return samples, acc, lp
 end
 
+"""
+    nuts_draws!(e, ndraws, max_depth, ϵ; seed = 0, normals = nothing, uniforms = nothing, delta_max = 1000.0)
+        -> (samples P × ndraws, accept_stat, logp, tree_depth, n_leapfrog, divergent)
+
+The resident No-U-Turn transitions (`pinn_nuts_draws`, DESIGN.md §4.14): `Kernel = NUTS(δ)` of `ahmc_bayesian_pinn_pde` on the chain of
+`hmc_init`, which it advances (hence the `!`), under the metric of `hmc_set_metric`.  AdvancedHMC's own NUTS owns its trajectory loop and cannot
+run on the resident chain.  `normals` are STANDARD normals (P × ndraws); `uniforms` has 2 max_depth + 2^max_depth - 1 values per draw.
+"""
+function nuts_draws!(e::HIPEngine, ndraws::Integer, max_depth::Integer, ϵ::Real; seed::Integer = 0, normals = nothing, uniforms = nothing, delta_max::Real = 1000.0)
+    z = normals === nothing ? Float64[] : Vector{Float64}(vec(normals)); uni = uniforms === nothing ? Float64[] : Vector{Float64}(vec(uniforms))
+    samples = zeros(Float64, e.P, ndraws); acc = zeros(Float64, ndraws); lp = zeros(Float64, ndraws)
+    depth = zeros(Cint, ndraws); nleap = zeros(Cint, ndraws); dvg = zeros(Cint, ndraws)
+    GC.@preserve z uni samples acc lp depth nleap dvg check(ccall(sym(:pinn_nuts_draws), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cdouble, Cdouble, UInt64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}),
+        e.h, ndraws, max_depth, Float64(ϵ), Float64(delta_max), UInt64(seed), normals === nothing ? Ptr{Float64}(C_NULL) : pointer(z),
+        uniforms === nothing ? Ptr{Float64}(C_NULL) : pointer(uni), samples, e.P, acc, lp, depth, nleap, dvg), "pinn_nuts_draws")
+    return samples, acc, lp, depth, nleap, dvg
+end
+
 function hmc_get(e::HIPEngine)
     θ = zeros(Float64, e.P); g = zeros(Float64, e.P); lp = Ref{Float64}(0.0)
     GC.@preserve θ g check(ccall(sym(:pinn_hmc_get), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}, Ptr{Float64}),

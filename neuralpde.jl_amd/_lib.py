@@ -39,6 +39,7 @@ SYMBOLS = [
     "pinn_residual_f64", "pinn_phi_f64", "pinn_derivative_f64", "pinn_term_grads_f64", "pinn_loglik_grad_f64",
     "pinn_loss_grad_sharded_device_f64", "pinn_loss_grad_sharded_f64",
     "pinn_hmc_init", "pinn_hmc_set_metric", "pinn_hmc_draws", "pinn_hmc_get", "pinn_hmc_find_stepsize", "pinn_hmc_warmup",
+    "pinn_nuts_draws",
     "pinn_lbfgs_init", "pinn_lbfgs_steps", "pinn_lbfgs_get",
     "pinn_bfgs_init", "pinn_bfgs_steps", "pinn_bfgs_get",
     "pinn_phi_ensemble", "pinn_derivative_ensemble",
@@ -126,6 +127,11 @@ class Library:
         try:                                     # (resident HMC warm-up: variant libraries built before it still load)
             L.pinn_hmc_find_stepsize.argtypes = [vp, C.c_double, C.c_uint64, dp, C.c_int64, dp, C.POINTER(C.c_int)]
             L.pinn_hmc_warmup.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint64, dp, dp, dp, C.c_int64, dp, dp, dp, dp, dp]
+        except AttributeError:
+            pass
+        try:                                     # (resident NUTS: variant libraries built before it still load)
+            ip = C.POINTER(C.c_int)
+            L.pinn_nuts_draws.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint64, dp, dp, dp, C.c_int64, dp, dp, ip, ip, ip]
         except AttributeError:
             pass
         try:                                     # (resident L-BFGS: variant libraries built before it still load)
@@ -762,6 +768,25 @@ class Engine:
                                                 smp.ctypes.data_as(dp), self.P, acc.ctypes.data_as(dp), lp.ctypes.data_as(dp), steps.ctypes.data_as(dp),
                                                 C.byref(eps), minv.ctypes.data_as(dp)), "pinn_hmc_warmup")
         return smp, acc, lp, steps, eps.value, minv
+
+    def nuts_draws(self, ndraws: int, max_depth: int, eps: float, seed: int = 0, normals=None, uniforms=None, delta_max: float = 1000.0):
+        """`pinn_nuts_draws`: `ndraws` No-U-Turn transitions of the chain of `hmc_init` on the device, one download.  normals ([ndraws x P]
+        STANDARD normals) / uniforms ([ndraws x (2 D + 2^D - 1)], D = max_depth: u_dir | u_merge | u_leaf) replace the device generator's draws
+        when given.  Returns (samples [ndraws x P], accept_stat, logp, tree_depth, n_leapfrog, divergent)."""
+        nd, dp, ip = max(int(ndraws), 0), C.POINTER(C.c_double), C.POINTER(C.c_int)
+        nu = 2 * int(max_depth) + (1 << min(max(int(max_depth), 0), 10)) - 1
+        z = None if normals is None else _f64(normals).reshape(-1)
+        uni = None if uniforms is None else _f64(uniforms).reshape(-1)
+        if (z is not None and z.size != nd * self.P) or (uni is not None and uni.size != nd * nu):
+            raise ValueError("normals: ndraws x P values, uniforms: ndraws x (2 max_depth + 2^max_depth - 1) values")
+        smp = np.zeros((nd, self.P), dtype=np.float64)
+        acc, lp = np.zeros(nd, dtype=np.float64), np.zeros(nd, dtype=np.float64)
+        depth, nleap, div = np.zeros(nd, dtype=np.int32), np.zeros(nd, dtype=np.int32), np.zeros(nd, dtype=np.int32)
+        self.L.check(self.L.lib.pinn_nuts_draws(self.h, int(ndraws), int(max_depth), float(eps), float(delta_max), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                z.ctypes.data_as(dp) if z is not None else None, uni.ctypes.data_as(dp) if uni is not None else None,
+                                                smp.ctypes.data_as(dp), self.P, acc.ctypes.data_as(dp), lp.ctypes.data_as(dp),
+                                                depth.ctypes.data_as(ip), nleap.ctypes.data_as(ip), div.ctypes.data_as(ip)), "pinn_nuts_draws")
+        return smp, acc, lp, depth, nleap, div
 
     def adam_init_f64(self, theta):
         th = _f64(theta)

@@ -16,6 +16,8 @@ host as in the reference (`sampler="host"`: one device evaluation and one host r
 transitions on the device (`pinn_hmc_*`): theta, momentum, metric, gradient and energies stay resident, a call
 makes many draws and downloads once; the step-size search, dual averaging and the windowed metric stay here in Python unless
 `adaptation="device"` runs the whole warm-up in ONE resident call (`pinn_hmc_warmup`).
+`kernel="nuts"` replaces the fixed-length trajectory by No-U-Turn transitions (`_nuts_transition`, the specification; on the device
+`pinn_nuts_draws`).
 """
 from __future__ import annotations
 
@@ -203,6 +205,210 @@ def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, ep
     return np.asarray(samples), {"acceptance": np.asarray(accs), "step_size": eps, "inv_metric": minv, "n_adapts": n_adapts}
 
 
+# ------------------------------------------------------------------------------------------------
+# NUTS: multinomial No-U-Turn transitions with the generalised U-turn criterion, iterative form
+# ------------------------------------------------------------------------------------------------
+def _logaddexp(a, b):
+    m = a if a > b else b
+    if m == -math.inf:
+        return -math.inf
+    return m + math.log1p(math.exp(-abs(a - b)))
+
+
+def _exp(x):
+    return math.exp(x) if x < 709.0 else math.inf       # (a weight ratio may overflow: the comparison u < inf is what matters)
+
+
+def nuts_uniforms(max_depth):
+    """length of a draw's row of uniforms: [u_dir[0..D) | u_merge[0..D) | u_leaf[0 .. 2^D - 1)]"""
+    return 2 * int(max_depth) + (1 << int(max_depth)) - 1
+
+
+def _nuts_transition(logp_grad, state, minv, eps, z, u, max_depth, delta_max=1000.0, *, sum_fn=np.sum, trace=None):
+    """ONE No-U-Turn transition from state = (th, lp, g), g = grad logp, under the diagonal inverse metric `minv`, with all its randomness
+    supplied: z = P standard normals, u = `nuts_uniforms(max_depth)` uniforms.  -> (th, lp, g), stats.  This function is the specification:
+    the host sampler's transition, the tests' restatement, and the text csrc/nuts_kernels.hpp restates operation by operation.
+    Conventions are `_hmc`'s: H = -logp + 1/2 sum minv r^2; a leapfrog of signed step s = v eps is r += s/2 g; th += s minv r; evaluate;
+    r += s/2 g.  A doubling at depth d builds 2^d leaves outward from the right (v = +1, u_dir[d] < 0.5) or the left edge; per leaf:
+    delta = H0 - H (-inf if not finite), sum_acc += exp(min(0, delta)), divergence if not -delta <= delta_max, progressive multinomial
+    sampling of the subtree's candidate, the momentum sum, a checkpoint (r, rho_sub) at index popcount(n) when n is even and the U-turn
+    checks of every sub-tree that ends at an odd n against the checkpoints.  A subtree that diverges or turns is discarded and ends the
+    transition; a completed one is merged (proposal <- candidate with probability min(1, w_sub / W)) and the whole tree is checked.
+    O(max_depth) saved vectors, no recursion.  sum_fn: the sum every dot product uses (the tests reverse it); trace: a list that receives
+    (kind, lhs, rhs, scale, outcome) of every comparison made — kind "direction", "divergence", "leaf", "merge", "uturn" (scale: what
+    |lhs - rhs| is relative to) — and ("energy", H, H0, 0, None) per leaf, ("end", reason, depth, leaves of the turning sub-tree, None)."""
+    th, lp, g = state
+    D = int(max_depth)
+    u = np.asarray(u, dtype=np.float64)
+    u_dir, u_merge, u_leaf = u[:D], u[D:2 * D], u[2 * D:]
+    note = (lambda *a: trace.append(a)) if trace is not None else (lambda *a: None)
+
+    def turning(rho, r):
+        t = rho * minv * r
+        d = float(sum_fn(t))
+        note("uturn", d, 0.0, float(np.sum(np.abs(t))), d <= 0.0)
+        return d <= 0.0
+
+    r0 = z / np.sqrt(minv)
+    h0 = -lp + 0.5 * float(sum_fn(minv * r0 * r0))
+    left, right = (th, r0, g), (th, r0, g)
+    prop = (th, lp, g)
+    rho = r0.copy()
+    log_w, depth, n_leaf, sum_acc, divergent = 0.0, 0, 0, 0.0, 0
+    r_ck, rho_ck = [None] * max(D, 1), [None] * max(D, 1)
+    with np.errstate(all="ignore"):
+        while depth < D:
+            v = 1.0 if u_dir[depth] < 0.5 else -1.0
+            note("direction", float(u_dir[depth]), 0.5, 1.0, v > 0)
+            th_m, r_m, g_m = right if v > 0 else left
+            s = v * eps
+            rho_sub, logw_sub, cand, ended = np.zeros_like(r0), -math.inf, None, False
+            for n in range(1 << depth):
+                r_m = r_m + 0.5 * s * g_m
+                th_m = th_m + s * minv * r_m
+                lp_m, g_m = logp_grad(th_m)
+                r_m = r_m + 0.5 * s * g_m
+                h = -lp_m + 0.5 * float(sum_fn(minv * r_m * r_m))
+                note("energy", h, h0, 0.0, None)
+                delta = h0 - h
+                if not math.isfinite(delta):
+                    delta = -math.inf
+                sum_acc += math.exp(min(0.0, delta))
+                n_leaf += 1
+                note("divergence", -delta, delta_max, max(abs(delta), delta_max), not (-delta <= delta_max))
+                if not (-delta <= delta_max):
+                    divergent, ended = 1, True
+                    note("end", "divergent", depth, n, None)
+                    break
+                logw_sub = _logaddexp(logw_sub, delta)
+                if n > 0:
+                    p = _exp(delta - logw_sub)
+                    note("leaf", float(u_leaf[n_leaf - 1]), p, max(float(u_leaf[n_leaf - 1]), p), bool(u_leaf[n_leaf - 1] < p))
+                if n == 0 or u_leaf[n_leaf - 1] < _exp(delta - logw_sub):
+                    cand = (th_m, lp_m, g_m)
+                rho_sub = rho_sub + r_m
+                if n % 2 == 0:
+                    i = bin(n).count("1")
+                    r_ck[i], rho_ck[i] = r_m, rho_sub
+                else:
+                    i_max = bin(n >> 1).count("1")
+                    k = 0
+                    while (n >> k) & 1:
+                        k += 1
+                    for i in range(i_max, i_max - k, -1):
+                        rho_s = rho_sub - rho_ck[i] + r_ck[i]
+                        if turning(rho_s, r_ck[i]) or turning(rho_s, r_m):
+                            ended = True
+                            note("end", "subtree", depth, 1 << (i_max - i + 1), None)
+                            break
+                    if ended:
+                        break
+            if ended:
+                break
+            p = _exp(logw_sub - log_w)
+            note("merge", float(u_merge[depth]), p, max(float(u_merge[depth]), p), bool(u_merge[depth] < p))
+            if u_merge[depth] < p:
+                prop = cand
+            log_w = _logaddexp(log_w, logw_sub)
+            rho = rho + rho_sub
+            if v > 0:
+                right = (th_m, r_m, g_m)
+            else:
+                left = (th_m, r_m, g_m)
+            depth += 1
+            if turning(rho, left[1]) or turning(rho, right[1]):
+                note("end", "uturn", depth, 0, None)
+                break
+            if depth == D:
+                note("end", "max_depth", depth, 0, None)
+    return prop, {"tree_depth": depth, "n_leapfrog": n_leaf, "accept_stat": sum_acc / n_leaf, "divergent": divergent}
+
+
+def _find_stepsize(logp_grad, th, lp, g, minv, eps, r0):
+    """the initial step-size search of `_hmc` (AdvancedHMC.find_good_stepsize) from (th, lp, g) with the momentum r0"""
+    def one_step(e):
+        r = r0 + 0.5 * e * g
+        lp1, g1 = logp_grad(th + e * minv * r)
+        r = r + 0.5 * e * g1
+        return -lp1 + 0.5 * np.sum(minv * r * r)
+
+    h0 = -lp + 0.5 * np.sum(minv * r0 * r0)
+    d = h0 - one_step(eps)
+    direction = 1.0 if (np.isfinite(d) and d > np.log(0.8)) else -1.0
+    for _ in range(40):
+        eps *= 2.0 ** direction
+        d = h0 - one_step(eps)
+        if not np.isfinite(d):
+            d = -np.inf
+        if (direction > 0) == (d <= np.log(0.8)):
+            break
+    return eps
+
+
+def _nuts(logp_grad, theta0, draw_samples, max_depth, eps0, target, rng, n_adapts=None, transition=None, set_metric=None, init_chain=None, chunk=256):
+    """NUTS ([3P] AdvancedHMC.NUTS(delta)) with `_hmc`'s step-size search, dual averaging — on the tree's accept_stat — and windowed diagonal
+    metric during the first n_adapts draws.  transition(n, eps, minv) -> lists of per-draw (th, accept_stat, tree_depth, n_leapfrog,
+    divergent) runs n draws of the chain: by default `_nuts_transition` on the host with z and u from `rng`; `_nuts_device` passes the
+    resident one (and set_metric / init_chain, which tell the device about a new metric / the start)."""
+    n = theta0.size
+    n_adapts = min(draw_samples // 10, 1000) if n_adapts is None else n_adapts
+    th = theta0.astype(np.float64).copy()
+    lp, g = logp_grad(th)
+    minv = np.ones(n)
+    eps = _find_stepsize(logp_grad, th, lp, g, minv, eps0, rng.standard_normal(n) / np.sqrt(minv))
+    if init_chain is not None:
+        init_chain(th)
+    host_state = [(th, lp, g)]
+
+    def host_transition(nd, eps, minv):
+        out = []
+        for _ in range(nd):
+            z, u = rng.standard_normal(n), rng.random(nuts_uniforms(max_depth))
+            host_state[0], st = _nuts_transition(logp_grad, host_state[0], minv, eps, z, u, max_depth)
+            out.append((host_state[0][0].copy(), st["accept_stat"], st["tree_depth"], st["n_leapfrog"], st["divergent"]))
+        return out
+    transition = host_transition if transition is None else transition
+    mu, hbar, log_eps_bar, t0, gamma, kappa = np.log(10 * eps), 0.0, 0.0, 10.0, 0.05, 0.75
+    w0, w1 = int(0.15 * n_adapts), int(0.9 * n_adapts)
+    win, rows = [], []
+    m_count = 0
+    for it in range(min(n_adapts, draw_samples)):
+        row = transition(1, eps, minv)[0]
+        rows.append(row)
+        a = float(row[1])
+        m_count += 1
+        hbar = (1 - 1 / (m_count + t0)) * hbar + (target - a) / (m_count + t0)
+        log_eps = mu - np.sqrt(m_count) / gamma * hbar
+        eta = m_count ** (-kappa)
+        log_eps_bar = eta * log_eps + (1 - eta) * log_eps_bar
+        eps = float(np.exp(log_eps))
+        if w0 <= it < w1:
+            win.append(row[0])
+        if it == w1 - 1 and len(win) >= 8 and n_adapts >= 100:
+            var = np.var(np.asarray(win), axis=0)
+            k = len(win)
+            minv = (k / (k + 5.0)) * var + 1e-3 * (5.0 / (k + 5.0))
+            if set_metric is not None:
+                set_metric(minv)
+            mu, hbar, log_eps_bar, m_count = np.log(10 * eps), 0.0, 0.0, 0
+        if it == n_adapts - 1:
+            eps = float(np.exp(log_eps_bar)) if m_count > 0 else eps
+    while len(rows) < draw_samples:
+        rows.extend(transition(min(int(chunk), draw_samples - len(rows)), eps, minv))
+    col = lambda j, dt: np.asarray([r[j] for r in rows], dtype=dt)
+    return col(0, np.float64), {"acceptance": col(1, np.float64), "step_size": eps, "inv_metric": minv, "n_adapts": n_adapts,
+                                "tree_depth": col(2, np.int64), "n_leapfrog": col(3, np.int64), "divergent": col(4, np.int64)}
+
+
+def _nuts_device(eng, logp_grad, theta0, init_chain, draw_samples, max_depth, eps0, target, rng, seed, n_adapts=None, chunk=256):
+    """`_nuts` with the transitions on the device (Engine.nuts_draws): `_hmc_device`'s structure — `nuts_draws(1, ...)` during adaptation (a
+    new metric goes down through `hmc_set_metric`), then chunks of `chunk`; normals and uniforms from the device generator (`seed`)."""
+    def transition(nd, eps, minv):
+        smp, acc, _, depth, nleap, div = eng.nuts_draws(nd, max_depth, eps, seed)
+        return [(smp[i], float(acc[i]), int(depth[i]), int(nleap[i]), int(div[i])) for i in range(nd)]
+    return _nuts(logp_grad, theta0, draw_samples, max_depth, eps0, target, rng, n_adapts, transition, eng.hmc_set_metric, init_chain, chunk)
+
+
 class LogNormal:
     """[3P] Distributions.LogNormal(mu, sigma) as a parameter prior (`param = [LogNormal(6.0, 0.5)]`, test/PDEBPINN/bpinn_pde__bpinn_pde_inv_i_*.jl:58)."""
 
@@ -235,7 +441,7 @@ class Normal:
 
 def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, bcstd=(0.01,), l2std=(0.05,), phystd=(0.05,), priorsNNw=(0.0, 2.0),
                            param=(), n_leapfrog=30, step_size=0.1, targetacceptancerate=0.8, saveats=(0.1,), numensemble=None, rng=None,
-                           sampler="host", seed=0, ensemble="host", ensemble_derivatives=(), adaptation="host"):
+                           sampler="host", seed=0, ensemble="host", ensemble_derivatives=(), adaptation="host", kernel="hmc", max_depth=10):
     """`ahmc_bayesian_pinn_pde(pde_system, discretization; draw_samples, bcstd, phystd, priorsNNw, Kernel = HMC(0.1, 30), saveats,
     numensemble)` — the forward-problem form of ext/bpinn/PDE_BPINN.jl:371-640: the posterior over the network parameters is
     prior N(priorsNNw[1], priorsNNw[2]^2 I) x physics likelihood (`pinn_loglik_grad`: every leapfrog step is ONE fused device evaluation,
@@ -254,7 +460,12 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
     `pinn_derivative[_f64]` call per draw and numpy.  The default `()` adds nothing.
     `adaptation = "device"` (needs `sampler = "device"`) runs the adaptation draws — dual averaging of the step size, the windowed diagonal
     metric — in ONE `pinn_hmc_warmup` call instead of one `pinn_hmc_draws(1)` round trip per draw; the initial step-size search stays on the
-    host, so both settings start from the same step size; `stats["adaptation"]` says which ran.  The default `"host"` changes nothing."""
+    host, so both settings start from the same step size; `stats["adaptation"]` says which ran.  The default `"host"` changes nothing.
+    `kernel = "nuts"` (the reference's `Kernel = NUTS(delta)`, delta = targetacceptancerate) replaces the fixed-length trajectory by
+    No-U-Turn transitions of at most 2^max_depth - 1 leapfrog steps (`_nuts_transition`; `n_leapfrog` is then unused): on the host with
+    `sampler = "host"`, resident on the device (`pinn_nuts_draws`) with `sampler = "device"`; the warm-up adapts on
+    the tree's accept_stat and stays on the host (`adaptation = "device"` is refused).  `stats` gains "kernel" and, for NUTS, "tree_depth",
+    "n_leapfrog" and "divergent" per draw.  The default `"hmc"` changes nothing."""
     reqs = []
     for r in ensemble_derivatives:
         name, order, axes = r
@@ -269,6 +480,12 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
         raise ValueError(f"adaptation must be \"host\" or \"device\", not {adaptation!r}")
     if adaptation == "device" and sampler != "device":
         raise ValueError("adaptation=\"device\" needs sampler=\"device\": the host sampler adapts on the host")
+    if kernel not in ("hmc", "nuts"):
+        raise ValueError(f"kernel must be \"hmc\" or \"nuts\", not {kernel!r}")
+    if kernel == "nuts" and adaptation == "device":
+        raise ValueError("kernel=\"nuts\" with adaptation=\"device\": the resident warm-up runs fixed-length HMC transitions only; NUTS adapts on the host")
+    if kernel == "nuts" and not 1 <= int(max_depth) <= 10:
+        raise ValueError("max_depth must be in 1..10")
     if rng is None:
         rng = np.random.default_rng() if sampler == "host" else np.random.default_rng(seed)
     rep = npde.symbolic_discretize(pde_system, discretization)
@@ -309,13 +526,20 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
             if not isinstance(pr, (Normal, LogNormal)):
                 raise ValueError("sampler=\"device\": parameter priors must be Normal or LogNormal")
             kinds.append((1 if isinstance(pr, LogNormal) else 0,) + tuple(pr.params()))
-        samples, stats = _hmc_device(eng, logp_grad, theta0, lambda th: eng.hmc_init(th, stds, (mu0, sd0), kinds), int(draw_samples), int(n_leapfrog),
-                                     float(step_size), float(targetacceptancerate), rng, int(seed), adaptation=adaptation)
+        if kernel == "nuts":
+            samples, stats = _nuts_device(eng, logp_grad, theta0, lambda th: eng.hmc_init(th, stds, (mu0, sd0), kinds), int(draw_samples), int(max_depth),
+                                          float(step_size), float(targetacceptancerate), rng, int(seed))
+        else:
+            samples, stats = _hmc_device(eng, logp_grad, theta0, lambda th: eng.hmc_init(th, stds, (mu0, sd0), kinds), int(draw_samples), int(n_leapfrog),
+                                         float(step_size), float(targetacceptancerate), rng, int(seed), adaptation=adaptation)
+    elif kernel == "nuts":
+        samples, stats = _nuts(logp_grad, theta0, int(draw_samples), int(max_depth), float(step_size), float(targetacceptancerate), rng)
     else:
         samples, stats = _hmc(logp_grad, theta0, int(draw_samples), int(n_leapfrog), float(step_size), float(targetacceptancerate), rng)
     stats["sampler"] = sampler
     stats["ensemble"] = ensemble
     stats["adaptation"] = adaptation
+    stats["kernel"] = kernel
     numensemble = int(draw_samples // 3) if numensemble is None else int(numensemble)
     # inference: the last `numensemble` draws on the saveats grid (one spacing per independent variable), per dependent variable
     doms = {str(d.variable): (float(d.domain.lo), float(d.domain.hi)) for d in pde_system.domain}

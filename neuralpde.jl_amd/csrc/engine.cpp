@@ -1253,7 +1253,14 @@ int pinn_set_option(pinn_handle h, const char* name, const char* value) {
         E.lbfgs_chunk = (int)q;
         return 0;
     }
-    return fail("pinn_set_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, lbfgs_chunk)");
+    if (k == "nuts_chunk") {
+        char* end = nullptr;
+        const long q = std::strtol(v.c_str(), &end, 10);
+        if (v.empty() || *end || q < 1 || q > 64) return fail("pinn_set_option: nuts_chunk must be an integer in 1..64, not \"" + v + "\"");
+        E.nuts_chunk = (int)q;
+        return 0;
+    }
+    return fail("pinn_set_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, lbfgs_chunk, nuts_chunk)");
 }
 
 int pinn_get_option(pinn_handle h, const char* name, char* buf, int64_t buflen) {
@@ -1273,6 +1280,7 @@ int pinn_get_option(pinn_handle h, const char* name, char* buf, int64_t buflen) 
     if (k == "f64_chunks") { std::snprintf(buf, (size_t)buflen, "%d", pe::f64_chunks(*h)); return 0; }          // chunks of the largest point set in the last float64 call
     if (k == "adam_path") { std::snprintf(buf, (size_t)buflen, "%s", h->adam_path == 2 ? "persistent" : (h->adam_path == 1 ? "loop" : "none")); return 0; }
     if (k == "lbfgs_chunk") { std::snprintf(buf, (size_t)buflen, "%d", h->lbfgs_chunk); return 0; }
+    if (k == "nuts_chunk") { std::snprintf(buf, (size_t)buflen, "%d", h->nuts_chunk); return 0; }
     if (k == "ens_passes") { std::snprintf(buf, (size_t)buflen, "%d", pe::ens_counter(*h, 0)); return 0; }            // jet passes of the last pinn_derivative_ensemble call
     if (k == "ens_point_passes") { std::snprintf(buf, (size_t)buflen, "%d", pe::ens_counter(*h, 1)); return 0; }      // ... its point passes
     if (k == "ens_scratch_passes") { std::snprintf(buf, (size_t)buflen, "%d", pe::ens_counter(*h, 2)); return 0; }    // ... its jet passes with the images in device scratch
@@ -1281,7 +1289,7 @@ int pinn_get_option(pinn_handle h, const char* name, char* buf, int64_t buflen) 
         std::snprintf(buf, (size_t)buflen, "%.4f %.4f %.4f %.4f %.4f %.4f", ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
         return 0;
     }
-    return fail("pinn_get_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, lbfgs_chunk, grad_health, gemm_delta, adam_path, eval_path, f64_path, f64_merged, f64_chunks, f64_affine, ens_passes, ens_point_passes, ens_scratch_passes, cub_ms)");
+    return fail("pinn_get_option: unknown option \"" + k + "\" (known: gemm, precision, persistent, derivative, integral_nodes, lbfgs_chunk, nuts_chunk, grad_health, gemm_delta, adam_path, eval_path, f64_path, f64_merged, f64_chunks, f64_affine, ens_passes, ens_point_passes, ens_scratch_passes, cub_ms)");
 }
 
 int pinn_set_timing(pinn_handle h, int level, int group) {

@@ -328,6 +328,7 @@ struct pinn_engine {
     pe::HmcState* hmc = nullptr;     // resident HMC sampler state (hmc.cpp; pinn_hmc_init), nullptr = none
     pe::LbfgsState* lbfgs = nullptr; // resident L-BFGS state (lbfgs.cpp; pinn_lbfgs_init), nullptr = none
     int lbfgs_history = 0;           // its history length (pinn_describe)
+    int nuts_chunk = 8;              // option "nuts_chunk": slots pinn_nuts_draws queues between two downloads of its control block, 1..64
     int lbfgs_chunk = 8;             // option "lbfgs_chunk": slots pinn_lbfgs_steps / pinn_bfgs_steps queue between two downloads of the control block, 1..64
     pe::BfgsState* bfgs = nullptr;   // resident dense BFGS state (bfgs.cpp; pinn_bfgs_init), nullptr = none
     pe::EnsState* ens = nullptr;     // buffers of pinn_phi_ensemble (ensemble.cpp), nullptr = none yet

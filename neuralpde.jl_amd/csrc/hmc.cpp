@@ -3,9 +3,11 @@
 // step-size search, dual averaging and the windowed diagonal metric of `_hmc_device`.
 // A leapfrog step = the handle's resident evaluation (resident.hpp: ResidentEval) + ONE update launch (hmc_kernels.hpp); nothing is read back
 // before the single download that ends pinn_hmc_draws.
+// pinn_nuts_draws (section 4.14): No-U-Turn transitions of the same chain — slots of one evaluation + one state-machine launch
+// (nuts_kernels.hpp), queued in chunks of "nuts_chunk"; the control block is all the host reads between chunks.
 // The state has buffers of its own: evaluations and optimiser runs between two calls do not touch the chain, and the chain does not touch them.
 #include "resident.hpp"
-#include "hmc_kernels.hpp"
+#include "nuts_kernels.hpp"
 
 using namespace pe;
 
@@ -19,6 +21,11 @@ struct pe::HmcState {
     double* d_r0 = nullptr; double* d_steps = nullptr;      // the search's momentum [P]; the warm-up's step sizes [n_adapts + 1]
     size_t samples_cap = 0, stat_cap = 0, mom_cap = 0, uni_cap = 0, r0_cap = 0, steps_cap = 0;
     unsigned long long draws = 0;        // draw counter of the generator (advanced per completed draw, whatever supplies momenta and uniforms)
+    // NUTS (allocated by the first pinn_nuts_draws)
+    double* d_tree = nullptr;            // [(12 + 2 MAX_DEPTH) P]: edges (theta, r, g) x 2 | candidates (theta, g) x 2 | rho | rho_sub | r_ck | rho_ck
+    nuts::Ctl* d_nctl = nullptr;
+    int* d_istat = nullptr;              // [3 ndraws]: tree_depth | n_leapfrog | divergent
+    size_t istat_cap = 0;
 };
 
 namespace {
@@ -29,6 +36,7 @@ void hmc_release(HmcState* H) {
     plat_free(H->d_state); plat_free(H->d_tab); plat_free(H->d_kind);
     plat_free(H->d_samples); plat_free(H->d_stat); plat_free(H->d_mom); plat_free(H->d_uni);
     plat_free(H->d_r0); plat_free(H->d_steps);
+    plat_free(H->d_tree); plat_free(H->d_nctl); plat_free(H->d_istat);
     delete H;
 }
 
@@ -192,6 +200,72 @@ int pinn_hmc_draws(pinn_handle h, int ndraws, int n_leapfrog, double eps, uint64
     }
     if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * P, E.stream)) || plat_d2h(accept_prob, d_acc, sizeof(double) * nd, E.stream) ||
         plat_d2h(logp, d_lp, sizeof(double) * nd, E.stream))
+        return fail(std::string(who) + ": D2H copy failed");
+    if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    return 0;
+}
+
+int pinn_nuts_draws(pinn_handle h, int ndraws, int max_depth, double eps, double delta_max, uint64_t seed, const double* normals, const double* uniforms,
+                    double* samples, int64_t p, double* accept_stat, double* logp, int* tree_depth, int* n_leapfrog, int* divergent) {
+    const char* who = "pinn_nuts_draws";
+    if (!h || !accept_stat || !logp || !tree_depth || !n_leapfrog || !divergent) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who)) return 1;
+    if (ndraws < 1) return fail(std::string(who) + ": ndraws must be at least 1");
+    if (max_depth < 1 || max_depth > nuts::MAX_DEPTH) return fail(std::string(who) + ": max_depth must be in 1.." + std::to_string(nuts::MAX_DEPTH));
+    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(std::string(who) + ": the step size eps must be positive and finite");
+    if (!(delta_max > 0.0) || !std::isfinite(delta_max)) return fail(std::string(who) + ": delta_max must be positive and finite");
+    HmcState& H = *E.hmc;
+    DeviceScope scope(E.device);
+    H.a.th_eval64 = H.ev.theta64(E);
+    const size_t P = (size_t)p, nd = (size_t)ndraws, nu = (size_t)(2 * max_depth + (1 << max_depth) - 1);
+    if (!H.d_tree) H.d_tree = (double*)plat_malloc(sizeof(double) * (12 + 2 * nuts::MAX_DEPTH) * P);
+    if (!H.d_nctl) H.d_nctl = (nuts::Ctl*)plat_malloc(sizeof(nuts::Ctl));
+    if (!H.d_tree || !H.d_nctl || (samples && !dev_grow(H.d_samples, H.samples_cap, nd * P, E.stream)) || !dev_grow(H.d_stat, H.stat_cap, 2 * nd, E.stream) ||
+        !dev_grow(H.d_istat, H.istat_cap, 3 * nd, E.stream) ||
+        (normals && !dev_grow(H.d_mom, H.mom_cap, nd * P, E.stream)) || (uniforms && !dev_grow(H.d_uni, H.uni_cap, nd * nu, E.stream)))
+        return fail(std::string(who) + ": device allocation failed");
+    nuts::Ctl ctl;
+    std::memset(&ctl, 0, sizeof ctl);
+    ctl.status = nuts::ST_RUN;
+    ctl.fresh = 1;
+    if ((normals && plat_h2d(H.d_mom, normals, sizeof(double) * nd * P, E.stream)) || (uniforms && plat_h2d(H.d_uni, uniforms, sizeof(double) * nd * nu, E.stream)) ||
+        plat_h2d(H.d_nctl, &ctl, sizeof ctl, E.stream))
+        return fail(std::string(who) + ": H2D copy failed");
+    nuts::Tree q;
+    std::memset(&q, 0, sizeof q);
+    q.ctl = H.d_nctl;
+    double* v = H.d_tree;
+    for (double** f : {&q.th_l, &q.r_l, &q.g_l, &q.th_r, &q.r_r, &q.g_r, &q.th_sc, &q.g_sc, &q.th_tc, &q.g_tc, &q.rho, &q.rho_sub}) { *f = v; v += P; }
+    q.r_ck = v; q.rho_ck = v + nuts::MAX_DEPTH * P;
+    q.normals = normals ? H.d_mom : nullptr; q.uniforms = uniforms ? H.d_uni : nullptr;
+    q.samples = samples ? H.d_samples : nullptr; q.accept_stat = H.d_stat; q.logp = H.d_stat + nd;
+    q.tree_depth = H.d_istat; q.n_leapfrog = H.d_istat + nd; q.divergent = H.d_istat + 2 * nd;
+    q.ndraws = ndraws; q.max_depth = max_depth; q.nu = (int)nu;
+    q.eps = eps; q.delta_max = delta_max;
+    q.seed_lo = (unsigned)seed; q.seed_hi = (unsigned)(seed >> 32); q.ctr0 = (unsigned)H.draws;
+    auto step = [&] {
+        if (H.ev.f64) nuts::launch_step<double>(H.a, q, H.ev.out<double>(), H.ev.sums(P), E.stream);
+        else nuts::launch_step<float>(H.a, q, H.ev.out<float>(), H.ev.sums(P), E.stream);
+    };
+    auto read_ctl = [&] { return plat_d2h(&ctl, H.d_nctl, sizeof ctl, E.stream) || plat_sync(E.stream); };
+    step();                                              // the first draw's momentum and first leaf; every slot after it: evaluation, then judge + propose
+    const long long max_slots = (long long)ndraws * ((1 << max_depth) - 1);      // (a draw has at most 2^D - 1 leaves)
+    for (long long slots = 0; ctl.status == nuts::ST_RUN;) {
+        if (slots >= max_slots) return fail(std::string(who) + ": the transitions did not end within ndraws (2^max_depth - 1) leapfrog steps");
+        for (int s = 0; s < E.nuts_chunk; ++s, ++slots) {
+            if (H.ev.eval(E)) {                          // (the current state only changes when a transition ends: the chain is at its last completed draw)
+                if (!read_ctl()) H.draws += (unsigned long long)ctl.draw;
+                return 1;
+            }
+            step();
+        }
+        if (read_ctl()) return fail(std::string("device error: ") + plat_last_error());
+    }
+    H.draws += nd;
+    if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * P, E.stream)) || plat_d2h(accept_stat, q.accept_stat, sizeof(double) * nd, E.stream) ||
+        plat_d2h(logp, q.logp, sizeof(double) * nd, E.stream) || plat_d2h(tree_depth, q.tree_depth, sizeof(int) * nd, E.stream) ||
+        plat_d2h(n_leapfrog, q.n_leapfrog, sizeof(int) * nd, E.stream) || plat_d2h(divergent, q.divergent, sizeof(int) * nd, E.stream))
         return fail(std::string(who) + ": D2H copy failed");
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     return 0;

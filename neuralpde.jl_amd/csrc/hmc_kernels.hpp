@@ -136,13 +136,9 @@ HMC_DEV void energy_partial(int t, const Args& a, int with_prior, double& kin, d
         }
     }
 }
-// mode 0: H_old = -logp(current) + kin / 2.  mode 1: logp(proposal) from the K sums of squares `sse` and the priors, H_new.
-HMC_DEV void energy_finish(const Args& a, int mode, double kin, double pri, const double* sse) {
+// logp(proposal) from the K sums of squares `sse`, the weights' sum of squares `pri` and the parameter priors at th_prop
+HMC_DEV double logp_from_sums(const Args& a, double pri, const double* sse) {
     HMC_NO_CONTRACT
-    if (mode == 0) {
-        a.sc[SC_H_OLD] = -a.sc[SC_LP_CUR] + 0.5 * kin;
-        return;
-    }
     double ll = 0.0;
     for (int k = 0; k < a.K; ++k) {
         double s = sse[k];
@@ -155,6 +151,16 @@ HMC_DEV void energy_finish(const Args& a, int mode, double kin, double pri, cons
         prior_logpdf_grad(a, j, a.th_prop[a.nn + j], l, d);
         lp += l;
     }
+    return lp;
+}
+// mode 0: H_old = -logp(current) + kin / 2.  mode 1: logp(proposal) from the K sums of squares `sse` and the priors, H_new.
+HMC_DEV void energy_finish(const Args& a, int mode, double kin, double pri, const double* sse) {
+    HMC_NO_CONTRACT
+    if (mode == 0) {
+        a.sc[SC_H_OLD] = -a.sc[SC_LP_CUR] + 0.5 * kin;
+        return;
+    }
+    const double lp = logp_from_sums(a, pri, sse);
     a.sc[SC_LP_PROP] = lp;
     a.sc[SC_H_NEW] = -lp + 0.5 * kin;
 }

@@ -1,5 +1,5 @@
 // qn_kernels.hpp — what the two device-resident quasi-Newton finishers share on the device (lbfgs_kernels.hpp, DESIGN.md section 4.8;
-// bfgs_kernels.hpp, section 4.12; only these two and the host driver qn_host.hpp include it): everything of the iteration except how the direction d = -H g and the curvature
+// bfgs_kernels.hpp, section 4.12; these two and the host driver qn_host.hpp include it, and nuts_kernels.hpp for the execution contexts DevCtx / EmuCtx alone): everything of the iteration except how the direction d = -H g and the curvature
 // update are formed.  The iterate x, its gradient g, the trial point xn, the direction d and a small control block live on the device in double.
 // A control kernel is ONE workgroup of 256 threads and a state machine on the control block:
 //   JUDGE (when an evaluation is pending)   fn = sum_k w_k sums_k / n_norm_k as pinn_lbfgs's `eval` forms it; Armijo: isfinite(fn) && fn <= f + 1e-4 t gd.
