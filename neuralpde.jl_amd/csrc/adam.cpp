@@ -111,7 +111,9 @@ int adam_loop(pinn_engine** es, int ndev, int nsteps, float lr, float beta1, flo
                 if (E.terms[t].sampler != 0) redraw_term(E, E.terms[t], true);
             // from the second step on the packed weight images are already those of the current theta: the update kernel below wrote them
             const bool fused = E.inv_ok && E.d_inv_ptr && std::getenv("PINN_NO_FUSED_ADAM") == nullptr;
-            if (run_loss_grad(E, E.d_opt_theta, E.d_opt_out, term_w, -1, false, nullptr, fused && s > 0)) return 1;
+            EvalRequest rq = EvalRequest::device(E.d_opt_theta, E.d_opt_out, term_w);
+            rq.packed_fresh = fused && s > 0;
+            if (run_loss_grad(E, rq)) return 1;
         }
         if (collective) {
             if (comm_all_reduce(es, ndev, vec.data(), raw.data())) return 1;

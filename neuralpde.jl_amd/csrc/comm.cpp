@@ -290,15 +290,13 @@ int pinn_loss_grad_sharded_device_f64(pinn_handle h, const double* d_theta, cons
         return fail("pinn_loss_grad_sharded_device_f64: the handle belongs to a single-process communicator (pinn_comm_init_all): use pinn_loss_grad_sharded_f64");
     DeviceScope scope(E.device);
     if (check_shards(E)) return 1;
-    plat_stream saved = E.stream;
-    E.stream = (plat_stream)stream;
+    StreamScope on_callers(E, stream);
     int rc = f64_eval_from_device_f64(E, d_theta, term_w, d_out);
     if (!rc) {
         pinn_engine* es[1] = {&E};
         double* vec[1] = {d_out};
         rc = comm_all_reduce_f64(es, 1, vec, E.ntheta + (int64_t)E.terms.size());
     }
-    E.stream = saved;
     return rc;
 }
 
@@ -341,12 +339,12 @@ int pinn_loss_grad_sharded_device(pinn_handle h, const float* d_theta, const flo
     if (!E.comm) return fail("pinn_loss_grad_sharded_device: the handle has no communicator (pinn_comm_init_rank / pinn_comm_init_all)");
     DeviceScope scope(E.device);
     if (check_shards(E)) return 1;
-    plat_stream st = (plat_stream)stream;
-    plat_stream saved = E.stream;
-    E.stream = st;
-    int rc = run_loss_grad(E, d_theta, d_out, term_w, -1, true);
-    E.stream = saved;
-    if (rc) return rc;
+    {
+        StreamScope on_callers(E, stream);
+        EvalRequest rq = EvalRequest::device(d_theta, d_out, term_w);
+        rq.timing = true;
+        if (const int rc = run_loss_grad(E, rq)) return rc;
+    }
     E.timing_valid = E.timing_level >= 2;
     if (!E.comm_per_process && E.comm_size > 1)
         return fail("pinn_loss_grad_sharded_device: the handle belongs to a single-process communicator (pinn_comm_init_all): use pinn_loss_grad_sharded");
@@ -354,12 +352,10 @@ int pinn_loss_grad_sharded_device(pinn_handle h, const float* d_theta, const flo
         pinn_engine* es[1] = {&E};
         float* vec[1] = {d_out};
         double* raw[1] = {E.d_lossraw};
-        E.stream = st;
-        rc = comm_all_reduce(es, 1, vec, raw);
-        E.stream = saved;
-        if (rc) return rc;
+        StreamScope on_callers(E, stream);               // (the all-reduce goes out on the handle's stream)
+        if (const int rc = comm_all_reduce(es, 1, vec, raw)) return rc;
     }
-    sums_from_double(d_out + E.ntheta, E.d_lossraw, (int)E.terms.size(), st);      // the exact (double) sums replace the float-summed ones
+    sums_from_double(d_out + E.ntheta, E.d_lossraw, (int)E.terms.size(), (plat_stream)stream);     // the exact (double) sums replace the float-summed ones
     return 0;
 }
 
@@ -381,7 +377,7 @@ int pinn_loss_grad_sharded(pinn_handle* hs, int ndev, const float* theta, int64_
         pinn_engine& E = *hs[i];
         DeviceScope scope(E.device);
         if (check_shards(E) || upload_theta(E, theta, p)) return 1;
-        if (run_loss_grad(E, E.d_theta, E.d_out, term_w, -1, false)) return 1;
+        if (run_loss_grad(E, EvalRequest::device(E.d_theta, E.d_out, term_w))) return 1;
     }
     // one grouped all-reduce of [gradient | sums] across the devices, each rank's call on that rank's stream
     {

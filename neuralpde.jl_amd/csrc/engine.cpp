@@ -7,6 +7,7 @@
 // and what it does per optimiser iteration (src/discretize.jl:567-598).
 #include "resident.hpp"
 #include "aux_kernels.hpp"
+#include <unistd.h>      // environ
 
 #ifdef PINN_EMU
 namespace wv {
@@ -136,7 +137,6 @@ void pe::pack_all(pinn_engine& E, const float* d_theta, bool packed_fresh) {
 
 namespace {
 
-// the device section shared by all loss/grad entry points; theta must already be in E.d_theta
 // launch arguments of k_expr for one coupled equation
 aux::ExprArgs expr_args(pinn_engine& E, Coupled& Cp, float scale, float* resid) {
     Term& T = E.terms[Cp.term];
@@ -225,234 +225,332 @@ int upload_int_rule(pinn_engine& E, int q) {
     return 0;
 }
 
-}  // namespace
+// workgroups of a forward-only launch (MODE_FWD / FWDREC / LOSS / RESID) over ntiles tiles: as many as stay resident, at most one per tile
+// (family 1: per four tiles, one per wave)
+int fwd_blocks(const pinn_engine& E, const pk::SpecInfo* spec, int ntiles) {
+    return std::max(1, std::min(E.ncu * spec->WG_FWD, spec->family == 1 ? (ntiles + 3) / 4 : ntiles));
+}
+// where a term sits in a group's term list (the last match; 0: not in it)
+int slot_of_term(const Group& G, int term) {
+    int j = 0;
+    for (size_t q = 0; q < G.terms.size(); ++q) if (G.terms[q] == term) j = (int)q;
+    return j;
+}
+// one = a group's launch arguments narrowed to its term j: that term's tiles alone, from tile 0
+void narrow_to_term(pk::GroupArgs& one, const pk::GroupArgs& ga, int j) {
+    one = ga;
+    one.nterms = 1;
+    one.terms[0] = ga.terms[j];
+    one.terms[0].tile0 = 0;
+    one.ntiles = one.terms[0].ntiles;
+}
 
-// the device section shared by all loss/grad entry points.  d_theta: theta in device memory; d_out: [P + K] floats in
-// device memory.  Launches per evaluation: pack (1 per net) -> fused residual kernel (1 per group, or 1 per MERGED pair of groups)
-// -> reduction (one kernel when a single slab set carries the gradient, else reduce1 -> reduce2).
-// loss_only: MODE_LOSS launches (forward + tape + sums of squares; coupled equations: forward launches + k_expr without adjoints), only
-// the K sums are reduced and d_out[0, P) is left untouched.
-int pe::run_loss_grad(pinn_engine& E, const float* d_theta, float* d_out, const float* term_w, int only_term /* -1 = all */, bool timing,
-                  double* lossraw /* K exact double sums; default: E.d_lossraw */, bool packed_fresh, bool loss_only, float* d_sums) {
-    if (!d_sums) d_sums = d_out + E.ntheta;              // the K sums follow the gradient unless the caller has a buffer of their own (loss-only)
-    if (ensure_points(E)) return 1;
-    const int K = (int)E.terms.size();
-    const bool phase_ev = timing && E.timing_level >= 2;
-    auto group_ev = [&](size_t g) { return timing && E.timing_level >= 1 && (E.timing_group < 0 || E.timing_group == (int)g); };
-    if (phase_ev) plat_event_record(E.ev0, E.stream);
-    pack_all(E, d_theta, packed_fresh);
-    if (phase_ev) plat_event_record(E.ev1, E.stream);
-    aux::Reduce1Args a1;
-    aux::Reduce2Args a2;
-    std::memset(&a1, 0, sizeof a1);
-    std::memset(&a2, 0, sizeof a2);
-    int max_n1 = 1, max_split = 1;
-    auto scale_of = [&](int ti) -> float {
-        const float w = term_w ? term_w[ti] : 1.0f;
-        const bool on = (only_term < 0 || only_term == ti);
-        return on ? (float)(2.0 * (double)w / (double)E.terms[ti].n_norm) : 0.f;
-    };
-    // Fused groups that cannot fill the chip on their own (at most ~1.5 rounds of workgroups, e.g. one rank's share in an
-    // 8-GPU strong-scaling run) are launched concurrently on auxiliary streams; big groups run back to back.
-    int nfused_active = 0;
-    bool all_small = true;
-    for (auto& G : E.groups) {
-        bool on = false;
-        for (int ti : G.terms) on = on || (only_term < 0 || only_term == ti);
-        if (G.kind == 0 && on) {
+// ---- the evaluation (run_loss_grad) in phases ----
+
+// the A/B switches of the launch structure, all read from the environment once per evaluation (the tests switch them on a live handle),
+// and what they come to for this evaluation
+struct EvalSwitches {
+    bool no_merge, no_chain, no_reduce_one, no_reduce_perm;
+    bool concurrent;                 // the fused groups run on auxiliary streams (fork / join by events)
+    bool may_merge;                  // a merged pair of groups may go out as ONE launch
+};
+EvalSwitches read_switches(const pinn_engine& E, const EvalRequest& rq) {
+    EvalSwitches sw = {};
+    bool want_concurrent = false;
+    // a switch is on when its variable is set, to anything (as with getenv); ONE pass over the environment finds all five — this runs in
+    // every evaluation, and five getenv scans cost the host more than the three the evaluation used to make
+    const struct { const char* name; bool* on; } vars[] = {{"NO_MERGE=", &sw.no_merge}, {"NO_CHAIN=", &sw.no_chain},
+        {"NO_REDUCE_ONE=", &sw.no_reduce_one}, {"NO_REDUCE_PERM=", &sw.no_reduce_perm}, {"CONCURRENT_GROUPS=", &want_concurrent}};
+    for (char** e = environ; e && *e; ++e) {
+        if (std::strncmp(*e, "PINN_", 5) != 0) continue;
+        for (const auto& v : vars)
+            if (std::strncmp(*e + 5, v.name, std::strlen(v.name)) == 0) *v.on = true;
+    }
+    // opt-in: on this stack a cross-stream event wait costs 15-20 us, more than the overlap buys (profiles/r01 timeline).  Fused groups that
+    // cannot fill the chip on their own (at most ~1.5 rounds of workgroups, e.g. one rank's share in an 8-GPU strong-scaling run) are then
+    // launched concurrently on auxiliary streams; big groups run back to back.
+    if (want_concurrent) {
+        int nfused_active = 0;
+        bool all_small = true;
+        for (const Group& G : E.groups) {
+            bool on = false;
+            for (int ti : G.terms) on = on || (rq.only_term < 0 || rq.only_term == ti);
+            if (G.kind != 0 || !on) continue;
             ++nfused_active;
             const int per_round = G.max_blocks * (G.spec->family == 2 ? 1 : 4);
             if (2 * G.ga.ntiles > 3 * per_round) all_small = false;
         }
+        sw.concurrent = nfused_active >= 2 && all_small;
     }
-    // opt-in: on this stack a cross-stream event wait costs 15-20 us, more than the overlap buys (profiles/r01 timeline)
-    static const bool want_concurrent = std::getenv("PINN_CONCURRENT_GROUPS") != nullptr;
-    const bool concurrent = want_concurrent && nfused_active >= 2 && all_small;
-    static const bool no_chain = std::getenv("PINN_NO_CHAIN") != nullptr;      // A/B switches
-    const bool no_merge = std::getenv("PINN_NO_MERGE") != nullptr;            // (read per call: the tests switch them)
-    const bool may_merge = !no_merge && !no_chain && !concurrent && only_term < 0;
-    int nforked = 0;
+    sw.may_merge = !sw.no_merge && !sw.no_chain && !sw.concurrent && rq.only_term < 0;
+    return sw;
+}
+
+inline bool term_on(const EvalRequest& rq, int ti) { return rq.only_term < 0 || rq.only_term == ti; }
+// d (w_k L_k) / d (sum of squares): the factor a term's seeds carry (0: the term is switched off in this evaluation)
+float term_scale(const pinn_engine& E, const EvalRequest& rq, int ti) {
+    const float w = rq.term_w ? rq.term_w[ti] : 1.0f;
+    return term_on(rq, ti) ? (float)(2.0 * (double)w / (double)E.terms[ti].n_norm) : 0.f;
+}
+
+// kernel events around a launch group's launch when this evaluation times that group (timing level >= 1); Group::timed says whether it did
+struct GroupTimer {
+    Group& G;
+    const plat_stream st;
+    const bool on;
+    GroupTimer(const pinn_engine& E, const EvalRequest& rq, size_t g, Group& G_, plat_stream st_)
+        : G(G_), st(st_), on(rq.timing && E.timing_level >= 1 && (E.timing_group < 0 || E.timing_group == (int)g)) {
+        if (on) plat_event_record(G.ev_a, st);
+    }
+    ~GroupTimer() {
+        if (on) plat_event_record(G.ev_b, st);
+        G.timed = on;
+    }
+};
+
+// The reduction's arguments: one slot per launch group, then one per coupled equation (the pseudo-group of its k_expr / k_int_expr launch),
+// filled while the launches go out; launch() then sums the slabs and loss partials of the active slots into the caller's arrays.
+struct ReduceSlots {
+    aux::Reduce1Args a1;
+    aux::Reduce2Args a2;
+    const int K;
+    const bool loss_only;
+    int max_n1 = 1, max_split = 1;
     int nslabsets = 0, slabset_group = -1;          // launch groups whose own slab set carries gradient sums in this evaluation
-    if (concurrent) plat_event_record(E.ev_fork, E.stream);
+    bool coupled_active = false;
+
+    ReduceSlots(int K_, bool loss_only_) : K(K_), loss_only(loss_only_) {
+        std::memset(&a1, 0, sizeof a1);
+        std::memset(&a2, 0, sizeof a2);
+    }
+    void slot(int g, double* tmp, float* slabs, double* losspart, int slab, int nblocks, int nsplit, int nent, int nwpb, bool active, bool ent_active) {
+        a1.tmp[g] = tmp; a1.slabs[g] = slabs; a1.losspart[g] = losspart;
+        a1.slab[g] = slab; a1.nblocks[g] = nblocks; a1.nsplit[g] = nsplit; a1.nent[g] = nent; a1.active[g] = active; a1.nwpb[g] = nwpb;
+        a2.tmp[g] = tmp; a2.stride[g] = nent + K; a2.nsplit[g] = nsplit; a2.nent[g] = nent; a2.active[g] = active; a2.ent_active[g] = ent_active;
+    }
+    void count(int nsplit, int nent) {
+        max_n1 = std::max(max_n1, nent / 4 + K);
+        max_split = std::max(max_split, nsplit);
+    }
+    // a group with a launch of its own over `blocks` workgroups (inactive: switched off in this evaluation, nothing is launched); chained: its
+    // gradient sums went onto the head group's slabs; losspart: where the launch writes its loss partials
+    void launched(int g, const Group& G, int blocks, bool active, bool chained, double* losspart) {
+        const int nent = (chained || loss_only) ? 0 : G.nent;
+        // stage-1 chunks: the serial part of the two-stage sum is (blocks / chunks) loads in stage 1 plus (chunks x slab entries per theta
+        // element: 4 per-wave copies in family 1, 1 in the others) in stage 2 — shortest for chunks ~ sqrt(blocks / entries)
+        const int epe = G.spec->family == 1 ? 4 : 1;
+        const int nsplit = std::max(1, std::min(REDUCE_SPLIT, (int)std::ceil(std::sqrt((double)blocks / epe))));
+        const bool ent_active = active && !chained && !loss_only;
+        slot(g, G.d_tmp, G.d_slabs, losspart, G.slab_floats, blocks, nsplit, nent, G.spec->NW, active, ent_active);
+        if (!active) return;
+        if (ent_active) { ++nslabsets; slabset_group = g; }
+        count(nsplit, nent);
+    }
+    // a group whose tiles rode in another group's launch (the tail of a merged pair): its gradient and its loss partials are in the head's buffers
+    void rode(int g, const Group& G) { slot(g, G.d_tmp, G.d_slabs, G.d_losspart, G.slab_floats, 0, 1, 0, G.spec->NW, false, false); }
+    // the pseudo-group of a coupled equation.  active: its term is on and its k_expr / k_int_expr launch carries the term's sums (not the
+    // equation's tail launch); launched: that launch goes out in this evaluation
+    void coupled(int g, const Coupled& Cp, bool active, bool launched) {
+        const int nsplit = std::min(REDUCE_SPLIT, Cp.blocks);
+        const int nent = loss_only ? 0 : 16;
+        slot(g, Cp.d_tmp, Cp.d_pslab, Cp.d_losspart, 16, Cp.blocks, nsplit, nent, 4, active, active && !loss_only);
+        if (launched) count(nsplit, nent);
+    }
+    // a loss-only launch of group g ran `blocks` workgroups: the rows of loss partials it wrote
+    void rows(int g, int blocks) { a1.nblocks[g] = blocks; }
+
+    // one kernel when a single slab set carries the whole gradient (a single network whose launch groups are merged / chained) or only the
+    // K sums are asked for; else reduce1 -> reduce2
+    void launch(pinn_engine& E, const EvalRequest& rq, const EvalSwitches& sw) {
+        float* d_sums = rq.d_sums ? rq.d_sums : rq.d_out + E.ntheta;      // the K sums follow the gradient unless the caller has a buffer of their own (loss-only)
+        a1.K = K;
+        a2.out = rq.d_out; a2.sums = d_sums; a2.lossraw = rq.lossraw ? rq.lossraw : E.d_lossraw;
+        a2.row_ptr = E.d_gr_ptr; a2.row_grp = E.d_gr_grp; a2.row_ent = E.d_gr_ent;
+        a2.ngroups = (int)(E.groups.size() + E.coupled.size()); a2.P = (int)E.ntheta; a2.K = K;
+        a2.skip_grad = loss_only ? 1 : 0;
+        a2.perm = sw.no_reduce_perm ? nullptr : E.d_red_perm;
+        const Group* RG = (nslabsets == 1 && !coupled_active && !loss_only && !sw.no_reduce_one) ? &E.groups[slabset_group] : nullptr;
+        const bool one_kernel = ((RG && RG->d_ent_theta && RG->ent_covers_theta) || (loss_only && !sw.no_reduce_one)) && !aux::reduce_is_small(a1, a2);
+        if (!one_kernel) {
+            aux::launch_reduce(a1, a2, max_n1, max_split, E.stream);
+            return;
+        }
+        aux::ReduceOneArgs ro;
+        std::memset(&ro, 0, sizeof ro);
+        if (RG) { ro.slabs = RG->d_slabs; ro.slab = RG->slab_floats; ro.nblocks = a1.nblocks[slabset_group]; ro.nent = RG->nent; ro.ent_theta = RG->d_ent_theta; }
+        ro.out = rq.d_out; ro.sums = d_sums; ro.lossraw = a2.lossraw; ro.P = (int)E.ntheta; ro.K = K;       // (loss-only: nent = 0, only the K loss blocks run)
+        for (int g = 0; g < a2.ngroups; ++g)
+            if (a1.active[g]) { ro.losspart[ro.nloss] = a1.losspart[g]; ro.nrows[ro.nloss] = a1.nblocks[g] * a1.nwpb[g]; ++ro.nloss; }
+        aux::launch_reduce_one(ro, E.stream);
+    }
+};
+
+// ga = ONE launch for the head group G's tiles and the tail group's of a merged pair: terms and tiles concatenated, the tail's after the
+// head's.  Returns its workgroups.
+int merged_args(pinn_engine& E, const EvalRequest& rq, const Group& G, const MergedUnit& mu, pk::GroupArgs& ga) {
+    const Group& T2 = E.groups[mu.tail];
+    ga = G.ga;
+    for (size_t j = 0; j < T2.terms.size(); ++j) {
+        pk::TermDev td = T2.ga.terms[j];
+        td.tile0 += G.ga.ntiles;
+        td.scale = term_scale(E, rq, T2.terms[j]);
+        ga.terms[G.terms.size() + j] = td;
+    }
+    ga.nterms = (int)(G.terms.size() + T2.terms.size());
+    ga.sub_terms0 = (int)G.terms.size();
+    ga.sub_tiles0 = G.ga.ntiles;
+    ga.ntiles = G.ga.ntiles + T2.ga.ntiles;
+    ga.scratch = mu.d_scratch;
+    ga.scr_stride = mu.pair->SCR;
+    ga.losspart = mu.d_losspart;
+    ga.chain = 0;
+    return std::max(1, std::min(rq.loss_only ? E.ncu * mu.pair->WG_FWD : mu.max_blocks, ga.ntiles));
+}
+
+// every launch group in plan order: its terms' scales and its per-evaluation state (Group::active, launched_by, launched_blocks, ga.slabs,
+// ga.chain), its slot of the reduction, and the launch itself — fused groups (merged with / chained onto an earlier group of their
+// network where the plan and the switches allow) and the forward launches of coupled equations' networks
+void launch_groups(pinn_engine& E, const EvalRequest& rq, const EvalSwitches& sw, ReduceSlots& R) {
+    const bool loss_only = rq.loss_only;
+    int nforked = 0;
+    if (sw.concurrent) plat_event_record(E.ev_fork, E.stream);
     for (size_t g = 0; g < E.groups.size(); ++g) {
         Group& G = E.groups[g];
         bool any = false;
         for (size_t j = 0; j < G.terms.size(); ++j) {
-            G.ga.terms[j].scale = scale_of(G.terms[j]);
-            any = any || (only_term < 0 || only_term == G.terms[j]);
+            G.ga.terms[j].scale = term_scale(E, rq, G.terms[j]);
+            any = any || term_on(rq, G.terms[j]);
         }
         G.active = any;
         G.timed = false;
-        const MergedUnit* mu = (may_merge && G.kind == 0 && G.merged >= 0) ? &E.merged[G.merged] : nullptr;
-        a1.tmp[g] = G.d_tmp; a1.slabs[g] = G.d_slabs; a1.losspart[g] = G.d_losspart;
-        a2.tmp[g] = G.d_tmp;
-        if (mu && (int)g == mu->tail) {
-            // this group's tiles ran in the head's merged launch: its gradient and its loss partials are in the head's buffers
+        const MergedUnit* mu = (sw.may_merge && G.kind == 0 && G.merged >= 0) ? &E.merged[G.merged] : nullptr;
+        if (mu && (int)g == mu->tail) {                  // this group's tiles ran in the head's merged launch
             G.launched_by = mu->head;
             G.launched_blocks = E.groups[mu->head].launched_blocks;
-            a1.active[g] = 0; a2.active[g] = 0; a2.ent_active[g] = 0;
-            a1.slab[g] = G.slab_floats; a1.nblocks[g] = 0; a1.nsplit[g] = 1; a1.nent[g] = 0; a1.nwpb[g] = G.spec->NW;
-            a2.stride[g] = K; a2.nsplit[g] = 1; a2.nent[g] = 0;
+            R.rode((int)g, G);
             continue;
         }
         // chained launch groups: this group's workgroups add their sums onto the slabs the head group (same network, launched
         // earlier on the same stream in this evaluation) has just written, so the reduction reads one slab set, not two
-        const bool chained = any && !loss_only && !no_chain && !concurrent && G.kind == 0 && G.chain_to >= 0 && E.groups[G.chain_to].active &&
+        const bool chained = any && !loss_only && !sw.no_chain && !sw.concurrent && G.kind == 0 && G.chain_to >= 0 && E.groups[G.chain_to].active &&
                              G.blocks <= E.groups[G.chain_to].launched_blocks;
-        const int nent = (chained || loss_only) ? 0 : G.nent;
         G.ga.slabs = chained ? E.groups[G.chain_to].d_slabs : G.d_slabs;
         G.ga.chain = chained ? 1 : 0;
-        // a single-term evaluation (pinn_term_grads) of a fused group launches ONLY that term's tiles: the K per-term gradients then cost
-        // about one full evaluation in total instead of K
         pk::GroupArgs ga_one;
         const pk::GroupArgs* ga_launch = &G.ga;
         int blocks = G.blocks;
-        if (any && only_term >= 0 && G.kind == 0 && G.terms.size() > 1) {
-            ga_one = G.ga;
-            for (size_t j = 0; j < G.terms.size(); ++j)
-                if (G.terms[j] == only_term) ga_one.terms[0] = G.ga.terms[j];
-            ga_one.nterms = 1;
-            ga_one.terms[0].tile0 = 0;
-            ga_one.ntiles = ga_one.terms[0].ntiles;
+        // a single-term evaluation (pinn_term_grads) of a fused group launches ONLY that term's tiles: the K per-term gradients then cost
+        // about one full evaluation in total instead of K
+        if (any && rq.only_term >= 0 && G.kind == 0 && G.terms.size() > 1) {
+            narrow_to_term(ga_one, G.ga, slot_of_term(G, rq.only_term));
             blocks = std::max(1, std::min(G.max_blocks, G.spec->family == 1 ? (ga_one.ntiles + 3) / 4 : ga_one.ntiles));
             ga_launch = &ga_one;
         }
         const bool merged_head = mu && (int)g == mu->head;
         if (merged_head) {
-            // ONE launch for this group's tiles and the tail group's: terms and tiles concatenated, the tail's after the head's
-            const Group& T2 = E.groups[mu->tail];
-            ga_one = G.ga;
-            for (size_t j = 0; j < T2.terms.size(); ++j) {
-                pk::TermDev td = T2.ga.terms[j];
-                td.tile0 += G.ga.ntiles;
-                td.scale = scale_of(T2.terms[j]);
-                ga_one.terms[G.terms.size() + j] = td;
-            }
-            ga_one.nterms = (int)(G.terms.size() + T2.terms.size());
-            ga_one.sub_terms0 = (int)G.terms.size();
-            ga_one.sub_tiles0 = G.ga.ntiles;
-            ga_one.ntiles = G.ga.ntiles + T2.ga.ntiles;
-            ga_one.scratch = mu->d_scratch;
-            ga_one.scr_stride = mu->pair->SCR;
-            ga_one.losspart = mu->d_losspart;
-            a1.losspart[g] = mu->d_losspart;
-            ga_one.chain = 0;
-            blocks = std::max(1, std::min(loss_only ? E.ncu * mu->pair->WG_FWD : mu->max_blocks, ga_one.ntiles));
+            blocks = merged_args(E, rq, G, *mu, ga_one);
             ga_launch = &ga_one;
         }
         G.launched_blocks = blocks;
         G.launched_by = (int)g;
-        // stage-1 chunks: the serial part of the two-stage sum is (blocks / chunks) loads in stage 1 plus (chunks x slab entries per theta
-        // element: 4 per-wave copies in family 1, 1 in the others) in stage 2 — shortest for chunks ~ sqrt(blocks / entries)
-        const int epe = G.spec->family == 1 ? 4 : 1;
-        const int nsplit_g = std::max(1, std::min(REDUCE_SPLIT, (int)std::ceil(std::sqrt((double)blocks / epe))));
-        a1.slab[g] = G.slab_floats; a1.nblocks[g] = blocks; a1.nsplit[g] = nsplit_g; a1.nent[g] = nent; a1.active[g] = any; a1.nwpb[g] = G.spec->NW;
-        a2.stride[g] = nent + K; a2.nsplit[g] = nsplit_g; a2.nent[g] = nent; a2.active[g] = any;
-        a2.ent_active[g] = any && !chained && !loss_only;
+        R.launched((int)g, G, blocks, any, chained, merged_head ? mu->d_losspart : G.d_losspart);
         if (!any) continue;
-        if (a2.ent_active[g]) { ++nslabsets; slabset_group = (int)g; }
-        max_n1 = std::max(max_n1, nent / 4 + K);
-        max_split = std::max(max_split, nsplit_g);
         if (G.kind == 1) {               // coupled: forward launch now, reverse launch after k_expr / the equation's tail launch
-            G.spec->launch(G.ga, (G.use_rec && !loss_only) ? pk::MODE_FWDREC : pk::MODE_FWD,
-                           std::max(1, std::min(E.ncu * G.spec->WG_FWD, G.spec->family == 1 ? (G.ga.ntiles + 3) / 4 : G.ga.ntiles)), E.stream);
+            G.spec->launch(G.ga, (G.use_rec && !loss_only) ? pk::MODE_FWDREC : pk::MODE_FWD, fwd_blocks(E, G.spec, G.ga.ntiles), E.stream);
             continue;
         }
-        if (G.kind == 2) continue;       // tail launch of a coupled equation: after the other networks' forward launches (below)
+        if (G.kind == 2) continue;       // tail launch of a coupled equation: after the other networks' forward launches (launch_coupled)
         plat_stream st = E.stream;
-        const bool forked = concurrent && nforked++ > 0;       // the first fused group stays on the caller's stream
+        const bool forked = sw.concurrent && nforked++ > 0;       // the first fused group stays on the caller's stream
         if (forked) {
             st = E.aux_stream[nforked % 2];
             plat_stream_wait_event(st, E.ev_fork);
         }
-        if (group_ev(g)) plat_event_record(G.ev_a, st);
-        if (merged_head) mu->pair->launch(*ga_launch, loss_only ? pk::MODE_LOSS : pk::MODE_FUSED, blocks, st);
-        else if (loss_only) {
-            const int tiles = ga_launch->ntiles;
-            const int fb = std::max(1, std::min(E.ncu * G.spec->WG_FWD, G.spec->family == 1 ? (tiles + 3) / 4 : tiles));
-            a1.nblocks[g] = fb;                            // rows of loss partials this launch writes
-            G.launched_blocks = fb;
-            G.spec->launch(*ga_launch, pk::MODE_LOSS, fb, st);
-        } else G.spec->launch(*ga_launch, pk::MODE_FUSED, blocks, st);
-        if (group_ev(g)) plat_event_record(G.ev_b, st);
-        G.timed = group_ev(g);
+        {
+            GroupTimer timer(E, rq, g, G, st);
+            if (merged_head) mu->pair->launch(*ga_launch, loss_only ? pk::MODE_LOSS : pk::MODE_FUSED, blocks, st);
+            else if (loss_only) {
+                const int fb = fwd_blocks(E, G.spec, ga_launch->ntiles);
+                R.rows((int)g, fb);
+                G.launched_blocks = fb;
+                G.spec->launch(*ga_launch, pk::MODE_LOSS, fb, st);
+            } else G.spec->launch(*ga_launch, pk::MODE_FUSED, blocks, st);
+        }
         if (forked) {
             plat_event_record(E.ev_join[g], st);
             plat_stream_wait_event(E.stream, E.ev_join[g]);
         }
     }
-    bool coupled_active = false;
+}
+
+// every coupled equation whose networks ran forward above: its slot of the reduction, then its TAIL launch — forward pass of the widest
+// network + the equation's tape (the other networks' jets as source rows) + its reverse sweep in one kernel; it writes the other networks'
+// seeds and carries the term's loss partials and parameter gradients itself, so the pseudo-group stays out of the reduction — or
+// k_expr / k_int_expr over all networks' jets
+void launch_coupled(pinn_engine& E, const EvalRequest& rq, ReduceSlots& R) {
+    const bool loss_only = rq.loss_only;
     for (size_t c = 0; c < E.coupled.size(); ++c) {
         Coupled& Cp = E.coupled[c];
-        const int g = (int)(E.groups.size() + c);
-        const bool on = (only_term < 0 || only_term == Cp.term);
-        const int nsplit = std::min(REDUCE_SPLIT, Cp.blocks);
-        const int nent = loss_only ? 0 : 16;
-        a1.tmp[g] = Cp.d_tmp; a1.slabs[g] = Cp.d_pslab; a1.losspart[g] = Cp.d_losspart;
-        a1.slab[g] = 16; a1.nblocks[g] = Cp.blocks; a1.nsplit[g] = nsplit; a1.nent[g] = nent; a1.active[g] = on; a1.nwpb[g] = 4;
-        a2.tmp[g] = Cp.d_tmp; a2.stride[g] = nent + K; a2.nsplit[g] = nsplit; a2.nent[g] = nent; a2.active[g] = on; a2.ent_active[g] = on && !loss_only;
         bool groups_active = false;
         for (int gi : Cp.groups) groups_active = groups_active || E.groups[gi].active;
+        const bool by_tail = groups_active && Cp.tail >= 0;
+        R.coupled((int)(E.groups.size() + c), Cp, term_on(rq, Cp.term) && !by_tail, groups_active && !by_tail);
         if (!groups_active) continue;
-        coupled_active = true;
-        if (Cp.tail >= 0) {
-            // TAIL launch: forward pass of the widest network + the equation's tape (the other networks' jets as source rows) + its reverse
-            // sweep in one kernel; it writes the other networks' seeds and carries the term's loss partials and parameter gradients
-            // itself, so the k_expr pseudo-group stays out of the reduction
-            Group& G = E.groups[Cp.groups[Cp.tail]];
-            a1.active[g] = 0; a2.active[g] = 0; a2.ent_active[g] = 0;
-            if (group_ev((size_t)Cp.groups[Cp.tail])) plat_event_record(G.ev_a, E.stream);
+        R.coupled_active = true;
+        if (by_tail) {
+            const int gt = Cp.groups[Cp.tail];
+            Group& G = E.groups[gt];
+            GroupTimer timer(E, rq, (size_t)gt, G, E.stream);
             if (loss_only) {
-                const int fb = std::max(1, std::min(E.ncu * G.spec->WG_FWD, G.ga.ntiles));
-                a1.nblocks[Cp.groups[Cp.tail]] = fb;
+                const int fb = fwd_blocks(E, G.spec, G.ga.ntiles);      // (the tail network's kernel is family 2: plan.cpp)
+                R.rows(gt, fb);
                 G.launched_blocks = fb;
                 G.spec->launch(G.ga, pk::MODE_LOSS, fb, E.stream);
             } else G.spec->launch(G.ga, pk::MODE_FUSED, G.blocks, E.stream);
-            if (group_ev((size_t)Cp.groups[Cp.tail])) plat_event_record(G.ev_b, E.stream);
-            G.timed = group_ev((size_t)Cp.groups[Cp.tail]);
-            continue;
-        }
-        max_n1 = std::max(max_n1, nent / 4 + K);
-        max_split = std::max(max_split, nsplit);
-        if (!E.terms[Cp.term].inodes.empty()) {          // integral term: the tail kernel over the site set's jets
-            aux::IntExprArgs ia = int_expr_args(E, Cp, scale_of(Cp.term), nullptr);
+        } else if (!E.terms[Cp.term].inodes.empty()) {          // integral term: the tail kernel over the site set's jets
+            aux::IntExprArgs ia = int_expr_args(E, Cp, term_scale(E, rq, Cp.term), nullptr);
             ia.loss_only = loss_only ? 1 : 0;
             aux::launch_int_expr(ia, Cp.blocks, E.stream);
-            continue;
+        } else {
+            aux::ExprArgs ea = expr_args(E, Cp, term_scale(E, rq, Cp.term), nullptr);    // scale 0 => zero seeds
+            ea.loss_only = loss_only ? 1 : 0;
+            aux::launch_expr(ea, Cp.blocks, E.stream);
         }
-        aux::ExprArgs ea = expr_args(E, Cp, scale_of(Cp.term), nullptr);    // scale 0 => zero seeds
-        ea.loss_only = loss_only ? 1 : 0;
-        aux::launch_expr(ea, Cp.blocks, E.stream);
     }
-    for (size_t g = 0; g < E.groups.size() && !loss_only; ++g) {
+}
+
+// the reverse launches of coupled equations' networks, from the seeds k_expr / the tail launch wrote
+void launch_coupled_reverse(pinn_engine& E, const EvalRequest& rq) {
+    for (size_t g = 0; g < E.groups.size(); ++g) {
         Group& G = E.groups[g];
         if (G.kind != 1 || !G.active) continue;
-        if (group_ev(g)) plat_event_record(G.ev_a, E.stream);
+        GroupTimer timer(E, rq, g, G, E.stream);
         G.spec->launch(G.ga, G.use_rec ? pk::MODE_GRADREC : pk::MODE_GRADIN, G.blocks, E.stream);
-        if (group_ev(g)) plat_event_record(G.ev_b, E.stream);
-        G.timed = group_ev(g);
     }
+}
+
+}  // namespace
+
+// The device section shared by all fp32 loss / gradient entry points: what rq (engine_types.hpp: EvalRequest) asks for, queued on E.stream.
+// Launches per evaluation: pack (1 per net) -> fused residual kernel (1 per group, or 1 per MERGED pair of groups); coupled equations:
+// forward launches, k_expr / k_int_expr / the tail launch, reverse launches -> reduction (one kernel when a single slab set carries the
+// gradient, else reduce1 -> reduce2).  loss_only: MODE_LOSS launches (forward + tape + sums of squares; coupled equations: forward
+// launches + k_expr without adjoints), only the K sums are reduced.  Each phase is one function above; what an evaluation leaves in a
+// Group (active, timed, launched_blocks, launched_by, ga.slabs, ga.chain, the terms' scales) is read afterwards by pinn_group_timing,
+// pinn_group_launched_by, eval_one_launch and the next evaluation's chaining decision.
+int pe::run_loss_grad(pinn_engine& E, const EvalRequest& rq) {
+    if (ensure_points(E)) return 1;
+    const bool phase_ev = rq.timing && E.timing_level >= 2;
+    if (phase_ev) plat_event_record(E.ev0, E.stream);
+    pack_all(E, rq.d_theta, rq.packed_fresh);
+    if (phase_ev) plat_event_record(E.ev1, E.stream);
+    const EvalSwitches sw = read_switches(E, rq);        // (after the pack launches: the device is busy while the host looks)
+    ReduceSlots R((int)E.terms.size(), rq.loss_only);
+    launch_groups(E, rq, sw, R);
+    launch_coupled(E, rq, R);
+    if (!rq.loss_only) launch_coupled_reverse(E, rq);
     if (phase_ev) plat_event_record(E.ev2, E.stream);
-    a1.K = K;
-    a2.out = d_out; a2.sums = d_sums; a2.lossraw = lossraw ? lossraw : E.d_lossraw; a2.row_ptr = E.d_gr_ptr; a2.row_grp = E.d_gr_grp; a2.row_ent = E.d_gr_ent;
-    a2.ngroups = (int)(E.groups.size() + E.coupled.size()); a2.P = (int)E.ntheta; a2.K = K;
-    a2.skip_grad = loss_only ? 1 : 0;
-    a2.perm = std::getenv("PINN_NO_REDUCE_PERM") ? nullptr : E.d_red_perm;
-    // one slab set carries the whole gradient (a single network whose launch groups are merged / chained): one reduction kernel
-    const bool no_reduce_one = std::getenv("PINN_NO_REDUCE_ONE") != nullptr;
-    const Group* RG = (nslabsets == 1 && !coupled_active && !loss_only && !no_reduce_one) ? &E.groups[slabset_group] : nullptr;
-    const bool one_kernel = ((RG && RG->d_ent_theta && RG->ent_covers_theta) || (loss_only && !no_reduce_one)) && !aux::reduce_is_small(a1, a2);
-    if (one_kernel) {
-        aux::ReduceOneArgs ro;
-        std::memset(&ro, 0, sizeof ro);
-        if (RG) { ro.slabs = RG->d_slabs; ro.slab = RG->slab_floats; ro.nblocks = a1.nblocks[slabset_group]; ro.nent = RG->nent; ro.ent_theta = RG->d_ent_theta; }
-        ro.out = d_out; ro.sums = d_sums; ro.lossraw = a2.lossraw; ro.P = (int)E.ntheta; ro.K = K;       // (loss-only: nent = 0, only the K loss blocks run)
-        for (int g = 0; g < a2.ngroups; ++g)
-            if (a1.active[g]) { ro.losspart[ro.nloss] = a1.losspart[g]; ro.nrows[ro.nloss] = a1.nblocks[g] * a1.nwpb[g]; ++ro.nloss; }
-        aux::launch_reduce_one(ro, E.stream);
-    } else {
-        aux::launch_reduce(a1, a2, max_n1, max_split, E.stream);
-    }
+    R.launch(E, rq, sw);
     if (phase_ev) plat_event_record(E.ev3, E.stream);
     // a run-time specialised kernel whose code object could not be produced / loaded at its first launch (jit.cpp: rtc_launch) was NOT launched
     { const std::string e = jit_take_launch_error(); if (!e.empty()) return fail(e); }
@@ -497,6 +595,11 @@ int pinn_create_on(const char* descriptor, int device, pinn_handle* out) {
     if (parse_descriptor(descriptor, *E)) return 1;
     E->terms0 = E->terms;                              // (before the planner rewrites them: the float64 mode evaluates the terms as parsed)
     E->ncu = plat_num_cus();
+#ifdef PINN_EMU
+    // the emulated device has 2 CUs unless $PINN_EMU_CUS (1..64) says otherwise: launch decisions that weigh a group against the chip (the
+    // concurrent path takes groups of at most 1.5 rounds of workgroups) are out of a small problem's reach on 2
+    if (const char* cus = std::getenv("PINN_EMU_CUS")) E->ncu = std::max(1, std::min(64, std::atoi(cus)));
+#endif
     E->stream = plat_stream_create();
     const int K = (int)E->terms.size();
     E->d_theta = (float*)plat_malloc(sizeof(float) * E->ntheta);
@@ -694,7 +797,10 @@ extern "C++" int pe::eval_and_sync(pinn_engine& E, float* d_out, const float* te
     const int one = eval_one_launch(E, d_out, term_w, lossraw);
     if (one == 1) return 1;
     if (one == 0) { E.eval_path = 2; return 0; }     // (2: not a small problem, or timed out — the stand-alone kernels run / repeat the evaluation)
-    if (run_loss_grad(E, E.d_theta, d_out, term_w, -1, timing, lossraw, false, false)) return 1;
+    EvalRequest rq = EvalRequest::device(E.d_theta, d_out, term_w);
+    rq.timing = timing;
+    rq.lossraw = lossraw;
+    if (run_loss_grad(E, rq)) return 1;
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     return 0;
 }
@@ -709,7 +815,10 @@ static int loss_grad_f32(pinn_engine& E, const float* theta, const float* term_w
     if (grad) {
         if (eval_and_sync(E, E.hp_out, term_w, E.hp_raw, true)) return 1;                                            // results land in pinned host memory
     } else {
-        if (run_loss_grad(E, E.d_theta, E.hp_out, term_w, -1, true, E.hp_raw, false, true)) return 1;
+        EvalRequest rq = EvalRequest::host_entry(E, term_w);
+        rq.timing = true;
+        rq.loss_only = true;
+        if (run_loss_grad(E, rq)) return 1;
         if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     }
     E.timing_valid = E.timing_level >= 2;
@@ -759,7 +868,7 @@ static int loglik_f32(pinn_engine& E, const float* theta, const double* stds, do
     std::vector<float> w(K);
     for (int k = 0; k < K; ++k) w[k] = (float)((double)E.terms[k].n_norm / (2.0 * stds[k] * stds[k]));
     if (upload_theta(E, theta, E.ntheta)) return 1;
-    if (run_loss_grad(E, E.d_theta, E.hp_out, w.data(), -1, false, E.hp_raw)) return 1;
+    if (run_loss_grad(E, EvalRequest::host_entry(E, w.data()))) return 1;
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     loglik_from_sse(E, stds, E.hp_raw, loglik, grad_std);
     if (grad_theta)
@@ -787,7 +896,9 @@ static int term_grads_f32(pinn_engine& E, const float* theta, double* term_losse
     const int64_t p = E.ntheta;
     if (upload_theta(E, theta, p)) return 1;
     for (int k = 0; k < K; ++k) {
-        if (run_loss_grad(E, E.d_theta, E.hp_out, nullptr, k, false, E.hp_raw)) return 1;
+        EvalRequest rq = EvalRequest::host_entry(E, nullptr);
+        rq.only_term = k;
+        if (run_loss_grad(E, rq)) return 1;
         if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
         std::memcpy(term_grads + (size_t)k * p, E.hp_out, sizeof(float) * p);
         if (term_losses) term_losses[k] = E.hp_raw[k] / (double)E.terms[k].n_norm;
@@ -799,13 +910,14 @@ int pinn_loss_grad_device(pinn_handle h, const float* d_theta, const float* term
     if (!h || !d_theta || !d_out) return fail("pinn_loss_grad_device: null argument");
     pinn_engine& E = *h;
     DeviceScope scope(E.device);
-    const int K = (int)E.terms.size();
-    plat_stream user = (plat_stream)stream;
-    plat_stream saved = E.stream;
-    E.stream = user;     // NULL is the (legacy) default stream — e.g. torch's current stream
-    // float64 mode (r05): the double kernels between a device-side widening of theta and narrowing of [gradient | sums]
-    int rc = E.f64 ? f64_eval_from_device_f32(E, d_theta, term_w, d_out, true) : run_loss_grad(E, d_theta, d_out, term_w, -1, true);
-    E.stream = saved;
+    int rc;
+    {
+        StreamScope on_callers(E, stream);
+        EvalRequest rq = EvalRequest::device(d_theta, d_out, term_w);
+        rq.timing = true;
+        // float64 mode (r05): the double kernels between a device-side widening of theta and narrowing of [gradient | sums]
+        rc = E.f64 ? f64_eval_from_device_f32(E, d_theta, term_w, d_out, true) : run_loss_grad(E, rq);
+    }
     if (rc && g_err.empty()) return fail("pinn_loss_grad_device failed");
     E.timing_valid = (rc == 0) && E.timing_level >= 2;
     return rc;
@@ -816,10 +928,11 @@ int pinn_loss_grad_device_f64(pinn_handle h, const double* d_theta, const float*
     pinn_engine& E = *h;
     if (!E.f64) return fail("pinn_loss_grad_device_f64: the handle is not in the float64 evaluation mode (pinn_set_option(h, \"precision\", \"f64\"))");
     DeviceScope scope(E.device);
-    plat_stream saved = E.stream;
-    E.stream = (plat_stream)stream;
-    const int rc = f64_eval_from_device_f64(E, d_theta, term_w, d_out);
-    E.stream = saved;
+    int rc;
+    {
+        StreamScope on_callers(E, stream);
+        rc = f64_eval_from_device_f64(E, d_theta, term_w, d_out);
+    }
     if (rc && g_err.empty()) return fail("pinn_loss_grad_device_f64 failed");
     return rc;
 }
@@ -828,11 +941,15 @@ int pinn_loss_device(pinn_handle h, const float* d_theta, float* d_sums, void* s
     if (!h || !d_theta || !d_sums) return fail("pinn_loss_device: null argument");
     pinn_engine& E = *h;
     DeviceScope scope(E.device);
-    plat_stream saved = E.stream;
-    E.stream = (plat_stream)stream;
-    int rc = E.f64 ? f64_eval_from_device_f32(E, d_theta, nullptr, d_sums, false)
-                   : run_loss_grad(E, d_theta, nullptr, nullptr, -1, false, nullptr, false, true, d_sums);      // loss-only: no gradient vector at all
-    E.stream = saved;
+    int rc;
+    {
+        StreamScope on_callers(E, stream);
+        EvalRequest rq;                                  // loss-only: no gradient vector at all
+        rq.d_theta = d_theta;
+        rq.loss_only = true;
+        rq.d_sums = d_sums;
+        rc = E.f64 ? f64_eval_from_device_f32(E, d_theta, nullptr, d_sums, false) : run_loss_grad(E, rq);
+    }
     if (rc && g_err.empty()) return fail("pinn_loss_device failed");
     return rc;
 }
@@ -870,28 +987,19 @@ extern "C++" int pe::residual_device(pinn_engine& E, int term) {
         Coupled& Cp = E.coupled[T.coupled];
         for (int gi : Cp.groups) {
             Group& G = E.groups[gi];
-            pk::GroupArgs ga = G.ga;
-            int j = 0;
-            for (size_t q = 0; q < G.terms.size(); ++q) if (G.terms[q] == term) j = (int)q;
-            ga.nterms = 1;
-            ga.terms[0] = G.ga.terms[j];
-            ga.terms[0].tile0 = 0;
-            ga.ntiles = ga.terms[0].ntiles;
-            G.spec->launch(ga, pk::MODE_FWD, std::max(1, std::min(E.ncu * G.spec->WG_FWD, G.spec->family == 1 ? (ga.ntiles + 3) / 4 : ga.ntiles)), E.stream);
+            pk::GroupArgs ga;
+            narrow_to_term(ga, G.ga, slot_of_term(G, term));
+            G.spec->launch(ga, pk::MODE_FWD, fwd_blocks(E, G.spec, ga.ntiles), E.stream);
         }
         if (!T.inodes.empty()) aux::launch_int_expr(int_expr_args(E, Cp, 0.f, T.d_resid), Cp.blocks, E.stream);
         else aux::launch_expr(expr_args(E, Cp, 0.f, T.d_resid), Cp.blocks, E.stream);
         return 0;
     }
     Group& G = E.groups[T.group];
-    pk::GroupArgs ga = G.ga;
-    ga.nterms = 1;
-    ga.terms[0] = G.ga.terms[T.slot_in_group];
-    ga.terms[0].tile0 = 0;
+    pk::GroupArgs ga;
+    narrow_to_term(ga, G.ga, T.slot_in_group);
     ga.terms[0].out = T.d_resid;
-    ga.ntiles = ga.terms[0].ntiles;
-    const int blocks = std::max(1, std::min(E.ncu * G.spec->WG_FWD, G.spec->family == 1 ? (ga.ntiles + 3) / 4 : ga.ntiles));
-    G.spec->launch(ga, pk::MODE_RESID, blocks, E.stream);
+    G.spec->launch(ga, pk::MODE_RESID, fwd_blocks(E, G.spec, ga.ntiles), E.stream);
     return 0;
 }
 
@@ -949,8 +1057,7 @@ static int forward_jets(pinn_engine& E, int net, const pk::SpecInfo* sp, const f
         ga.dgm_npad = ga.ntiles * 64;
         ga.dgm_nparams = N.nparams();
     }
-    const int blocks = std::max(1, std::min(E.ncu * sp->WG_FWD, sp->family == 1 ? (ga.ntiles + 3) / 4 : ga.ntiles));
-    sp->launch(ga, pk::MODE_FWD, blocks, E.stream);
+    sp->launch(ga, pk::MODE_FWD, fwd_blocks(E, sp, ga.ntiles), E.stream);
     { const std::string le = jit_take_launch_error(); if (!le.empty()) return fail("forward kernel: " + le); }
     return 0;
 }
@@ -1151,11 +1258,11 @@ extern "C++" int pe::gemm_auto_check(pinn_engine& E, const float* d_theta, const
     const int64_t P = E.ntheta;
     const int start = E.gemm;
     std::vector<float> ga((size_t)P), gb((size_t)P);
-    if (run_loss_grad(E, d_theta, E.d_out, term_w, -1, false)) return 1;
+    if (run_loss_grad(E, EvalRequest::device(d_theta, E.d_out, term_w))) return 1;
     if (plat_d2h(ga.data(), E.d_out, sizeof(float) * P, E.stream) || plat_sync(E.stream)) return fail("D2H copy failed");
     if (replan_gemm(E, start == pk::GEMM_SPLIT ? pk::GEMM_FP32 : pk::GEMM_SPLIT)) return 1;
     if (E.gemm == start) return 0;                       // (the twin could not be built: the handle stays where it was)
-    if (run_loss_grad(E, d_theta, E.d_out, term_w, -1, false)) return 1;
+    if (run_loss_grad(E, EvalRequest::device(d_theta, E.d_out, term_w))) return 1;
     if (plat_d2h(gb.data(), E.d_out, sizeof(float) * P, E.stream) || plat_sync(E.stream)) return fail("D2H copy failed");
     const std::vector<float>& gs = start == pk::GEMM_SPLIT ? ga : gb;      // split / fp32 gradients
     const std::vector<float>& gf = start == pk::GEMM_SPLIT ? gb : ga;

@@ -351,8 +351,31 @@ int lower_sexpr_term(const SexprContext& C, const std::vector<std::string>& indv
 void analyse_static(Term& T, int np);
 bool fuse_laplacian(Term& T, int np);
 // engine.cpp (shared with comm.cpp, adam.cpp and the resident solvers' units)
-int run_loss_grad(pinn_engine& E, const float* d_theta, float* d_out, const float* term_w, int only_term, bool timing, double* lossraw = nullptr,
-                  bool packed_fresh = false, bool loss_only = false, float* d_sums = nullptr);
+// One fp32 evaluation, as its caller asks for it: a call site fills the fields it means and leaves the rest at their defaults.
+struct EvalRequest {
+    const float* d_theta = nullptr;  // parameters in device memory (nullptr: E.d_theta)
+    float* d_out = nullptr;          // [P gradient | K sums] in device-visible memory (loss_only: [0, P) is left untouched)
+    const float* term_w = nullptr;   // host, K term weights (nullptr: all 1)
+    int only_term = -1;              // >= 0: this term alone, the others with scale 0 (pinn_term_grads)
+    bool timing = false;             // record the events the handle's timing level asks for
+    double* lossraw = nullptr;       // K exact double sums (nullptr: E.d_lossraw)
+    bool packed_fresh = false;       // the optimiser's update kernel has already written the fp32 weight images
+    bool loss_only = false;          // MODE_LOSS launches, no reverse sweep, only the K sums are reduced
+    float* d_sums = nullptr;         // the K float sums (nullptr: d_out + P)
+    // parameters and results in device memory
+    static EvalRequest device(const float* d_theta, float* d_out, const float* term_w) {
+        EvalRequest rq;
+        rq.d_theta = d_theta; rq.d_out = d_out; rq.term_w = term_w;
+        return rq;
+    }
+    // a host entry point: the uploaded parameters, results straight into the handle's pinned block
+    static EvalRequest host_entry(const pinn_engine& E, const float* term_w) {
+        EvalRequest rq = device(E.d_theta, E.hp_out, term_w);
+        rq.lossraw = E.hp_raw;
+        return rq;
+    }
+};
+int run_loss_grad(pinn_engine& E, const EvalRequest& rq);
 int upload_theta(pinn_engine& E, const float* theta, int64_t p);
 void sums_from_double(float* d_out_sums, const double* d_raw, int K, plat_stream st);      // (float)raw[k] -> out_sums[k], on the stream
 int ensure_points(pinn_engine& E);              // every term has its point set (and per-point data) installed, or the reason in g_err
@@ -436,6 +459,16 @@ struct DeviceScope {
     int prev;
     explicit DeviceScope(int dev) : prev(plat_get_device()) { if (prev != dev) plat_set_device(dev); else prev = -1; }
     ~DeviceScope() { if (prev >= 0) plat_set_device(prev); }
+};
+// an entry point that evaluates on a caller's stream: the handle's work goes there for the duration (NULL is the legacy default stream —
+// e.g. torch's current stream), the handle's own stream is back on every way out
+struct StreamScope {
+    pinn_engine& E;
+    plat_stream saved;
+    StreamScope(pinn_engine& E_, void* stream) : E(E_), saved(E_.stream) { E.stream = (plat_stream)stream; }
+    ~StreamScope() { E.stream = saved; }
+    StreamScope(const StreamScope&) = delete;
+    StreamScope& operator=(const StreamScope&) = delete;
 };
 // f64.cpp: the float64 evaluation mode (pinn_kernels4.hpp)
 int f64_enable(pinn_engine& E);

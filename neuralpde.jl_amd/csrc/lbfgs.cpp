@@ -37,7 +37,9 @@ int pinn_lbfgs(pinn_handle h, double* theta, int64_t p, int maxiters, int histor
         if (grad) {
             if (eval_and_sync(E, E.hp_out, term_w, E.hp_raw, false)) return 1;
         } else {
-            if (run_loss_grad(E, E.d_theta, E.hp_out, term_w, -1, false, E.hp_raw, false, true)) return 1;
+            EvalRequest rq = EvalRequest::host_entry(E, term_w);
+            rq.loss_only = true;
+            if (run_loss_grad(E, rq)) return 1;
             if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
         }
         f = 0.0;

@@ -59,7 +59,12 @@ struct ResidentEval {
             return fail(std::string(who) + ": the handle's precision changed since " + init_name + " (call " + init_name + " again)");
         return 0;
     }
-    int eval(pinn_engine& E) { return f64 ? f64_eval_resident(E, w64.data(), d_ev64) : run_loss_grad(E, d_th32, d_ev32, w32.data(), -1, false, d_raw); }
+    int eval(pinn_engine& E) {
+        if (f64) return f64_eval_resident(E, w64.data(), d_ev64);
+        EvalRequest rq = EvalRequest::device(d_th32, d_ev32, w32.data());
+        rq.lossraw = d_raw;
+        return run_loss_grad(E, rq);
+    }
     template <class T> const T* out() const {            // [gradient | sums] of the last evaluation, T the mode's type
         if constexpr (std::is_same_v<T, double>) return d_ev64;
         else return d_ev32;

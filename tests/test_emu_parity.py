@@ -943,6 +943,55 @@ def test_merged_launch_matches_chained_launches_and_oracle(npde, use_emu, monkey
     assert np.array_equal(l_again, l_m) and np.array_equal(g_again, g_m)
 
 
+def test_unchained_launches_match_chained_launches_and_oracle(npde, use_emu, monkeypatch):
+    """PINN_NO_MERGE=1: the boundary group's launch adds its sums onto the interior group's slabs (chained, one slab set); PINN_NO_CHAIN=1
+    on top: two launches, each onto its own slab set, summed by the two-stage reduction.  The switches are read per evaluation, so one live
+    handle runs all three forms; each form also goes through `check` against the oracle on a handle of its own."""
+    wl = _merge_cfg2(npde)
+    w = [1.0, 2.0, 0.5, 3.0, 1.5]
+    rep, _, _, th = check(npde, wl.pde_system, wl.chains, wl.strategy, wl.theta, weights=w)
+    l_0, g_0 = rep.engine.loss_grad(th, w)
+    monkeypatch.setenv("PINN_NO_MERGE", "1")
+    check(npde, wl.pde_system, wl.chains, wl.strategy, wl.theta, weights=w)
+    l_c, g_c = rep.engine.loss_grad(th, w)
+    assert [g["launched_by"] for g in rep.engine.group_timings()] == [0, 1]
+    monkeypatch.setenv("PINN_NO_CHAIN", "1")
+    check(npde, wl.pde_system, wl.chains, wl.strategy, wl.theta, weights=w)
+    l_n, g_n = rep.engine.loss_grad(th, w)
+    assert [g["launched_by"] for g in rep.engine.group_timings()] == [0, 1]
+    monkeypatch.delenv("PINN_NO_CHAIN")
+    monkeypatch.delenv("PINN_NO_MERGE")
+    np.testing.assert_allclose(l_n, l_c, rtol=1e-12)                # same forward arithmetic, same per-wave partials
+    np.testing.assert_allclose(g_n, g_c, rtol=0, atol=2e-6 * np.abs(g_c).max())
+    l_again, g_again = rep.engine.loss_grad(th, w)
+    assert np.array_equal(l_again, l_0) and np.array_equal(g_again, g_0)
+
+
+def test_concurrent_launch_groups_match_merged_launch_and_oracle(npde, use_emu, monkeypatch):
+    """PINN_CONCURRENT_GROUPS=1: two fused groups that cannot fill the chip on their own go out side by side, the second on an auxiliary stream
+    between a fork and a join event — neither merged nor chained.  Against the default merged launch and, through `check`, the oracle.
+
+    The engine forks only when every fused group fits in 1.5 rounds of workgroups (2 * tiles <= 3 * resident workgroups).  On the MI355X
+    (256 CUs) this problem's groups do.  On the emulation's default device of 2 CUs (4 resident workgroups per group; group 0 has 13 tiles,
+    group 1 has 8) they would not and the evaluation would stay merged, so the handles of this test live on an emulated device of 8 CUs
+    (PINN_EMU_CUS, read by the emulation build only: 26 <= 48 and 16 <= 48)."""
+    monkeypatch.setenv("PINN_EMU_CUS", "8")
+    wl = _merge_cfg2(npde)
+    w = [1.0, 2.0, 0.5, 3.0, 1.5]
+    rep, _, _, th = check(npde, wl.pde_system, wl.chains, wl.strategy, wl.theta, weights=w)
+    l_m, g_m = rep.engine.loss_grad(th, w)
+    assert [g["launched_by"] for g in rep.engine.group_timings()] == [0, 0]
+    monkeypatch.setenv("PINN_CONCURRENT_GROUPS", "1")
+    check(npde, wl.pde_system, wl.chains, wl.strategy, wl.theta, weights=w)
+    l_p, g_p = rep.engine.loss_grad(th, w)
+    assert [g["launched_by"] for g in rep.engine.group_timings()] == [0, 1]
+    monkeypatch.delenv("PINN_CONCURRENT_GROUPS")
+    np.testing.assert_allclose(l_p, l_m, rtol=1e-12)
+    np.testing.assert_allclose(g_p, g_m, rtol=0, atol=2e-6 * np.abs(g_m).max())
+    l_again, g_again = rep.engine.loss_grad(th, w)
+    assert np.array_equal(l_again, l_m) and np.array_equal(g_again, g_m)
+
+
 def test_gemm_mode_switch_on_a_live_handle(npde, use_emu):
     """pinn_set_option(h, "gemm", "fp32" | "split") (include/pinn_hip.h): both kernel sets are in the library; the switch rebuilds the kernel
     plan in place and keeps point sets and optimiser state.  fp32 mode = v_mfma_f32_16x16x4_f32 (an fmaf chain per product); split mode =
