@@ -592,7 +592,7 @@ int pinn_derivative_ensemble(pinn_handle h, int net, const double* thetas, int64
  *   recursion for mixed derivatives and orders > 4) with the steps of get_eps (src/symbolic_utilities.jl:98-103: eps(Float64)^(1/(2+order)),
  *   the TOTAL order's step on every axis, :185), in the reference's order of operations — as value-only forward passes at shifted copies of the
  *   point set, the difference formulas as tape ops, and a reverse sweep through the same combination (one seeded launch per shifted set;
- *   csrc/f64.cpp: f64_stencil_term).  pinn_loss_grad*, pinn_term_grads*, pinn_loglik_grad*, pinn_residual* then return the reference's
+ *   csrc/f64_stencil.cpp: f64_stencil_term).  pinn_loss_grad*, pinn_term_grads*, pinn_loglik_grad*, pinn_residual* then return the reference's
  *   finite-difference numbers instead of exact derivatives: for digit-by-digit comparisons with the reference's generated loss functions
  *   (julia: NeuralPDEHIP.selftest) and with the stencil oracle.  How close two correct implementations of these formulas can be is bounded by the
  *   formulas themselves: u(x +- eps) carries ~1e-16 relative rounding and 1 / eps^2 ~ 7e7 multiplies it — 1e-8 at initialisation, 1e-5 ... 1e-4

@@ -1,4 +1,4 @@
-// adam.cpp — the resident fp32 Adam of the C ABI (pinn_adam_init / _steps / _steps_sharded / _apply / _get; the float64 loop: f64.cpp) and
+// adam.cpp — the resident fp32 Adam of the C ABI (pinn_adam_init / _steps / _steps_sharded / _apply / _get; the float64 loop: f64_adam.cpp) and
 // the host side of the persistent training kernel (pinn_train.hpp): the stand-alone loop, K iterations of a small problem inside one launch,
 // and that kernel's eval_only form behind pe::eval_and_sync.
 #include "resident.hpp"
@@ -9,7 +9,7 @@ using namespace pe;
 
 namespace {
 
-// fp32 optimiser state (float64 mode: f64.cpp keeps its own, in double)
+// fp32 optimiser state (float64 mode: f64_adam.cpp keeps its own, in double)
 int adam_init_f32(pinn_engine& E, const float* theta) {
     const int64_t p = E.ntheta;
     const int K = (int)E.terms.size();
@@ -384,7 +384,7 @@ int pinn_adam_steps(pinn_handle h, int nsteps, float lr, float beta1, float beta
     DeviceScope scope(E.device);
     if (E.comm && !E.comm_per_process && E.comm_size > 1)
         return fail("pinn_adam_steps: the handle belongs to a single-process communicator (pinn_comm_init_all): use pinn_adam_steps_sharded");
-    if (E.f64) {                                         // float64 mode: redraw -> evaluate -> Adam, all in double on the device (f64.cpp)
+    if (E.f64) {                                         // float64 mode: redraw -> evaluate -> Adam, all in double on the device (f64_adam.cpp)
         if (nsteps <= 0) return fail("pinn_adam_steps: nsteps must be positive");
         E.adam_path = 1;
         return f64_adam_steps(E, nsteps, (double)lr, (double)beta1, (double)beta2, (double)eps, term_w, loss_history);
@@ -437,7 +437,7 @@ int pinn_adam_apply(pinn_handle h, const float* grad_and_sums, int64_t n, float 
     DeviceScope scope(E.device);
     const int K = (int)E.terms.size(), P = (int)E.ntheta;
     if (n != (int64_t)P + K) return fail("pinn_adam_apply: the vector must hold P + K floats ([gradient | raw per-term sums])");
-    if (E.f64) {                                         // float64 mode: the optimiser state lives in double (f64.cpp)
+    if (E.f64) {                                         // float64 mode: the optimiser state lives in double (f64_adam.cpp)
         std::vector<double> v(grad_and_sums, grad_and_sums + n);
         return f64_adam_apply(E, v.data(), (double)lr, (double)beta1, (double)beta2, (double)eps, term_w, loss);
     }

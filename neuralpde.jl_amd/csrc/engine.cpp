@@ -1,6 +1,6 @@
 // engine.cpp — host side of the C ABI: handles, point sets and samplers, options, and the evaluation (run_loss_grad and the entry points over
 // it).  Parsing, program passes and the kernel plan are descriptor.cpp, program.cpp and plan.cpp; the communicator comm.cpp; the float64 mode
-// f64.cpp; the resident solvers adam.cpp, hmc.cpp, lbfgs.cpp and ensemble.cpp.  This unit alone sees aux_kernels.hpp.
+// f64.cpp and its f64_*.cpp units; the resident solvers adam.cpp, hmc.cpp, lbfgs.cpp and ensemble.cpp.  This unit alone sees aux_kernels.hpp.
 //
 // Mirrors what the reference does once per `discretize` call on the host
 // (src/discretize.jl:413-767: build loss functions, merge with the strategy, build full_loss_function)

@@ -470,7 +470,8 @@ struct StreamScope {
     StreamScope(const StreamScope&) = delete;
     StreamScope& operator=(const StreamScope&) = delete;
 };
-// f64.cpp: the float64 evaluation mode (pinn_kernels4.hpp)
+// f64.cpp (evaluation), f64_setup.cpp, f64_stencil.cpp, f64_adam.cpp: the float64 evaluation mode (pinn_kernels4.hpp); what those units share
+// among themselves is f64_internal.hpp
 int f64_enable(pinn_engine& E);
 void f64_destroy(pinn_engine& E);
 std::string f64_describe(const pinn_engine& E);

@@ -1,4 +1,4 @@
-// resident.hpp — host plumbing the resident solvers share (hmc.cpp, lbfgs.cpp, bfgs.cpp; the grow-only buffers also adam.cpp, ensemble.cpp, f64.cpp).
+// resident.hpp — host plumbing the resident solvers share (hmc.cpp, lbfgs.cpp, bfgs.cpp; the grow-only buffers also adam.cpp, ensemble.cpp, the f64*.cpp units).
 // Host-only: no kernel translation unit sees it.
 #pragma once
 #include "engine_types.hpp"

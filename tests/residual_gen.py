@@ -1,6 +1,6 @@
 """Seeded generator of random residual programs for tests/test_random_residuals.py: equations assembled from the atoms, coefficients and
 term shapes the planner's rewrites act on (program.cpp: analyse_static, fuse_laplacian; plan.cpp: detect_linear, riding boundary terms,
-coupled / tail / two-launch paths; f64.cpp: f64_affine; sexpr.cpp), so that sign patterns and shared subexpressions nobody wrote by hand
+coupled / tail / two-launch paths; f64_setup.cpp: f64_affine; sexpr.cpp), so that sign patterns and shared subexpressions nobody wrote by hand
 reach them.  Deterministic in (family, seed) through numpy.random.default_rng; plain Python + sympy.
 
     case(npde, family, seed) -> Case(sysm, chains, theta, param_estim, symbolic, record)

@@ -1,4 +1,4 @@
-"""The FLOAT64 evaluation mode (pinn_set_option(h, "precision", "f64"); csrc/pinn_kernels4.hpp, csrc/f64.cpp): the reference's default
+"""The FLOAT64 evaluation mode (pinn_set_option(h, "precision", "f64"); csrc/pinn_kernels4.hpp, csrc/f64*.cpp): the reference's default
 eltype (src/discretize.jl:432-449) on the device.  Same mathematics as the fp32 kernels — exact Taylor jets, residual tape, hand-derived
 reverse sweep — in IEEE double, one lane per point.  Against the float64 oracle's exact-derivative mode the results agree to ROUNDING
 (1e-12 and better): the engine's algorithm and the oracle's autograd are the same function.  That is also the strongest statement this
@@ -914,6 +914,21 @@ def test_f64_periodic_embedding(npde, use_emu):
     assert eng.get_option("derivative") == "exact"
 
 
+def _lorenz(npde):
+    """the reference's Lorenz test (test/NNPDE2/additional_loss__lorenz_system.jl): three equations over different subsets of three networks,
+    three initial conditions, three estimated parameters -> (system, chains, initial parameters)"""
+    (tt,) = npde.parameters("t")
+    sg, rho, beta = npde.parameters("sigma_ rho beta")
+    xv, yv, zv = npde.variables("x y z")
+    D = npde.Differential(tt)
+    eqs = [npde.Eq(D(xv(tt)), sg * (yv(tt) - xv(tt))), npde.Eq(D(yv(tt)), xv(tt) * (rho - zv(tt)) - yv(tt)), npde.Eq(D(zv(tt)), xv(tt) * yv(tt) - beta * zv(tt))]
+    ics = [npde.Eq(xv(0), 1.0), npde.Eq(yv(0), 0.0), npde.Eq(zv(0), 0.0)]
+    lsys = npde.PDESystem(eqs, ics, [npde.In(tt, npde.Interval(0.0, 1.0))], [tt], [xv(tt), yv(tt), zv(tt)], ps=[sg, rho, beta], defaults={sg: 1.0, rho: 1.0, beta: 1.0})
+    chains = [npde.Chain(npde.Dense(1, 12, "tanh"), npde.Dense(12, 12, "sigmoid"), npde.Dense(12, 1)) for _ in range(3)]
+    th0 = np.concatenate([tp.theta_for(c, 40 + i) for i, c in enumerate(chains)])
+    return lsys, chains, th0
+
+
 def test_f64_merged_launches_of_small_problems(npde, use_emu):
     """r06: small problems (the reference's own regime) are bound by one tile's latency per launch, so the terms that share networks, input binding and
     an instantiated jet set ride in ONE tile / dW / reduction launch sequence on the union jet set (csrc/f64.cpp: f64_make_groups; F64Sub in
@@ -972,15 +987,7 @@ def test_f64_merged_launches_of_small_problems(npde, use_emu):
     both(npde.PDESystem([eq], bcs, dom, [t, x, y], [u(t, x, y)]), [chain], lambda: npde.GridTraining(0.25), 21, [1.0, 0.5, 2.0, 1.5, 1.0, 3.0, 0.7], 1)
     # a system whose equations read different subsets of the dependent variables (the reference's Lorenz test, test/NNPDE2/additional_loss__lorenz_system.jl:
     # three networks, estimated parameters): the launch evaluates the union of the members' networks, six terms in one sequence
-    (tt,) = npde.parameters("t")
-    sg, rho, beta = npde.parameters("sigma_ rho beta")
-    xv, yv, zv = npde.variables("x y z")
-    D = npde.Differential(tt)
-    eqs = [npde.Eq(D(xv(tt)), sg * (yv(tt) - xv(tt))), npde.Eq(D(yv(tt)), xv(tt) * (rho - zv(tt)) - yv(tt)), npde.Eq(D(zv(tt)), xv(tt) * yv(tt) - beta * zv(tt))]
-    ics = [npde.Eq(xv(0), 1.0), npde.Eq(yv(0), 0.0), npde.Eq(zv(0), 0.0)]
-    lsys = npde.PDESystem(eqs, ics, [npde.In(tt, npde.Interval(0.0, 1.0))], [tt], [xv(tt), yv(tt), zv(tt)], ps=[sg, rho, beta], defaults={sg: 1.0, rho: 1.0, beta: 1.0})
-    chains = [npde.Chain(npde.Dense(1, 12, "tanh"), npde.Dense(12, 12, "sigmoid"), npde.Dense(12, 1)) for _ in range(3)]
-    th0 = np.concatenate([tp.theta_for(c, 40 + i) for i, c in enumerate(chains)])
+    lsys, chains, th0 = _lorenz(npde)
     res = []
     for merge in (True, False):
         if not merge:
@@ -1007,9 +1014,47 @@ def test_f64_merged_launches_of_small_problems(npde, use_emu):
     assert int(rep.engine.get_option("f64_merged")) == 1        # the four boundary terms together; the 9,000-point interior term on its own
 
 
+def test_f64_merge_switch_on_a_live_handle(npde, use_emu):
+    """PINN_F64_NO_MERGE takes effect at the next call on a LIVE handle, like every other switch of the mode (csrc/f64_setup.cpp:
+    f64_read_switches; the switch is part of what f64.cpp: f64_make_groups keys the grouping on) — no point set is touched in between.  The
+    smallest case of test_f64_merged_launches_of_small_problems (the Lorenz system: six terms, a few dozen points): merged -> term by term -> merged
+    again on one handle; first and third results bit-equal, the second bit-equal to a fresh handle created with the variable set, all = the oracle."""
+    import os
+
+    lsys, chains, th0 = _lorenz(npde)
+    w = [1.0, 2.0, 0.5, 1.5, 3.0, 0.7]
+
+    def handle():
+        return npde.symbolic_discretize(lsys, npde.PhysicsInformedNN(chains, npde.GridTraining(0.05), init_params=th0, param_estim=True))
+
+    def run(eng, th):
+        l, g = eng.loss_grad_f64(th, w)
+        return l, g, int(eng.get_option("f64_merged"))
+
+    assert "PINN_F64_NO_MERGE" not in os.environ
+    rep = handle()
+    th = np.asarray(rep.flat_init_params, dtype=np.float64) + 1e-9
+    first = run(rep.engine, th)
+    os.environ["PINN_F64_NO_MERGE"] = "1"
+    try:
+        second = run(rep.engine, th)
+        fresh = run(handle().engine, th)
+    finally:
+        os.environ.pop("PINN_F64_NO_MERGE", None)
+    third = run(rep.engine, th)
+    assert first[2] >= 1 and second[2] == 0 and fresh[2] == 0 and third[2] == first[2], (first[2], second[2], fresh[2], third[2])
+    for a, b in ((first, third), (second, fresh)):
+        assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+    prob = helpers.oracle_problem(npde, lsys, chains, param_estim=True)
+    ref = po.loss_and_grad(prob, th, rep.pde_train_sets + rep.bcs_train_sets, weights=w, mode="exact")
+    for l, g, _ in (first, second, fresh, third):
+        le, g2, gi = helpers.rel_errors(l, g, ref)
+        assert le.max() < EXACT and g2 < EXACT and gi < EXACT, (le, g2, gi)
+
+
 def test_f64_affine_residual_fast_path(npde, use_emu):
     """r06: residuals that are affine in the trial functions with constant coefficients (boundary conditions, Poisson / heat with forcing terms) skip the
-    tape interpreter in the matrix-pipe tile kernel — r = S(point) + sum a_s u_s, S evaluated once per point set on the device (csrc/f64.cpp:
+    tape interpreter in the matrix-pipe tile kernel — r = S(point) + sum a_s u_s, S evaluated once per point set on the device (csrc/f64_setup.cpp:
     f64_affine).  Same numbers as the tape (PINN_F64_NO_LIN=1) to rounding, = the oracle; nonlinear terms, estimated parameters and redrawn sets
     keep the interpreter."""
     import os
