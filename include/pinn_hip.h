@@ -401,6 +401,33 @@ int pinn_nuts_draws(pinn_handle h, int ndraws, int max_depth, double eps, double
                     int* divergent);
 
 /*
+ * Chain-resident HMC: nchains chains of the same posterior in ONE launch, one workgroup per chain — evaluation, kick, drift,
+ * energies and accept between workgroup barriers, no launch per leapfrog step.  Opt-in; the state is the sampler's own: evaluations, pinn_adam_* and
+ * pinn_hmc_* on the same handle leave it alone, and it leaves them alone.  Arithmetic: pinn_hmc_draws's bodies in fp32 mode; the evaluation's tiles
+ * are walked by the chain's four waves, so gradient sums associate as a one-workgroup launch's do.
+ *   pinn_hmc_chains_init   theta: [nchains][p] doubles, chain c starts at row c.  eps, inv_metric (p doubles, NULL: ones), stds (k == pinn_num_terms),
+ *                          the weight prior and the parameter priors (as pinn_hmc_init), n_leapfrog and the generator's seed are shared by the chains
+ *                          and fixed until the next init.  Evaluates logp and its gradient at every start point.
+ *   pinn_hmc_chains_draws  ndraws transitions of every chain in one launch.  momenta: [nchains][ndraws][p] (NULL: r = z / sqrt(inv_metric) from the
+ *                          generator), uniforms: [nchains][ndraws] (NULL: the generator).  The generator is pinn_hmc_draws's, its key of draw counter
+ *                          t mixed with the chain index c as key = mix32(key_t ^ mix32(c * 0xCC9E2D51 + 0x1B873593)) for c > 0: chain 0 is the
+ *                          stream of pinn_hmc_draws.  The draw counter starts at 0 in init and advances by ndraws per call.
+ *   pinn_hmc_chains_get    of the last draws call: samples [nchains][ndraws][p], accept_prob and logp [nchains][ndraws]; the current states: theta
+ *                          [nchains][p], logp_cur [nchains], grad = d logp / d theta [nchains][p].  Every output is nullable.
+ * Covered: one family-1 network of at most 32 hidden units per layer (tanh / sigmoid) whose kernel was compiled ahead of time or by the hipcc back
+ * end, fixed point sets, the fp32 kernels, estimated PDE parameters and data terms.  Refused by name, with the handle left as it was: the float64
+ * mode; device samplers on a term; communicators; several networks or launch groups; sin / swish / per-layer activations; DGM networks, embedded
+ * coordinates, integral terms; more than 2048 parameters (a stated bound: nothing in the kernel depends on it); nchains outside 1..1024; non-positive or non-finite eps, metric, stds; n_leapfrog or ndraws
+ * below 1; calls before init, and calls after the handle's kernel plan changed (init again).
+ */
+int pinn_hmc_chains_init(pinn_handle h, int nchains, const double* theta, int64_t p, double eps, const double* inv_metric, const double* stds, int k,
+                         double nn_mu, double nn_sigma, int n_prior, const int* prior_kind, const double* prior_mu, const double* prior_sigma,
+                         int n_leapfrog, uint64_t seed);
+int pinn_hmc_chains_draws(pinn_handle h, int ndraws, const double* momenta, const double* uniforms);
+int pinn_hmc_chains_get(pinn_handle h, int nchains, int ndraws, int64_t p, double* samples, double* accept_prob, double* logp,
+                        double* theta, double* logp_cur, double* grad);
+
+/*
  * RESIDENT L-BFGS: pinn_lbfgs's iteration with the iterate x, its gradient, the trial point, the direction, the curvature
  * pairs (rings of `history` vectors) and the line search's bookkeeping in HBM in double.  Opt-in: pinn_lbfgs is unchanged.  The host queues SLOTS —
  * one state-machine launch (judge the evaluation just finished: Armijo test, accept with the curvature-pair update or halve the step; propose the

@@ -411,6 +411,33 @@ function nuts_draws!(e::HIPEngine, ndraws::Integer, max_depth::Integer, ϵ::Real
     return samples, acc, lp, depth, nleap, dvg
 end
 
+"""
+    hmc_chains_init(e, θ0, ϵ, stds; nn_prior = (0.0, 2.0), kinds = Cint[], mus = Float64[], sigmas = Float64[], n_leapfrog = 30, inv_metric = nothing, seed = 0)
+    hmc_chains_draws!(e, nchains, ndraws; momenta = nothing, uniforms = nothing) -> (samples P × ndraws × nchains, accept_prob, logp)
+
+Chain-resident HMC (`pinn_hmc_chains_*`, DESIGN.md §4.15): the reference's `nchains` (ext/bpinn/PDE_BPINN.jl:548) as one workgroup per chain, whole
+trajectories in one launch.  `θ0` is P × nchains; step size, metric, stds and priors are shared by the chains.
+"""
+function hmc_chains_init(e::HIPEngine, θ0::AbstractMatrix, ϵ::Real, stds; nn_prior = (0.0, 2.0), kinds = Cint[], mus = Float64[], sigmas = Float64[],
+                         n_leapfrog::Integer = 30, inv_metric = nothing, seed::Integer = 0)
+    θ = Matrix{Float64}(θ0); sd = Vector{Float64}(stds); kd = Vector{Cint}(kinds); mu = Vector{Float64}(mus); sg = Vector{Float64}(sigmas)
+    m = inv_metric === nothing ? Float64[] : Vector{Float64}(inv_metric)
+    GC.@preserve θ sd kd mu sg m check(ccall(sym(:pinn_hmc_chains_init), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64, Cdouble, Ptr{Float64}, Ptr{Float64}, Cint, Cdouble, Cdouble, Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Float64}, Cint, UInt64),
+        e.h, size(θ, 2), θ, e.P, Float64(ϵ), inv_metric === nothing ? Ptr{Float64}(C_NULL) : pointer(m), sd, length(sd), Float64(nn_prior[1]), Float64(nn_prior[2]),
+        length(kd), kd, mu, sg, n_leapfrog, UInt64(seed)), "pinn_hmc_chains_init")
+end
+function hmc_chains_draws!(e::HIPEngine, nchains::Integer, ndraws::Integer; momenta = nothing, uniforms = nothing)
+    r = momenta === nothing ? Float64[] : Vector{Float64}(vec(momenta)); uni = uniforms === nothing ? Float64[] : Vector{Float64}(vec(uniforms))
+    GC.@preserve r uni check(ccall(sym(:pinn_hmc_chains_draws), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}),
+        e.h, ndraws, momenta === nothing ? Ptr{Float64}(C_NULL) : pointer(r), uniforms === nothing ? Ptr{Float64}(C_NULL) : pointer(uni)), "pinn_hmc_chains_draws")
+    samples = zeros(Float64, e.P, ndraws, nchains); acc = zeros(Float64, ndraws, nchains); lp = zeros(Float64, ndraws, nchains)
+    GC.@preserve samples acc lp check(ccall(sym(:pinn_hmc_chains_get), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        e.h, nchains, ndraws, e.P, samples, acc, lp, Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL)), "pinn_hmc_chains_get")
+    return samples, acc, lp
+end
+
 function hmc_get(e::HIPEngine)
     θ = zeros(Float64, e.P); g = zeros(Float64, e.P); lp = Ref{Float64}(0.0)
     GC.@preserve θ g check(ccall(sym(:pinn_hmc_get), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}, Ptr{Float64}),

@@ -40,6 +40,7 @@ SYMBOLS = [
     "pinn_loss_grad_sharded_device_f64", "pinn_loss_grad_sharded_f64",
     "pinn_hmc_init", "pinn_hmc_set_metric", "pinn_hmc_draws", "pinn_hmc_get", "pinn_hmc_find_stepsize", "pinn_hmc_warmup",
     "pinn_nuts_draws",
+    "pinn_hmc_chains_init", "pinn_hmc_chains_draws", "pinn_hmc_chains_get",
     "pinn_lbfgs_init", "pinn_lbfgs_steps", "pinn_lbfgs_get",
     "pinn_bfgs_init", "pinn_bfgs_steps", "pinn_bfgs_get",
     "pinn_phi_ensemble", "pinn_derivative_ensemble",
@@ -132,6 +133,13 @@ class Library:
         try:                                     # (resident NUTS: variant libraries built before it still load)
             ip = C.POINTER(C.c_int)
             L.pinn_nuts_draws.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint64, dp, dp, dp, C.c_int64, dp, dp, ip, ip, ip]
+        except AttributeError:
+            pass
+        try:                                     # (chain-resident HMC: variant libraries built before it still load)
+            L.pinn_hmc_chains_init.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_double, dp, dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), dp, dp,
+                                               C.c_int, C.c_uint64]
+            L.pinn_hmc_chains_draws.argtypes = [vp, C.c_int, dp, dp]
+            L.pinn_hmc_chains_get.argtypes = [vp, C.c_int, C.c_int, C.c_int64, dp, dp, dp, dp, dp, dp]
         except AttributeError:
             pass
         try:                                     # (resident L-BFGS: variant libraries built before it still load)
@@ -738,6 +746,53 @@ class Engine:
         lp, dp = C.c_double(), C.POINTER(C.c_double)
         self.L.check(self.L.lib.pinn_hmc_get(self.h, th.ctypes.data_as(dp), th.size, C.byref(lp), g.ctypes.data_as(dp) if g is not None else None), "pinn_hmc_get")
         return th, lp.value, g
+
+    # ---- chain-resident HMC (include/pinn_hip.h: pinn_hmc_chains_*) ----
+    def hmc_chains_init(self, theta, eps, stds, nn_prior=(0.0, 2.0), param_priors=(), n_leapfrog=30, inv_metric=None, seed=0):
+        """`pinn_hmc_chains_init`: nchains = len(theta) chains, chain c at theta[c]; eps, inv_metric (None: ones), stds, the priors (as `hmc_init`),
+        n_leapfrog and the generator's seed are shared by the chains."""
+        th, sd = np.ascontiguousarray(np.atleast_2d(_f64(theta))), _f64(stds).reshape(-1)
+        if th.ndim != 2 or th.shape[1] != self.P:
+            raise ValueError("theta: nchains x P values")
+        kinds = {"normal": 0, "lognormal": 1}
+        kd = np.ascontiguousarray([kinds.get(str(q[0]).lower(), q[0]) for q in param_priors], dtype=np.int32)
+        mu, sg = _f64([q[1] for q in param_priors]), _f64([q[2] for q in param_priors])
+        m = None if inv_metric is None else _f64(inv_metric).reshape(-1)
+        if m is not None and m.size != self.P:
+            raise ValueError("inv_metric: P values")
+        dp = C.POINTER(C.c_double)
+        self.L.check(self.L.lib.pinn_hmc_chains_init(self.h, th.shape[0], th.ctypes.data_as(dp), self.P, float(eps), m.ctypes.data_as(dp) if m is not None else None,
+                                                     sd.ctypes.data_as(dp), sd.size, float(nn_prior[0]), float(nn_prior[1]),
+                                                     kd.size, kd.ctypes.data_as(C.POINTER(C.c_int)) if kd.size else None,
+                                                     mu.ctypes.data_as(dp) if kd.size else None, sg.ctypes.data_as(dp) if kd.size else None,
+                                                     int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF), "pinn_hmc_chains_init")
+        self._nchains = th.shape[0]
+
+    def hmc_chains_draws(self, ndraws: int, momenta=None, uniforms=None):
+        """`pinn_hmc_chains_draws` + `pinn_hmc_chains_get`: `ndraws` transitions of every chain in one launch, one download.  Returns (samples
+        [nchains x ndraws x P], accept_prob [nchains x ndraws], logp [nchains x ndraws]).  momenta ([nchains x ndraws x P]) / uniforms ([nchains x
+        ndraws]) replace the device generator's draws when given."""
+        nc, nd, dp = int(getattr(self, "_nchains", 0)), max(int(ndraws), 0), C.POINTER(C.c_double)
+        if nc == 0:                              # no successful hmc_chains_init on this handle: the library says so
+            self.L.check(self.L.lib.pinn_hmc_chains_draws(self.h, int(ndraws), None, None), "pinn_hmc_chains_draws")
+        mom = None if momenta is None else _f64(momenta).reshape(-1)
+        uni = None if uniforms is None else _f64(uniforms).reshape(-1)
+        if (mom is not None and mom.size != nc * nd * self.P) or (uni is not None and uni.size != nc * nd):
+            raise ValueError("momenta: nchains x ndraws x P values, uniforms: nchains x ndraws values")
+        self.L.check(self.L.lib.pinn_hmc_chains_draws(self.h, int(ndraws), mom.ctypes.data_as(dp) if mom is not None else None,
+                                                      uni.ctypes.data_as(dp) if uni is not None else None), "pinn_hmc_chains_draws")
+        smp, acc, lp = np.zeros((nc, nd, self.P)), np.zeros((nc, nd)), np.zeros((nc, nd))
+        self.L.check(self.L.lib.pinn_hmc_chains_get(self.h, nc, nd, self.P, smp.ctypes.data_as(dp), acc.ctypes.data_as(dp), lp.ctypes.data_as(dp), None, None, None),
+                     "pinn_hmc_chains_get")
+        return smp, acc, lp
+
+    def hmc_chains_get(self):
+        """`pinn_hmc_chains_get`: (theta [nchains x P], logp [nchains], d logp / d theta [nchains x P]) of the chains' current states"""
+        nc, dp = int(getattr(self, "_nchains", 0)), C.POINTER(C.c_double)
+        th, lp, g = np.zeros((nc, self.P)), np.zeros(nc), np.zeros((nc, self.P))
+        self.L.check(self.L.lib.pinn_hmc_chains_get(self.h, nc, 0, self.P, None, None, None, th.ctypes.data_as(dp), lp.ctypes.data_as(dp), g.ctypes.data_as(dp)),
+                     "pinn_hmc_chains_get")
+        return th, lp, g
 
     def hmc_find_stepsize(self, eps0: float, seed: int = 0, normals=None):
         """`pinn_hmc_find_stepsize`: the initial step-size search from the chain's current state, which it leaves alone.  normals: P standard

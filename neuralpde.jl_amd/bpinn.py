@@ -441,7 +441,7 @@ class Normal:
 
 def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, bcstd=(0.01,), l2std=(0.05,), phystd=(0.05,), priorsNNw=(0.0, 2.0),
                            param=(), n_leapfrog=30, step_size=0.1, targetacceptancerate=0.8, saveats=(0.1,), numensemble=None, rng=None,
-                           sampler="host", seed=0, ensemble="host", ensemble_derivatives=(), adaptation="host", kernel="hmc", max_depth=10):
+                           sampler="host", seed=0, ensemble="host", ensemble_derivatives=(), adaptation="host", kernel="hmc", max_depth=10, nchains=1):
     """`ahmc_bayesian_pinn_pde(pde_system, discretization; draw_samples, bcstd, phystd, priorsNNw, Kernel = HMC(0.1, 30), saveats,
     numensemble)` — the forward-problem form of ext/bpinn/PDE_BPINN.jl:371-640: the posterior over the network parameters is
     prior N(priorsNNw[1], priorsNNw[2]^2 I) x physics likelihood (`pinn_loglik_grad`: every leapfrog step is ONE fused device evaluation,
@@ -465,21 +465,36 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
     No-U-Turn transitions of at most 2^max_depth - 1 leapfrog steps (`_nuts_transition`; `n_leapfrog` is then unused): on the host with
     `sampler = "host"`, resident on the device (`pinn_nuts_draws`) with `sampler = "device"`; the warm-up adapts on
     the tree's accept_stat and stays on the host (`adaptation = "device"` is refused).  `stats` gains "kernel" and, for NUTS, "tree_depth",
-    "n_leapfrog" and "divergent" per draw.  The default `"hmc"` changes nothing."""
+    "n_leapfrog" and "divergent" per draw.  The default `"hmc"` changes nothing.
+    `sampler = "chains"` with `nchains` (the reference's `nchains`, ext/bpinn/PDE_BPINN.jl:548) runs `nchains` chains side by side, one workgroup
+    each, whole trajectories inside one launch (`pinn_hmc_chains_*`).  The warm-up — step size and metric — runs ONCE
+    on the `sampler = "device"` path (`adaptation` as given) from the first start point; the chains share its step size and metric, chain 0
+    starts where the warm-up ended and chain c > 0 at a draw of the weight prior (PDE parameters at their priors' first parameter), and each
+    makes `draw_samples - n_adapts` draws.  `sol.chain_samples` (set by this sampler only) is [nchains x draws x P]; `sol.samples` and the ensemble statistics pool the
+    chains (draw-major, so the last rows hold every chain's last draws).  `numensemble` counts pooled rows and is not scaled by `nchains`: the default
+    `draw_samples // 3` takes about `numensemble / nchains` final draws of every chain.  The chain kernel runs the fp32 kernels: the discretization needs
+    `precision = "f32"` (the float64 mode is refused by name).  `kernel = "nuts"` is refused; `nchains > 1` needs `sampler = "chains"`."""
     reqs = []
     for r in ensemble_derivatives:
         name, order, axes = r
         reqs.append((str(name), int(order), tuple(int(a) for a in axes)))
         if len(reqs[-1][2]) != reqs[-1][1]:
             raise ValueError(f"ensemble_derivatives: order {order} takes {order} axes, not {list(axes)}")
-    if sampler not in ("host", "device"):
-        raise ValueError(f"sampler must be \"host\" or \"device\", not {sampler!r}")
+    if sampler not in ("host", "device", "chains"):
+        raise ValueError(f"sampler must be \"host\" or \"device\" (or \"chains\"), not {sampler!r}")
+    nchains = int(nchains)
+    if nchains < 1:
+        raise ValueError("nchains must be at least 1")
+    if nchains > 1 and sampler != "chains":
+        raise ValueError("nchains > 1 needs sampler=\"chains\": the host and device samplers run one chain")
+    if sampler == "chains" and kernel == "nuts":
+        raise ValueError("sampler=\"chains\" runs fixed-length HMC trajectories; kernel=\"nuts\" needs sampler=\"host\" or \"device\"")
     if ensemble not in ("host", "device"):
         raise ValueError(f"ensemble must be \"host\" or \"device\", not {ensemble!r}")
     if adaptation not in ("host", "device"):
         raise ValueError(f"adaptation must be \"host\" or \"device\", not {adaptation!r}")
-    if adaptation == "device" and sampler != "device":
-        raise ValueError("adaptation=\"device\" needs sampler=\"device\": the host sampler adapts on the host")
+    if adaptation == "device" and sampler not in ("device", "chains"):
+        raise ValueError("adaptation=\"device\" needs sampler=\"device\" or \"chains\": the host sampler adapts on the host")
     if kernel not in ("hmc", "nuts"):
         raise ValueError(f"kernel must be \"hmc\" or \"nuts\", not {kernel!r}")
     if kernel == "nuts" and adaptation == "device":
@@ -520,13 +535,31 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
     theta0 = np.asarray(rep.flat_init_params, dtype=np.float64).copy()
     for j, pr in enumerate(param):
         theta0[nn + j] = pr.params()[0]
-    if sampler == "device":
+    chain_samples = None
+    if sampler in ("device", "chains"):
         kinds = []
         for pr in param:
             if not isinstance(pr, (Normal, LogNormal)):
                 raise ValueError("sampler=\"device\": parameter priors must be Normal or LogNormal")
             kinds.append((1 if isinstance(pr, LogNormal) else 0,) + tuple(pr.params()))
-        if kernel == "nuts":
+        if sampler == "chains":
+            # the shared warm-up on the resident single-chain path, then every chain's draws in launches of `chunk` draws
+            n_adapts = min(int(draw_samples) // 10, 1000)
+            _, stats = _hmc_device(eng, logp_grad, theta0, lambda th: eng.hmc_init(th, stds, (mu0, sd0), kinds), n_adapts, int(n_leapfrog),
+                                      float(step_size), float(targetacceptancerate), rng, int(seed), n_adapts=n_adapts, adaptation=adaptation)
+            starts = np.tile(eng.hmc_get(want_grad=False)[0] if n_adapts else theta0, (nchains, 1))
+            starts[1:, :nn] = mu0 + sd0 * rng.standard_normal((nchains - 1, nn))
+            eng.hmc_chains_init(starts, stats["step_size"], stds, (mu0, sd0), kinds, int(n_leapfrog), stats["inv_metric"], int(seed))
+            parts, accs, left = [], [], int(draw_samples) - n_adapts
+            while left > 0:
+                smp, acc, _ = eng.hmc_chains_draws(min(256, left))
+                parts.append(smp); accs.append(acc)
+                left -= smp.shape[1]
+            chain_samples = np.concatenate(parts, axis=1) if parts else np.zeros((nchains, 0, eng.P))
+            samples = chain_samples.transpose(1, 0, 2).reshape(-1, eng.P)          # pooled, draw-major
+            stats["acceptance"] = np.concatenate(accs, axis=1) if accs else np.zeros((nchains, 0))
+            stats["nchains"] = nchains
+        elif kernel == "nuts":
             samples, stats = _nuts_device(eng, logp_grad, theta0, lambda th: eng.hmc_init(th, stds, (mu0, sd0), kinds), int(draw_samples), int(max_depth),
                                           float(step_size), float(targetacceptancerate), rng, int(seed))
         else:
@@ -583,6 +616,8 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
                           for th in ens_samples[:numensemble]])     # the reference predicts with the FIRST numensemble of its slice (:302)
         ens.append(preds.mean(axis=0)); ens_std.append(preds.std(axis=0)); tps.append(pts)
     sol = BPINNsolution(samples, ens, ens_std, tps, stats)
+    if chain_samples is not None:        # sampler="chains": every chain's own draws, [nchains x draws x P]
+        sol.chain_samples = chain_samples
     if reqs:
         sol.ensemble_derivs, sol.ensemble_derivs_std = ens_d, ens_d_std
     sol.estimated_de_params = [float(ens_samples[:, nn + j].mean()) for j in range(ninv)]

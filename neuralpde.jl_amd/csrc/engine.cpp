@@ -643,6 +643,7 @@ int pinn_destroy(pinn_handle h) {
     pinn_comm_destroy(h);
     plat_sync(E.stream);
     hmc_free(E);
+    chains_free(E);
     lbfgs_free(E);
     bfgs_free(E);
     ens_free(E);

@@ -227,6 +227,7 @@ struct NetPlan {
     int npacked = 0;
 };
 struct HmcState;                     // hmc.cpp
+struct ChainsState;                  // hmc_chains.cpp
 struct LbfgsState;                   // lbfgs.cpp
 struct BfgsState;                    // bfgs.cpp
 struct EnsState;                     // ensemble.cpp
@@ -326,6 +327,7 @@ struct pinn_engine {
     int64_t phi_cap = 0;
     int phi_chan = 0;                // jet channels d_phi_out holds per point
     pe::HmcState* hmc = nullptr;     // resident HMC sampler state (hmc.cpp; pinn_hmc_init), nullptr = none
+    pe::ChainsState* chains = nullptr;   // chain-resident HMC state (hmc_chains.cpp; pinn_hmc_chains_init), nullptr = none
     pe::LbfgsState* lbfgs = nullptr; // resident L-BFGS state (lbfgs.cpp; pinn_lbfgs_init), nullptr = none
     int lbfgs_history = 0;           // its history length (pinn_describe)
     int nuts_chunk = 8;              // option "nuts_chunk": slots pinn_nuts_draws queues between two downloads of its control block, 1..64
@@ -441,6 +443,7 @@ public:
 template <class V, class T> As<V, T> as(T* x, size_t n) { return As<V, T>(x, n); }
 // hmc.cpp, lbfgs.cpp, bfgs.cpp, ensemble.cpp: release the handle's resident solver state / ensemble buffers (nothing to do when there is none)
 void hmc_free(pinn_engine& E);
+void chains_free(pinn_engine& E);
 void lbfgs_free(pinn_engine& E);
 void bfgs_free(pinn_engine& E);
 int bfgs_params(const pinn_engine& E);          // P of the resident BFGS state (pinn_describe), 0 = none

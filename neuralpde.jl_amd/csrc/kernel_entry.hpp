@@ -11,11 +11,13 @@
 typedef struct ihipStream_t* plat_stream;       // (= hipStream_t; only the type of SpecInfo::launch's last parameter matters here)
 #else
 #include "plat.hpp"
+#include "hmc_chain_kernels.hpp"       // (double-precision library calls: ahead-of-time and hipcc-specialised members only)
 #endif
 
 namespace pk {
 
 constexpr int MAX_GEN_CHANNELS = 24;
+struct ChainArgs;                    // hmc_chain_kernels.hpp
 
 struct SpecInfo {
     int family;                      // 1: one wave per tile (pinn_kernels.hpp); 2: neuron-split workgroups (pinn_kernels2.hpp)
@@ -45,13 +47,17 @@ struct SpecInfo {
     void (*launch)(const GroupArgs&, int mode, int blocks, plat_stream);
     // family 1: K optimiser iterations in one launch (pinn_train.hpp: k_train, tanh / sigmoid variants); nullptr: not compiled for this spec
     void (*train)(const GroupArgs&, const TrainArgs&, int blocks, plat_stream);
+    // family 1, at most 32 wide: chain-resident HMC, one workgroup per chain (hmc_chain_kernels.hpp: k_hmc_chains, tanh / sigmoid variants); nullptr: not compiled for this spec
+    void (*chains)(const GroupArgs&, const ChainArgs&, int nchains, plat_stream);
 };
 
 template <class S>
 HD SpecInfo make_info(void (*launch)(const GroupArgs&, int, int, plat_stream), int has_sin = 0,
-                      void (*train)(const GroupArgs&, const TrainArgs&, int, plat_stream) = nullptr) {
+                      void (*train)(const GroupArgs&, const TrainArgs&, int, plat_stream) = nullptr,
+                      void (*chains)(const GroupArgs&, const ChainArgs&, int, plat_stream) = nullptr) {
     SpecInfo s = {};
     s.train = train;
+    s.chains = chains;
     s.has_sin = has_sin;
     s.jit = 0;
     s.act1 = s.act2 = s.dgm_rows = 0;
@@ -125,6 +131,15 @@ __global__ void __launch_bounds__(256, 1) k_train(const GroupArgs ga, const Trai
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     wave_train<S, ACTK>(ga, ta, (int)blockIdx.x, (int)gridDim.x, w, lds_all);
 }
+// nchains HMC chains, one workgroup each (hmc_chain_kernels.hpp); no workgroup waits for another, so any number may queue
+#ifndef __HIPCC_RTC__
+template <class S, int ACTK>
+__global__ void __launch_bounds__(256, 1) k_hmc_chains(const GroupArgs ga, const ChainArgs ca) {
+    __shared__ __attribute__((aligned(16))) float lds_all[S::LDS_WG];
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    wave_hmc_chains<S, ACTK>(ga, ca, (int)blockIdx.x, w, lds_all);
+}
+#endif
 // family 2: two waves per SIMD => at most 256 VGPR+AGPR per lane: two 4-wave workgroups per CU (H = 64), or one 8-wave workgroup
 // (H = 128: LDS 100-150 KB per workgroup)
 template <class S, int MODE, int ACTK>

@@ -513,9 +513,12 @@ DEV vint tr_addr(vint col, vint slot) {
 // ------------------------------------------------------------------------------------------------
 // WTHRU (training kernel, pinn_train.hpp): what other workgroups read inside the launch — gradient slabs, loss partials — is stored write-through,
 // and the weight image, which other workgroups rewrote, is read with agent-scope loads: no fences around the grid barriers
+// `slot` >= 0 (chain-resident HMC, hmc_chain_kernels.hpp): the workgroup's memory — weight image, parameter row, record scratch, gradient slab, loss
+// partials — is slice `slot` of each buffer, whatever its place (blk of nblocks) in the tile walk; -1: slice blk, one image and one row
 template <class S, int MODE, int ACTK, bool WTHRU = false>
-DEV void wave_main(const GroupArgs& ga, int blk, int nblocks, int w, float* lds_wg) {
-    const int wave = blk * 4 + w;
+DEV void wave_main(const GroupArgs& ga, int blk, int nblocks, int w, float* lds_wg, int slot = -1) {
+    const int mem = slot < 0 ? blk : slot;                     // the workgroup's slice of the per-workgroup buffers
+    const int wave = mem * 4 + w;
     float* lds = lds_wg + S::LDS_SHARED + w * S::LDS_PRIV;     // wave-private LDS
     float* lds_sh = lds_wg;                                    // workgroup-shared chunk buffers (COOP)
     constexpr bool BWD = (MODE == MODE_FUSED || MODE == MODE_GRADIN);       // modes that run the reverse sweep
@@ -528,7 +531,8 @@ DEV void wave_main(const GroupArgs& ga, int blk, int nblocks, int w, float* lds_
     const vint g = lane >> 4;
     const vint c = lane & vint(15);
     const vbool g0 = veq(g, 0);
-    const float* P = ga.packed;
+    const float* P = slot < 0 ? ga.packed : ga.packed + (size_t)slot * S::PACKED;
+    const float* prow = slot < 0 ? ga.params : ga.params + (size_t)slot * MAX_PARAMS;
     // the activation kind is a template parameter: every kernel is straight-line code behind its GEMMs (no activation branches for the
     // optimiser to hoist); sin / swish variants are compiled only for the specs registered with them (PINN_INSTANTIATE*_SIN / _SWISH / _SIN_SWISH)
     constexpr int ACLS = act_class(ACTK);
@@ -803,7 +807,7 @@ DEV void wave_main(const GroupArgs& ga, int blk, int nblocks, int w, float* lds_
                     for (int j = 0; j < DT; ++j)
                         lds_store(tv, vint(j * 64) + lane, gload_masked(T.pts, (vint(pbase + 16 * pg) + c) * DT + vint(j), valid[pg]));
                 }
-                for (int j = 0; j < NP; ++j) lds_store(tv, vint((DT + j) * 64) + lane, vfloat(ga.params[j]));
+                for (int j = 0; j < NP; ++j) lds_store(tv, vint((DT + j) * 64) + lane, vfloat(prow[j]));
                 PINN_UNROLL for (int ch = 0; ch < C; ++ch) lds_store(tv, vint((DT + NP + ch) * 64) + lane, U[pg][ch]);
                 for (int j = 0; j < T.nsrc; ++j)
                     lds_store(tv, vint((DT + NP + C + j) * 64) + lane, gload_masked(T.src, vint(j * T.N + pbase + 16 * pg) + c, valid[pg]));
@@ -1055,7 +1059,7 @@ DEV void wave_main(const GroupArgs& ga, int blk, int nblocks, int w, float* lds_
     }
     // per-workgroup slab: [shared section | 4 x per-wave section]; COOP: dW / hidden-bias rows are written by their
     // owner wave into the shared section, everything else (and everything for small nets) is per wave.
-    float* slab_wg = ga.slabs + (size_t)blk * S::SLAB;
+    float* slab_wg = ga.slabs + (size_t)mem * S::SLAB;
     float* mine = slab_wg + S::SH + w * S::PW;
     float* big = S::COOP ? slab_wg : mine;
     const ubuf SLW = ub_make(slab_wg, S::SLAB);
