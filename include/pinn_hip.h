@@ -367,6 +367,30 @@ int pinn_hmc_warmup(pinn_handle h, int n_adapts, int n_leapfrog, double eps0, do
                     double* inv_metric);
 
 /*
+ * DENSE EUCLIDEAN METRIC (AdvancedHMC's DenseEuclideanMetric): the chain of pinn_hmc_init under a full symmetric positive
+ * definite inverse mass matrix M^-1 = L L^T, P <= 4096.  Opt-in: pinn_hmc_init starts diagonal and every diagonal-metric launch is what it was.
+ *   pinn_hmc_set_metric_dense   inv_metric: p x p doubles, row-major (NULL: the identity).  Uploads it, factorises it ON THE DEVICE (blocked Cholesky,
+ *                        the same launches the warm-up uses) and, when every pivot was positive and finite, makes it the chain's metric.
+ *                        pinn_hmc_set_metric switches the chain back to a diagonal metric.
+ *   pinn_hmc_get_metric_dense   M^-1 and the lower factor L (strict upper triangle zero), p x p doubles each; either pointer may be NULL.
+ *   While the chain holds a dense metric, pinn_hmc_draws, pinn_hmc_find_stepsize and pinn_hmc_warmup run
+ *       r = L^-T z (z from the unchanged generator, or the warm-up's / search's `normals`; the `momenta` of pinn_hmc_draws are used as given);
+ *       theta += eps (M^-1 r);  H = -logp + 1/2 r.(M^-1 r);
+ *       and the warm-up's metric event is M^-1 = (k/(k + 5)) cov + 1e-3 (5/(k + 5)) I, cov the population covariance (means first, rows in order)
+ *       of the same window under the same condition, then the factorisation and the dual-averaging restart.  If a pivot of that factorisation is
+ *       not positive and finite the metric before the window stays in force, the call completes with every output valid and returns
+ *       PINN_HMC_METRIC_KEPT instead of 0 (pinn_last_error names the pivot).  pinn_hmc_warmup's `inv_metric` receives diag(M^-1).
+ *   All metric arithmetic is double, sums in a fixed order, no atomics: calls are bit-reproducible.
+ * Refused, with the handle's metric and chain left as they were: calls before pinn_hmc_init; p != ntheta; ntheta > 4096; a non-finite entry;
+ * |a_ij - a_ji| > 1e-12 max|a|; a pivot that is not positive and finite (the message names its index); a handle on a communicator or with a device
+ * sampler; pinn_hmc_get_metric_dense on a chain that holds a diagonal metric.  pinn_nuts_draws and pinn_hmc_chains_init / _draws refuse a handle
+ * whose chain holds a dense metric.
+ */
+#define PINN_HMC_METRIC_KEPT 2
+int pinn_hmc_set_metric_dense(pinn_handle h, const double* inv_metric, int64_t p);
+int pinn_hmc_get_metric_dense(pinn_handle h, double* inv_metric, double* chol, int64_t p);
+
+/*
  * RESIDENT NUTS: the second kernel of the BPINN sampler (`ahmc_bayesian_pinn_pde` with Kernel = NUTS(delta)) — No-U-Turn
  * transitions of the chain of pinn_hmc_init, under the metric of pinn_hmc_set_metric; pinn_hmc_get reads the state afterwards.  Opt-in: pinn_hmc_*
  * and every other path are unchanged.  Multinomial NUTS with the generalised U-turn criterion in iterative form, as neuralpde.jl_amd/bpinn.py

@@ -382,6 +382,26 @@ function hmc_set_metric(e::HIPEngine, inv_metric)
     return nothing
 end
 
+"""
+    hmc_set_metric_dense(e, inv_metric)      # P × P symmetric positive definite; `nothing`: the identity
+    hmc_get_metric_dense(e) -> (M⁻¹, L)      # M⁻¹ = L Lᵀ, L lower triangular
+
+The dense Euclidean metric of the resident chain (`pinn_hmc_set_metric_dense`, DESIGN.md §4.16; AdvancedHMC's `DenseEuclideanMetric`): factorised
+on the device; `hmc_draws`, `hmc_find_stepsize` and `hmc_warmup` then run under it.  `hmc_set_metric` returns to a diagonal metric.
+"""
+function hmc_set_metric_dense(e::HIPEngine, inv_metric)
+    m = inv_metric === nothing ? Float64[] : Vector{Float64}(vec(permutedims(Matrix{Float64}(inv_metric))))
+    GC.@preserve m check(ccall(sym(:pinn_hmc_set_metric_dense), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64),
+        e.h, inv_metric === nothing ? Ptr{Float64}(C_NULL) : pointer(m), e.P), "pinn_hmc_set_metric_dense")
+    return nothing
+end
+
+function hmc_get_metric_dense(e::HIPEngine)
+    m = zeros(Float64, e.P, e.P); l = zeros(Float64, e.P, e.P)
+    GC.@preserve m l check(ccall(sym(:pinn_hmc_get_metric_dense), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64), e.h, m, l, e.P), "pinn_hmc_get_metric_dense")
+    return permutedims(m), permutedims(l)
+end
+
 function hmc_draws(e::HIPEngine, ndraws::Integer, n_leapfrog::Integer, ϵ::Real; seed::Integer = 0, momenta = nothing, uniforms = nothing)
     mom = momenta === nothing ? Float64[] : Vector{Float64}(vec(momenta)); uni = uniforms === nothing ? Float64[] : Vector{Float64}(uniforms)
     samples = zeros(Float64, e.P, ndraws); acc = zeros(Float64, ndraws); lp = zeros(Float64, ndraws)

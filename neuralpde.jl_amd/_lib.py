@@ -39,6 +39,7 @@ SYMBOLS = [
     "pinn_residual_f64", "pinn_phi_f64", "pinn_derivative_f64", "pinn_term_grads_f64", "pinn_loglik_grad_f64",
     "pinn_loss_grad_sharded_device_f64", "pinn_loss_grad_sharded_f64",
     "pinn_hmc_init", "pinn_hmc_set_metric", "pinn_hmc_draws", "pinn_hmc_get", "pinn_hmc_find_stepsize", "pinn_hmc_warmup",
+    "pinn_hmc_set_metric_dense", "pinn_hmc_get_metric_dense",
     "pinn_nuts_draws",
     "pinn_hmc_chains_init", "pinn_hmc_chains_draws", "pinn_hmc_chains_get",
     "pinn_lbfgs_init", "pinn_lbfgs_steps", "pinn_lbfgs_get",
@@ -121,6 +122,8 @@ class Library:
         try:                                     # (resident HMC: variant libraries built before it still load)
             L.pinn_hmc_init.argtypes = [vp, dp, C.c_int64, dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), dp, dp]
             L.pinn_hmc_set_metric.argtypes = [vp, dp, C.c_int64]
+            L.pinn_hmc_set_metric_dense.argtypes = [vp, dp, C.c_int64]
+            L.pinn_hmc_get_metric_dense.argtypes = [vp, dp, dp, C.c_int64]
             L.pinn_hmc_draws.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint64, dp, dp, dp, C.c_int64, dp, dp]
             L.pinn_hmc_get.argtypes = [vp, dp, C.c_int64, dp, dp]
         except AttributeError:
@@ -723,6 +726,21 @@ class Engine:
         self.L.check(self.L.lib.pinn_hmc_set_metric(self.h, m.ctypes.data_as(C.POINTER(C.c_double)) if m is not None else None,
                                                     m.size if m is not None else self.P), "pinn_hmc_set_metric")
 
+    def hmc_set_metric_dense(self, inv_metric=None):
+        """`pinn_hmc_set_metric_dense`: the dense inverse mass matrix ([P x P] symmetric positive definite; None: the identity), factorised on
+        the device; `hmc_draws`, `hmc_find_stepsize` and `hmc_warmup` then run under it.  `hmc_set_metric` returns to a diagonal metric."""
+        m = None if inv_metric is None else np.ascontiguousarray(_f64(inv_metric))
+        if m is not None and (m.ndim != 2 or m.shape[0] != m.shape[1]):
+            raise ValueError("inv_metric: a square matrix")
+        self.L.check(self.L.lib.pinn_hmc_set_metric_dense(self.h, m.ctypes.data_as(C.POINTER(C.c_double)) if m is not None else None,
+                                                          m.shape[0] if m is not None else self.P), "pinn_hmc_set_metric_dense")
+
+    def hmc_get_metric_dense(self):
+        """`pinn_hmc_get_metric_dense`: (M^-1, L) of the chain's dense metric, M^-1 = L L^T, L lower triangular"""
+        m, l, dp = np.zeros((self.P, self.P)), np.zeros((self.P, self.P)), C.POINTER(C.c_double)
+        self.L.check(self.L.lib.pinn_hmc_get_metric_dense(self.h, m.ctypes.data_as(dp), l.ctypes.data_as(dp), self.P), "pinn_hmc_get_metric_dense")
+        return m, l
+
     def hmc_draws(self, ndraws: int, n_leapfrog: int, eps: float, seed: int = 0, momenta=None, uniforms=None, want_samples: bool = True):
         """`pinn_hmc_draws`: `ndraws` transitions on the device, one download.  Returns (samples [ndraws x P] or None, accept_prob, logp).
         momenta ([ndraws x P]) / uniforms ([ndraws]) replace the device generator's draws when given."""
@@ -818,10 +836,12 @@ class Engine:
         smp = np.zeros((nd, self.P), dtype=np.float64)
         acc, lp, steps, minv = np.zeros(nd, dtype=np.float64), np.zeros(nd, dtype=np.float64), np.zeros(nd, dtype=np.float64), np.zeros(self.P, dtype=np.float64)
         eps = C.c_double()
-        self.L.check(self.L.lib.pinn_hmc_warmup(self.h, int(n_adapts), int(n_leapfrog), float(eps0), float(target), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                z.ctypes.data_as(dp) if z is not None else None, uni.ctypes.data_as(dp) if uni is not None else None,
-                                                smp.ctypes.data_as(dp), self.P, acc.ctypes.data_as(dp), lp.ctypes.data_as(dp), steps.ctypes.data_as(dp),
-                                                C.byref(eps), minv.ctypes.data_as(dp)), "pinn_hmc_warmup")
+        rc = self.L.lib.pinn_hmc_warmup(self.h, int(n_adapts), int(n_leapfrog), float(eps0), float(target), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        z.ctypes.data_as(dp) if z is not None else None, uni.ctypes.data_as(dp) if uni is not None else None,
+                                        smp.ctypes.data_as(dp), self.P, acc.ctypes.data_as(dp), lp.ctypes.data_as(dp), steps.ctypes.data_as(dp),
+                                        C.byref(eps), minv.ctypes.data_as(dp))
+        self.metric_kept = rc == 2               # PINN_HMC_METRIC_KEPT (dense metric only): the run is complete, the window's covariance was not adopted
+        self.L.check(0 if self.metric_kept else rc, "pinn_hmc_warmup")
         return smp, acc, lp, steps, eps.value, minv
 
     def nuts_draws(self, ndraws: int, max_depth: int, eps: float, seed: int = 0, normals=None, uniforms=None, delta_max: float = 1000.0):

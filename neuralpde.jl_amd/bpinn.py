@@ -63,35 +63,53 @@ class BPINNsolution:
         self.samples, self.ensemblesol, self.ensemblestd, self.timepoints, self.stats = samples, ensemblesol, ensemblestd, timepoints, stats
 
 
-def _hmc(logp_grad, theta0, draw_samples, n_leapfrog, eps0, target, rng, n_adapts=None):
+def _dense_window_metric(win):
+    """the dense twin of the windowed variance rule: (k/(k+5)) cov + 1e-3 (5/(k+5)) I over the k window rows, and its lower Cholesky factor;
+    None when the matrix is not positive definite (the metric in force stays)"""
+    W = np.asarray(win)
+    k = W.shape[0]
+    Minv = (k / (k + 5.0)) * np.cov(W.T, bias=True) + 1e-3 * (5.0 / (k + 5.0)) * np.eye(W.shape[1])
+    try:
+        return Minv, np.linalg.cholesky(Minv)
+    except np.linalg.LinAlgError:
+        return None
+
+
+def _hmc(logp_grad, theta0, draw_samples, n_leapfrog, eps0, target, rng, n_adapts=None, metric="diag"):
     """HMC with `n_leapfrog` leapfrog steps per draw ([3P] AdvancedHMC.HMC(eps, n_leapfrog)), Stan-style adaptation during the first
     n_adapts = min(draw_samples / 10, 1000) draws (AdvancedHMC's default): dual averaging of the step size towards `target` acceptance
-    and a diagonal metric from the windowed sample variance (StanHMCAdaptor + DiagEuclideanMetric)."""
+    and a diagonal metric from the windowed sample variance (StanHMCAdaptor + DiagEuclideanMetric).  metric="dense": a full inverse metric
+    M^-1 = L L^T from the windowed covariance (DenseEuclideanMetric): r = L^-T z, theta += eps M^-1 r, kinetic energy 1/2 r.(M^-1 r)."""
     n = theta0.size
     n_adapts = min(draw_samples // 10, 1000) if n_adapts is None else n_adapts
     th = theta0.astype(np.float64).copy()
     lp, g = logp_grad(th)
     minv = np.ones(n)                                # inverse mass (diagonal metric)
+    dense = metric == "dense"
+    if dense:
+        minv, chol = np.eye(n), np.eye(n)
+    momentum = (lambda z: np.linalg.solve(chol.T, z)) if dense else (lambda z: z / np.sqrt(minv))
+    kinetic = (lambda r: 0.5 * (r @ (minv @ r))) if dense else (lambda r: 0.5 * np.sum(minv * r * r))
 
     def leap(th, r, g, eps, steps):
         r = r + 0.5 * eps * g
         for s in range(steps):
-            th = th + eps * minv * r
+            th = th + eps * (minv @ r if dense else minv * r)
             lp, g = logp_grad(th)
             r = r + (eps if s < steps - 1 else 0.5 * eps) * g
         return th, r, lp, g
 
     # find_good_stepsize: double / halve until the one-step acceptance crosses 0.8 (AdvancedHMC.find_good_stepsize)
     eps = eps0
-    r0 = rng.standard_normal(n) / np.sqrt(minv)
-    h0 = -lp + 0.5 * np.sum(minv * r0 * r0)
+    r0 = momentum(rng.standard_normal(n))
+    h0 = -lp + kinetic(r0)
     t1, r1, lp1, _ = leap(th, r0, g, eps, 1)
-    d = h0 - (-lp1 + 0.5 * np.sum(minv * r1 * r1))
+    d = h0 - (-lp1 + kinetic(r1))
     direction = 1.0 if (np.isfinite(d) and d > np.log(0.8)) else -1.0
     for _ in range(40):
         eps *= 2.0 ** direction
         t1, r1, lp1, _ = leap(th, r0, g, eps, 1)
-        d = h0 - (-lp1 + 0.5 * np.sum(minv * r1 * r1))
+        d = h0 - (-lp1 + kinetic(r1))
         if not np.isfinite(d):
             d = -np.inf
         if (direction > 0) == (d <= np.log(0.8)):
@@ -102,10 +120,10 @@ def _hmc(logp_grad, theta0, draw_samples, n_leapfrog, eps0, target, rng, n_adapt
     samples, accs = [], []
     m_count = 0
     for it in range(draw_samples):
-        r = rng.standard_normal(n) / np.sqrt(minv)
-        h_old = -lp + 0.5 * np.sum(minv * r * r)
+        r = momentum(rng.standard_normal(n))
+        h_old = -lp + kinetic(r)
         tn, rn, lpn, gn = leap(th, r, g, eps, n_leapfrog)
-        h_new = -lpn + 0.5 * np.sum(minv * rn * rn)
+        h_new = -lpn + kinetic(rn)
         a = float(np.exp(min(0.0, h_old - h_new))) if np.isfinite(h_new) else 0.0
         if rng.random() < a:
             th, lp, g = tn, lpn, gn
@@ -121,26 +139,34 @@ def _hmc(logp_grad, theta0, draw_samples, n_leapfrog, eps0, target, rng, n_adapt
             if w0 <= it < w1:
                 win.append(th.copy())
             if it == w1 - 1 and len(win) >= 8 and n_adapts >= 100:       # (a metric from fewer draws is noise; short runs keep the unit metric)
-                var = np.var(np.asarray(win), axis=0)
-                k = len(win)
-                minv = (k / (k + 5.0)) * var + 1e-3 * (5.0 / (k + 5.0))
+                if dense:
+                    new = _dense_window_metric(win)
+                    minv, chol = new if new is not None else (minv, chol)
+                else:
+                    var = np.var(np.asarray(win), axis=0)
+                    k = len(win)
+                    minv = (k / (k + 5.0)) * var + 1e-3 * (5.0 / (k + 5.0))
                 mu, hbar, log_eps_bar, m_count = np.log(10 * eps), 0.0, 0.0, 0          # restart the step-size search on the new metric
             if it == n_adapts - 1:
                 eps = float(np.exp(log_eps_bar)) if m_count > 0 else eps
     return np.asarray(samples), {"acceptance": np.asarray(accs), "step_size": eps, "inv_metric": minv, "n_adapts": n_adapts}
 
 
-def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, eps0, target, rng, seed, n_adapts=None, chunk=256, adaptation="host"):
+def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, eps0, target, rng, seed, n_adapts=None, chunk=256, adaptation="host",
+                metric="diag"):
     """`_hmc` with the transitions on the device (Engine.hmc_*): the same initial step-size search on the host evaluation path (at most 42
     evaluations), the same dual averaging and windowed metric in Python around `hmc_draws(1, ...)` during adaptation (a new metric goes down
     through `hmc_set_metric`), then the remaining draws in chunks of `chunk`.  Momenta and uniforms come from the device generator (`seed`).
     adaptation="device": the adaptation draws are ONE `hmc_warmup` call — the same recurrence and window on the device — after the same host
-    search, so both settings start from the same step size."""
+    search, so both settings start from the same step size.  metric="dense": the chain starts under the dense identity
+    (`hmc_set_metric_dense`); the host adaptation sends the windowed covariance down through it, the device adaptation forms and factorises it
+    in the `hmc_warmup` call; stats["inv_metric"] is then P x P."""
     n = theta0.size
     n_adapts = min(draw_samples // 10, 1000) if n_adapts is None else n_adapts
     th = theta0.astype(np.float64).copy()
     lp, g = logp_grad(th)
     minv = np.ones(n)
+    dense = metric == "dense"
 
     def one_step(r, eps):
         r = r + 0.5 * eps * g
@@ -162,6 +188,9 @@ def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, ep
         if (direction > 0) == (d <= np.log(0.8)):
             break
     init_chain(th)
+    if dense:                                        # (the search above ran under the unit metric, which the dense identity is)
+        eng.hmc_set_metric_dense(None)
+        minv = np.eye(n)
     mu, hbar, log_eps_bar, t0, gamma, kappa = np.log(10 * eps), 0.0, 0.0, 10.0, 0.05, 0.75
     w0, w1 = int(0.15 * n_adapts), int(0.9 * n_adapts)
     win, samples, accs = [], [], []
@@ -171,6 +200,8 @@ def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, ep
         if n_adapts > draw_samples:
             raise ValueError("adaptation=\"device\": the warm-up is one call of n_adapts draws; draw_samples must be at least n_adapts")
         smp, acc, _, _, eps, minv = eng.hmc_warmup(n_adapts, n_leapfrog, eps, target, seed)
+        if dense:
+            minv = eng.hmc_get_metric_dense()[0]
         samples.extend(smp)
         accs.extend(acc)
         host_adapts = 0
@@ -188,10 +219,16 @@ def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, ep
         if w0 <= it < w1:
             win.append(th)
         if it == w1 - 1 and len(win) >= 8 and n_adapts >= 100:
-            var = np.var(np.asarray(win), axis=0)
-            k = len(win)
-            minv = (k / (k + 5.0)) * var + 1e-3 * (5.0 / (k + 5.0))
-            eng.hmc_set_metric(minv)
+            if dense:
+                new = _dense_window_metric(win)
+                if new is not None:
+                    minv = new[0]
+                    eng.hmc_set_metric_dense(minv)
+            else:
+                var = np.var(np.asarray(win), axis=0)
+                k = len(win)
+                minv = (k / (k + 5.0)) * var + 1e-3 * (5.0 / (k + 5.0))
+                eng.hmc_set_metric(minv)
             mu, hbar, log_eps_bar, m_count = np.log(10 * eps), 0.0, 0.0, 0
         if it == n_adapts - 1:
             eps = float(np.exp(log_eps_bar)) if m_count > 0 else eps
@@ -441,7 +478,8 @@ class Normal:
 
 def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, bcstd=(0.01,), l2std=(0.05,), phystd=(0.05,), priorsNNw=(0.0, 2.0),
                            param=(), n_leapfrog=30, step_size=0.1, targetacceptancerate=0.8, saveats=(0.1,), numensemble=None, rng=None,
-                           sampler="host", seed=0, ensemble="host", ensemble_derivatives=(), adaptation="host", kernel="hmc", max_depth=10, nchains=1):
+                           sampler="host", seed=0, ensemble="host", ensemble_derivatives=(), adaptation="host", kernel="hmc", max_depth=10, nchains=1,
+                           metric="diag"):
     """`ahmc_bayesian_pinn_pde(pde_system, discretization; draw_samples, bcstd, phystd, priorsNNw, Kernel = HMC(0.1, 30), saveats,
     numensemble)` — the forward-problem form of ext/bpinn/PDE_BPINN.jl:371-640: the posterior over the network parameters is
     prior N(priorsNNw[1], priorsNNw[2]^2 I) x physics likelihood (`pinn_loglik_grad`: every leapfrog step is ONE fused device evaluation,
@@ -473,7 +511,11 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
     makes `draw_samples - n_adapts` draws.  `sol.chain_samples` (set by this sampler only) is [nchains x draws x P]; `sol.samples` and the ensemble statistics pool the
     chains (draw-major, so the last rows hold every chain's last draws).  `numensemble` counts pooled rows and is not scaled by `nchains`: the default
     `draw_samples // 3` takes about `numensemble / nchains` final draws of every chain.  The chain kernel runs the fp32 kernels: the discretization needs
-    `precision = "f32"` (the float64 mode is refused by name).  `kernel = "nuts"` is refused; `nchains > 1` needs `sampler = "chains"`."""
+    `precision = "f32"` (the float64 mode is refused by name).  `kernel = "nuts"` is refused; `nchains > 1` needs `sampler = "chains"`.
+    `metric = "dense"` (the reference's `Metric = DenseEuclideanMetric`) adapts a full inverse mass matrix from the windowed sample covariance
+    instead of its diagonal: in numpy with `sampler = "host"`, resident on the device (`pinn_hmc_set_metric_dense`) with
+    `sampler = "device"` under either `adaptation`; `stats["inv_metric"]` is then P x P and `stats["metric"]` says which ran.  `kernel = "nuts"`
+    and `sampler = "chains"` are refused with it.  The default `"diag"` changes nothing."""
     reqs = []
     for r in ensemble_derivatives:
         name, order, axes = r
@@ -499,6 +541,10 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
         raise ValueError(f"kernel must be \"hmc\" or \"nuts\", not {kernel!r}")
     if kernel == "nuts" and adaptation == "device":
         raise ValueError("kernel=\"nuts\" with adaptation=\"device\": the resident warm-up runs fixed-length HMC transitions only; NUTS adapts on the host")
+    if metric not in ("diag", "dense"):
+        raise ValueError(f"metric must be \"diag\" or \"dense\", not {metric!r}")
+    if metric == "dense" and (kernel == "nuts" or sampler == "chains"):
+        raise ValueError("metric=\"dense\" runs fixed-length HMC on one chain: kernel=\"nuts\" and sampler=\"chains\" keep the diagonal metric")
     if kernel == "nuts" and not 1 <= int(max_depth) <= 10:
         raise ValueError("max_depth must be in 1..10")
     if rng is None:
@@ -564,15 +610,16 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
                                           float(step_size), float(targetacceptancerate), rng, int(seed))
         else:
             samples, stats = _hmc_device(eng, logp_grad, theta0, lambda th: eng.hmc_init(th, stds, (mu0, sd0), kinds), int(draw_samples), int(n_leapfrog),
-                                         float(step_size), float(targetacceptancerate), rng, int(seed), adaptation=adaptation)
+                                         float(step_size), float(targetacceptancerate), rng, int(seed), adaptation=adaptation, metric=metric)
     elif kernel == "nuts":
         samples, stats = _nuts(logp_grad, theta0, int(draw_samples), int(max_depth), float(step_size), float(targetacceptancerate), rng)
     else:
-        samples, stats = _hmc(logp_grad, theta0, int(draw_samples), int(n_leapfrog), float(step_size), float(targetacceptancerate), rng)
+        samples, stats = _hmc(logp_grad, theta0, int(draw_samples), int(n_leapfrog), float(step_size), float(targetacceptancerate), rng, metric=metric)
     stats["sampler"] = sampler
     stats["ensemble"] = ensemble
     stats["adaptation"] = adaptation
     stats["kernel"] = kernel
+    stats["metric"] = metric
     numensemble = int(draw_samples // 3) if numensemble is None else int(numensemble)
     # inference: the last `numensemble` draws on the saveats grid (one spacing per independent variable), per dependent variable
     doms = {str(d.variable): (float(d.domain.lo), float(d.domain.hi)) for d in pde_system.domain}

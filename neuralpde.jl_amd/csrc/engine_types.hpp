@@ -443,6 +443,8 @@ public:
 template <class V, class T> As<V, T> as(T* x, size_t n) { return As<V, T>(x, n); }
 // hmc.cpp, lbfgs.cpp, bfgs.cpp, ensemble.cpp: release the handle's resident solver state / ensemble buffers (nothing to do when there is none)
 void hmc_free(pinn_engine& E);
+// hmc.cpp: nonzero (and the error set) when the handle's chain of pinn_hmc_init holds a dense metric (pinn_hmc_set_metric_dense); `why`: the caller's reason
+int hmc_refuse_dense(const pinn_engine& E, const char* who, const char* why);
 void chains_free(pinn_engine& E);
 void lbfgs_free(pinn_engine& E);
 void bfgs_free(pinn_engine& E);

@@ -5,9 +5,12 @@
 // before the single download that ends pinn_hmc_draws.
 // pinn_nuts_draws (section 4.14): No-U-Turn transitions of the same chain — slots of one evaluation + one state-machine launch
 // (nuts_kernels.hpp), queued in chunks of "nuts_chunk"; the control block is all the host reads between chunks.
+// pinn_hmc_set_metric_dense / _get_metric_dense (section 4.16): the same chain under a full inverse metric M^-1 = L L^T — a host-side branch per draw
+// onto the launches of hmc_dense_kernels.hpp (DenseRun below); the diagonal launch sequences are what they were.
 // The state has buffers of its own: evaluations and optimiser runs between two calls do not touch the chain, and the chain does not touch them.
 #include "resident.hpp"
 #include "nuts_kernels.hpp"
+#include "hmc_dense_kernels.hpp"
 
 using namespace pe;
 
@@ -26,6 +29,12 @@ struct pe::HmcState {
     nuts::Ctl* d_nctl = nullptr;
     int* d_istat = nullptr;              // [3 ndraws]: tree_depth | n_leapfrog | divergent
     size_t istat_cap = 0;
+    // the dense metric (allocated by the first pinn_hmc_set_metric_dense; section 4.16)
+    bool dense = false;                  // which metric the chain holds
+    hmc::Dense dn{};
+    double* d_dmat = nullptr;            // [4 ld ld]: M^-1 | L | staged M^-1 | staged L
+    double* d_dvec = nullptr;            // [5 P]: second momentum | second proposal (the ping-pong partners of a.r, a.th_prop) | v | mu | diag
+    int* d_dflag = nullptr;
 };
 
 namespace {
@@ -37,6 +46,7 @@ void hmc_release(HmcState* H) {
     plat_free(H->d_samples); plat_free(H->d_stat); plat_free(H->d_mom); plat_free(H->d_uni);
     plat_free(H->d_r0); plat_free(H->d_steps);
     plat_free(H->d_tree); plat_free(H->d_nctl); plat_free(H->d_istat);
+    plat_free(H->d_dmat); plat_free(H->d_dvec); plat_free(H->d_dflag);
     delete H;
 }
 
@@ -59,7 +69,56 @@ void hmc_leap_dev(pinn_engine& E, HmcState& H, bool from_eval, double kfac, int 
     else hmc::launch_leap_dev<float>(H.a, from_eval ? H.ev.out<float>() : nullptr, kfac, drift, E.stream);
 }
 
+
+// One call's launches under the dense metric.  Momentum and proposal ping-pong between (a.r, a.th_prop) and their partners in d_dvec; `args()` is the
+// argument block whose r / th_prop are the current ones, for the energy and accept launches.
+struct DenseRun {
+    pinn_engine& E; HmcState& H;
+    int rc = 0, tc = 0;
+    double* rb(int k) const { return k ? H.d_dvec : H.a.r; }
+    double* tb(int k) const { return k ? H.d_dvec + H.a.P : H.a.th_prop; }
+    double* r() const { return rb(rc); }
+    hmc::Args args() const { hmc::Args b = H.a; b.r = rb(rc); b.th_prop = tb(tc); return b; }
+    void leap(int mode, double kick, double eps, int from_sc, int drift) {
+        const hmc::LeapIO io{tb(tc), tb(1 - tc), rb(rc), rb(1 - rc)};
+        if (H.ev.f64) hmc::launch_dense_leap<double>(H.a, H.dn, mode == hmc::DMODE_EVAL ? H.ev.out<double>() : nullptr, io, mode, kick, eps, from_sc, drift, E.stream);
+        else hmc::launch_dense_leap<float>(H.a, H.dn, mode == hmc::DMODE_EVAL ? H.ev.out<float>() : nullptr, io, mode, kick, eps, from_sc, drift, E.stream);
+        if (mode != hmc::DMODE_PRODUCT) rc = 1 - rc;
+        if (drift) tc = 1 - tc;
+    }
+    // r = L^-T z (z: a device row of standard normals, or the generator), or the caller's momentum as given; then v = M^-1 r and H_old
+    void momentum(const double* z, const double* given, uint64_t seed, unsigned ctr) {
+        if (given) plat_d2d(r(), given, sizeof(double) * (size_t)H.a.P, E.stream);
+        else hmc::launch_dense_momentum(H.a, H.dn, z, seed, ctr, r(), E.stream);
+        leap(hmc::DMODE_PRODUCT, 0.0, 0.0, 0, 0);
+        hmc::launch_energy_dense(args(), H.dn, 0, nullptr, E.stream);
+    }
+    // the trajectory after the momentum: eps from the host, or (from_sc) from the scalar block with kick factors 1/2, 1
+    int trajectory(int n_leapfrog, double eps, int from_sc) {
+        const double half = from_sc ? 0.5 : 0.5 * eps, full = from_sc ? 1.0 : eps;
+        leap(hmc::DMODE_FIRST, half, eps, from_sc, 1);
+        for (int s = 0; s < n_leapfrog; ++s) {
+            if (H.ev.eval(E)) return 1;
+            const bool last = s == n_leapfrog - 1;
+            leap(hmc::DMODE_EVAL, last ? half : full, eps, from_sc, last ? 0 : 1);
+        }
+        hmc::launch_energy_dense(args(), H.dn, 1, H.ev.sums((size_t)H.a.P), E.stream);
+        return 0;
+    }
+};
+
+// stage -> factorise -> commit, all on the stream; the caller reads the flag when it wants to know
+void dense_refactor(pinn_engine& E, HmcState& H) {
+    hmc::launch_chol(H.dn, H.a.P, E.stream);
+    hmc::launch_commit(H.a, H.dn, E.stream);
+}
+
 }  // namespace
+
+int pe::hmc_refuse_dense(const pinn_engine& E, const char* who, const char* why) {
+    if (E.hmc && E.hmc->dense) return fail(std::string(who) + ": the handle's chain holds a dense metric (pinn_hmc_set_metric_dense); " + why + " (pinn_hmc_set_metric returns to a diagonal one)");
+    return 0;
+}
 
 void pe::hmc_free(pinn_engine& E) {
     hmc_release(E.hmc);
@@ -161,6 +220,71 @@ int pinn_hmc_set_metric(pinn_handle h, const double* inv_metric, int64_t p) {
     }
     DeviceScope scope(E.device);
     if (plat_h2d((double*)H.a.minv, m.data(), sizeof(double) * (size_t)p, E.stream) || plat_sync(E.stream)) return fail(std::string(who) + ": H2D copy failed");
+    H.dense = false;
+    return 0;
+}
+
+int pinn_hmc_set_metric_dense(pinn_handle h, const double* inv_metric, int64_t p) {
+    const char* who = "pinn_hmc_set_metric_dense";
+    if (!h) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who)) return 1;
+    if (p > hmc::DENSE_MAX_P) return fail(std::string(who) + ": " + std::to_string(p) + " parameters; the dense metric is limited to P <= " + std::to_string(hmc::DENSE_MAX_P));
+    HmcState& H = *E.hmc;
+    const size_t P = (size_t)p, ld = (size_t)hmc::dense_ld((int)p);
+    std::vector<double> img(ld * ld, 0.0);               // the padded image: pads zero
+    double amax = 0.0;
+    for (size_t i = 0; i < P; ++i)
+        for (size_t j = 0; j < P; ++j) {
+            const double x = inv_metric ? inv_metric[i * P + j] : (i == j ? 1.0 : 0.0);
+            if (!std::isfinite(x)) return fail(std::string(who) + ": the inverse metric has a non-finite entry at (" + std::to_string(i) + ", " + std::to_string(j) + ")");
+            amax = std::max(amax, std::fabs(x));
+            img[i * ld + j] = x;
+        }
+    for (size_t i = 0; i < P; ++i)
+        for (size_t j = 0; j < i; ++j)
+            if (std::fabs(img[i * ld + j] - img[j * ld + i]) > 1e-12 * amax)
+                return fail(std::string(who) + ": the inverse metric is not symmetric at (" + std::to_string(i) + ", " + std::to_string(j) + ")");
+    DeviceScope scope(E.device);
+    if (!H.d_dmat) {
+        double* mat = (double*)plat_malloc(sizeof(double) * 4 * ld * ld);
+        double* vec = (double*)plat_malloc(sizeof(double) * 5 * P);
+        int* flg = (int*)plat_malloc(sizeof(int) * hmc::DF_COUNT);
+        if (!mat || !vec || !flg) { plat_free(mat); plat_free(vec); plat_free(flg); return fail(std::string(who) + ": device allocation failed"); }
+        H.d_dmat = mat; H.d_dvec = vec; H.d_dflag = flg;
+        H.dn.ld = (int)ld;
+        H.dn.M = mat; H.dn.L = mat + ld * ld; H.dn.Mn = mat + 2 * ld * ld; H.dn.Ln = mat + 3 * ld * ld;
+        H.dn.v = vec + 2 * P; H.dn.mu = vec + 3 * P; H.dn.diag = vec + 4 * P;
+        H.dn.flag = flg;
+    }
+    int flag[hmc::DF_COUNT] = {0, -1, 0, -1};
+    if (plat_h2d(H.dn.Mn, img.data(), sizeof(double) * ld * ld, E.stream) || plat_h2d(H.dn.flag, flag, sizeof flag, E.stream))
+        return fail(std::string(who) + ": H2D copy failed");
+    dense_refactor(E, H);
+    if (plat_d2h(flag, H.dn.flag, sizeof flag, E.stream) || plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    if (flag[hmc::DF_STATUS] != 0)
+        return fail(std::string(who) + ": the inverse metric is not positive definite: pivot " + std::to_string(flag[hmc::DF_INDEX]) + " of its Cholesky factorisation is not positive and finite");
+    H.dense = true;
+    return 0;
+}
+
+int pinn_hmc_get_metric_dense(pinn_handle h, double* inv_metric, double* chol, int64_t p) {
+    const char* who = "pinn_hmc_get_metric_dense";
+    if (!h) return fail(std::string(who) + ": null argument");
+    pinn_engine& E = *h;
+    if (hmc_ready(E, who) || check_theta(E, who, p)) return 1;
+    HmcState& H = *E.hmc;
+    if (!H.dense) return fail(std::string(who) + ": the handle's chain holds a diagonal metric (pinn_hmc_set_metric_dense sets a dense one)");
+    DeviceScope scope(E.device);
+    const size_t P = (size_t)p, ld = (size_t)H.dn.ld;
+    std::vector<double> img(ld * ld);
+    const double* src[2] = {H.dn.M, H.dn.L};
+    double* dst[2] = {inv_metric, chol};
+    for (int q = 0; q < 2; ++q) {
+        if (!dst[q]) continue;
+        if (plat_d2h(img.data(), src[q], sizeof(double) * ld * ld, E.stream) || plat_sync(E.stream)) return fail(std::string(who) + ": D2H copy failed");
+        for (size_t i = 0; i < P; ++i) std::copy(img.begin() + i * ld, img.begin() + i * ld + P, dst[q] + i * P);
+    }
     return 0;
 }
 
@@ -184,8 +308,16 @@ int pinn_hmc_draws(pinn_handle h, int ndraws, int n_leapfrog, double eps, uint64
         return fail(std::string(who) + ": H2D copy failed");
     double* d_acc = H.d_stat;
     double* d_lp = H.d_stat + nd;
+    DenseRun R{E, H};
     for (int d = 0; d < ndraws; ++d) {
         const unsigned ctr = (unsigned)H.draws;
+        if (H.dense) {                                   // the same draw under the dense metric (hmc_dense_kernels.hpp)
+            R.momentum(nullptr, momenta ? H.d_mom + (size_t)d * P : nullptr, seed, ctr);
+            if (R.trajectory(n_leapfrog, eps, 0)) return 1;
+            hmc::launch_accept(R.args(), d, uniforms ? H.d_uni : nullptr, seed, ctr, samples ? H.d_samples : nullptr, d_acc, d_lp, E.stream);
+            ++H.draws;
+            continue;
+        }
         hmc::launch_momentum(H.a, momenta ? H.d_mom + (size_t)d * P : nullptr, seed, ctr, E.stream);
         hmc::launch_energy(H.a, 0, nullptr, E.stream);
         hmc_leap(E, H, false, 0.5 * eps, eps, 1);
@@ -210,7 +342,7 @@ int pinn_nuts_draws(pinn_handle h, int ndraws, int max_depth, double eps, double
     const char* who = "pinn_nuts_draws";
     if (!h || !accept_stat || !logp || !tree_depth || !n_leapfrog || !divergent) return fail(std::string(who) + ": null argument");
     pinn_engine& E = *h;
-    if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who)) return 1;
+    if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who) || hmc_refuse_dense(E, who, "the U-turn test runs under a diagonal metric")) return 1;
     if (ndraws < 1) return fail(std::string(who) + ": ndraws must be at least 1");
     if (max_depth < 1 || max_depth > nuts::MAX_DEPTH) return fail(std::string(who) + ": max_depth must be in 1.." + std::to_string(nuts::MAX_DEPTH));
     if (!(eps > 0.0) || !std::isfinite(eps)) return fail(std::string(who) + ": the step size eps must be positive and finite");
@@ -285,21 +417,29 @@ int pinn_hmc_find_stepsize(pinn_handle h, double eps0, uint64_t seed, const doub
         return fail(std::string(who) + ": device allocation failed");
     if (normals && plat_h2d(H.d_mom, normals, sizeof(double) * P, E.stream)) return fail(std::string(who) + ": H2D copy failed");
     // r0 and h0 = -logp(current) + 1/2 sum minv r0^2; the current state, its gradient and logp are only read from here on
-    hmc::launch_momentum_z(H.a, normals ? H.d_mom : nullptr, seed, 0xFFFFFFFFu, E.stream);
-    hmc::launch_energy(H.a, 0, nullptr, E.stream);
-    plat_d2d(H.d_r0, H.a.r, sizeof(double) * P, E.stream);
+    DenseRun R{E, H};
+    if (H.dense) R.momentum(normals ? H.d_mom : nullptr, nullptr, seed, 0xFFFFFFFFu);
+    else {
+        hmc::launch_momentum_z(H.a, normals ? H.d_mom : nullptr, seed, 0xFFFFFFFFu, E.stream);
+        hmc::launch_energy(H.a, 0, nullptr, E.stream);
+    }
+    plat_d2d(H.d_r0, H.dense ? R.r() : H.a.r, sizeof(double) * P, E.stream);
     const double log08 = std::log(0.8);
     double e = eps0, direction = 0.0;
     int trials = 0;
     for (int t = 0; t <= 40; ++t) {
         if (t > 0) {
             e *= direction > 0 ? 2.0 : 0.5;
-            plat_d2d(H.a.r, H.d_r0, sizeof(double) * P, E.stream);
+            plat_d2d(H.dense ? R.r() : H.a.r, H.d_r0, sizeof(double) * P, E.stream);
         }
-        hmc_leap(E, H, false, 0.5 * e, e, 1);
-        if (H.ev.eval(E)) return 1;
-        hmc_leap(E, H, true, 0.5 * e, e, 0);
-        hmc::launch_energy(H.a, 1, H.ev.sums(P), E.stream);
+        if (H.dense) {
+            if (R.trajectory(1, e, 0)) return 1;
+        } else {
+            hmc_leap(E, H, false, 0.5 * e, e, 1);
+            if (H.ev.eval(E)) return 1;
+            hmc_leap(E, H, true, 0.5 * e, e, 0);
+            hmc::launch_energy(H.a, 1, H.ev.sums(P), E.stream);
+        }
         double hh[2];                                    // H_old, H_new: neighbours in the scalar block
         if (plat_d2h(hh, H.a.sc + hmc::SC_H_OLD, sizeof hh, E.stream) || plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
         double d = hh[0] - hh[1];
@@ -343,8 +483,24 @@ int pinn_hmc_warmup(pinn_handle h, int n_adapts, int n_leapfrog, double eps0, do
     const bool metric_event = w1 - w0 >= 8 && n_adapts >= 100;
     double* d_acc = H.d_stat;
     double* d_lp = H.d_stat + nd;
+    DenseRun R{E, H};
+    int dflag[hmc::DF_COUNT] = {0, -1, 0, -1};
+    if (H.dense && plat_h2d(H.dn.flag, dflag, sizeof dflag, E.stream)) return fail(std::string(who) + ": H2D copy failed");
     for (int d = 0; d < n_adapts; ++d) {
         const unsigned ctr = (unsigned)H.draws;
+        if (H.dense) {                                   // the same draw and adaptation under the dense metric
+            R.momentum(normals ? H.d_mom + (size_t)d * P : nullptr, nullptr, seed, ctr);
+            if (R.trajectory(n_leapfrog, 0.0, 1)) return 1;
+            const bool restart = metric_event && d == w1 - 1;
+            const int flags = (restart ? hmc::ADAPT_RESTART : 0) | (d == n_adapts - 1 ? hmc::ADAPT_LAST : 0);
+            hmc::launch_accept_adapt(R.args(), d, uniforms ? H.d_uni : nullptr, seed, ctr, H.d_samples, d_acc, d_lp, target, flags, H.d_steps, E.stream);
+            if (restart) {                               // the window's regularised covariance, staged; a bad pivot keeps the old metric
+                hmc::launch_cov(H.a, H.dn, H.d_samples, w0, w1, E.stream);
+                dense_refactor(E, H);
+            }
+            ++H.draws;
+            continue;
+        }
         hmc::launch_momentum_z(H.a, normals ? H.d_mom + (size_t)d * P : nullptr, seed, ctr, E.stream);
         hmc::launch_energy(H.a, 0, nullptr, E.stream);
         hmc_leap_dev(E, H, false, 0.5, 1);
@@ -362,9 +518,15 @@ int pinn_hmc_warmup(pinn_handle h, int n_adapts, int n_leapfrog, double eps0, do
     }
     if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * P, E.stream)) || plat_d2h(accept_prob, d_acc, sizeof(double) * nd, E.stream) ||
         plat_d2h(logp, d_lp, sizeof(double) * nd, E.stream) || (step_sizes && plat_d2h(step_sizes, H.d_steps, sizeof(double) * nd, E.stream)) ||
-        plat_d2h(eps_final, H.d_steps + nd, sizeof(double), E.stream) || (inv_metric && plat_d2h(inv_metric, H.a.minv, sizeof(double) * P, E.stream)))
+        plat_d2h(eps_final, H.d_steps + nd, sizeof(double), E.stream) ||
+        (inv_metric && plat_d2h(inv_metric, H.dense ? H.dn.diag : H.a.minv, sizeof(double) * P, E.stream)) ||
+        (H.dense && plat_d2h(dflag, H.dn.flag, sizeof dflag, E.stream)))
         return fail(std::string(who) + ": D2H copy failed");
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
+    if (dflag[hmc::DF_REJECTED] != 0) {                  // the run is complete and its outputs are valid: a report, not a failure
+        fail(std::string(who) + ": the window covariance was not positive definite (pivot " + std::to_string(dflag[hmc::DF_REJECTED_INDEX]) + "); the metric before the window was kept");
+        return PINN_HMC_METRIC_KEPT;
+    }
     return 0;
 }
 

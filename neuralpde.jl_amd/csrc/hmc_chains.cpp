@@ -98,7 +98,7 @@ int pinn_hmc_chains_init(pinn_handle h, int nchains, const double* theta, int64_
     const char* who = "pinn_hmc_chains_init";
     if (!h || !theta || !stds) return fail(std::string(who) + ": null argument");
     pinn_engine& E = *h;
-    if (check_theta(E, who, p)) return 1;
+    if (check_theta(E, who, p) || hmc_refuse_dense(E, who, "the chain kernel keeps a diagonal metric in LDS")) return 1;
     if (nchains < 1 || nchains > pk::CHAIN_MAX_CHAINS) return fail(std::string(who) + ": nchains must be in 1.." + std::to_string(pk::CHAIN_MAX_CHAINS));
     if (n_leapfrog < 1) return fail(std::string(who) + ": n_leapfrog must be at least 1");
     if (!(eps > 0.0) || !std::isfinite(eps)) return fail(std::string(who) + ": the step size eps must be positive and finite");
@@ -181,7 +181,7 @@ int pinn_hmc_chains_draws(pinn_handle h, int ndraws, const double* momenta, cons
     if (!h) return fail(std::string(who) + ": null argument");
     pinn_engine& E = *h;
     DeviceScope scope(E.device);
-    if (chains_ready(E, who)) return 1;
+    if (chains_ready(E, who) || hmc_refuse_dense(E, who, "the chain kernel keeps a diagonal metric in LDS")) return 1;
     if (ndraws < 1) return fail(std::string(who) + ": ndraws must be at least 1");
     ChainsState& C = *E.chains;
     const size_t P = (size_t)C.P, n = (size_t)C.nchains * (size_t)ndraws;
