@@ -5,10 +5,11 @@
 // before the single download that ends pinn_hmc_draws.
 // pinn_nuts_draws (section 4.14): No-U-Turn transitions of the same chain — slots of one evaluation + one state-machine launch
 // (nuts_kernels.hpp), queued in chunks of "nuts_chunk"; the control block is all the host reads between chunks.
-// pinn_hmc_set_metric_dense / _get_metric_dense (section 4.16): the same chain under a full inverse metric M^-1 = L L^T — a host-side branch per draw
-// onto the launches of hmc_dense_kernels.hpp (DenseRun below); the diagonal launch sequences are what they were.
+// pinn_hmc_set_metric_dense / _get_metric_dense (section 4.16): the same chain under a full inverse metric M^-1 = L L^T (hmc_dense_kernels.hpp).
+// The trajectory is written once, in Run below: the entry points queue momentum, trajectory and metric event through it and do not ask which
+// metric the chain holds.
 // The state has buffers of its own: evaluations and optimiser runs between two calls do not touch the chain, and the chain does not touch them.
-#include "resident.hpp"
+#include "hmc_host.hpp"
 #include "nuts_kernels.hpp"
 #include "hmc_dense_kernels.hpp"
 
@@ -58,59 +59,88 @@ int hmc_ready(pinn_engine& E, const char* who) {
 int hmc_refuse_target(pinn_engine& E, const char* who) {
     return resident_refuse_target(E, who, "the resident sampler runs single-device chains only", "HMC needs a fixed target");
 }
-// the update launch after an evaluation at the proposal (from_eval), or the opening half kick
-void hmc_leap(pinn_engine& E, HmcState& H, bool from_eval, double kick, double eps, int drift) {
-    if (H.ev.f64) hmc::launch_leap<double>(H.a, from_eval ? H.ev.out<double>() : nullptr, kick, eps, drift, E.stream);
-    else hmc::launch_leap<float>(H.a, from_eval ? H.ev.out<float>() : nullptr, kick, eps, drift, E.stream);
-}
-// the same with the step size read from the scalar block on the device: kick = kfac * eps
-void hmc_leap_dev(pinn_engine& E, HmcState& H, bool from_eval, double kfac, int drift) {
-    if (H.ev.f64) hmc::launch_leap_dev<double>(H.a, from_eval ? H.ev.out<double>() : nullptr, kfac, drift, E.stream);
-    else hmc::launch_leap_dev<float>(H.a, from_eval ? H.ev.out<float>() : nullptr, kfac, drift, E.stream);
+
+// stage -> factorise -> commit, all on the stream; the caller reads the flag when it wants to know
+void dense_refactor(pinn_engine& E, HmcState& H) {
+    hmc::launch_chol(H.dn, H.a.P, E.stream);
+    hmc::launch_commit(H.a, H.dn, E.stream);
 }
 
-
-// One call's launches under the dense metric.  Momentum and proposal ping-pong between (a.r, a.th_prop) and their partners in d_dvec; `args()` is the
-// argument block whose r / th_prop are the current ones, for the energy and accept launches.
-struct DenseRun {
+// One call's launches, under the metric the chain holds.  Diagonal: momentum and proposal stay in a.r and a.th_prop.  Dense: they ping-pong between
+// (a.r, a.th_prop) and their partners in d_dvec, every leap flipping the side.  `args()` is the argument block whose r / th_prop are the current
+// ones, for the energy and accept launches.
+struct Run {
     pinn_engine& E; HmcState& H;
     int rc = 0, tc = 0;
     double* rb(int k) const { return k ? H.d_dvec : H.a.r; }
     double* tb(int k) const { return k ? H.d_dvec + H.a.P : H.a.th_prop; }
     double* r() const { return rb(rc); }
     hmc::Args args() const { hmc::Args b = H.a; b.r = rb(rc); b.th_prop = tb(tc); return b; }
-    void leap(int mode, double kick, double eps, int from_sc, int drift) {
+    // the update launch, T the evaluation's element type: DMODE_EVAL after an evaluation at the proposal, DMODE_FIRST the opening half kick
+    template <class T> void leap_as(int mode, double kick, double eps, int from_sc, int drift) {
+        const T* ev = mode == hmc::DMODE_EVAL ? H.ev.out<T>() : nullptr;
+        if (!H.dense) return hmc::launch_leap<T>(H.a, ev, kick, eps, from_sc, drift, E.stream);
         const hmc::LeapIO io{tb(tc), tb(1 - tc), rb(rc), rb(1 - rc)};
-        if (H.ev.f64) hmc::launch_dense_leap<double>(H.a, H.dn, mode == hmc::DMODE_EVAL ? H.ev.out<double>() : nullptr, io, mode, kick, eps, from_sc, drift, E.stream);
-        else hmc::launch_dense_leap<float>(H.a, H.dn, mode == hmc::DMODE_EVAL ? H.ev.out<float>() : nullptr, io, mode, kick, eps, from_sc, drift, E.stream);
+        hmc::launch_dense_leap<T>(H.a, H.dn, ev, io, mode, kick, eps, from_sc, drift, E.stream);
         if (mode != hmc::DMODE_PRODUCT) rc = 1 - rc;
         if (drift) tc = 1 - tc;
     }
-    // r = L^-T z (z: a device row of standard normals, or the generator), or the caller's momentum as given; then v = M^-1 r and H_old
+    void leap(int mode, double kick, double eps, int from_sc, int drift) {
+        if (H.ev.f64) leap_as<double>(mode, kick, eps, from_sc, drift);
+        else leap_as<float>(mode, kick, eps, from_sc, drift);
+    }
+    // mode 0: H_old.  mode 1: logp(proposal) from the last evaluation's sums, H_new
+    void energy(int mode) {
+        hmc::launch_energy(args(), mode, mode ? H.ev.sums((size_t)H.a.P) : nullptr, H.dense ? H.dn.v : nullptr, E.stream);
+    }
+    // the momentum from z (a device row of standard normals, or the generator) under the metric, or the caller's momentum as given; then H_old.
+    // Dense: r = L^-T z, and the product launch v = M^-1 r the energy reads
     void momentum(const double* z, const double* given, uint64_t seed, unsigned ctr) {
-        if (given) plat_d2d(r(), given, sizeof(double) * (size_t)H.a.P, E.stream);
-        else hmc::launch_dense_momentum(H.a, H.dn, z, seed, ctr, r(), E.stream);
-        leap(hmc::DMODE_PRODUCT, 0.0, 0.0, 0, 0);
-        hmc::launch_energy_dense(args(), H.dn, 0, nullptr, E.stream);
+        if (!H.dense) hmc::launch_momentum(H.a, z, given, seed, ctr, E.stream);
+        else {
+            if (given) plat_d2d(r(), given, sizeof(double) * (size_t)H.a.P, E.stream);
+            else hmc::launch_dense_momentum(H.a, H.dn, z, seed, ctr, r(), E.stream);
+            leap(hmc::DMODE_PRODUCT, 0.0, 0.0, 0, 0);
+        }
+        energy(0);
     }
     // the trajectory after the momentum: eps from the host, or (from_sc) from the scalar block with kick factors 1/2, 1
     int trajectory(int n_leapfrog, double eps, int from_sc) {
         const double half = from_sc ? 0.5 : 0.5 * eps, full = from_sc ? 1.0 : eps;
         leap(hmc::DMODE_FIRST, half, eps, from_sc, 1);
         for (int s = 0; s < n_leapfrog; ++s) {
-            if (H.ev.eval(E)) return 1;
+            if (H.ev.eval(E)) return 1;                 // (the current state only changes in the accept launch: a failed call leaves the chain at its last completed draw)
             const bool last = s == n_leapfrog - 1;
             leap(hmc::DMODE_EVAL, last ? half : full, eps, from_sc, last ? 0 : 1);
         }
-        hmc::launch_energy_dense(args(), H.dn, 1, H.ev.sums((size_t)H.a.P), E.stream);
+        energy(1);
         return 0;
+    }
+    // the warm-up's metric event from rows [w0, w1) of the sample buffer.  Dense: the window's regularised covariance, staged; a bad pivot keeps the old metric
+    void metric_event(int w0, int w1) {
+        if (!H.dense) return hmc::launch_window_metric(H.a, H.d_samples, w0, w1, E.stream);
+        hmc::launch_cov(H.a, H.dn, H.d_samples, w0, w1, E.stream);
+        dense_refactor(E, H);
     }
 };
 
-// stage -> factorise -> commit, all on the stream; the caller reads the flag when it wants to know
-void dense_refactor(pinn_engine& E, HmcState& H) {
-    hmc::launch_chol(H.dn, H.a.P, E.stream);
-    hmc::launch_commit(H.a, H.dn, E.stream);
+// the staging of a call of nd draws: the sample buffer when wanted, the statistic | logp pair, `rows` [nd][P] momenta or normals and `uni` [nd][nu]
+// uniforms uploaded (null: the generator's)
+int hmc_stage(pinn_engine& E, HmcState& H, const char* who, size_t nd, const double* rows, const double* uni, size_t nu, bool want_samples) {
+    const size_t P = (size_t)H.a.P;
+    if ((want_samples && !dev_grow(H.d_samples, H.samples_cap, nd * P, E.stream)) || !dev_grow(H.d_stat, H.stat_cap, 2 * nd, E.stream) ||
+        (rows && !dev_grow(H.d_mom, H.mom_cap, nd * P, E.stream)) || (uni && !dev_grow(H.d_uni, H.uni_cap, nd * nu, E.stream)))
+        return fail(std::string(who) + ": device allocation failed");
+    if ((rows && plat_h2d(H.d_mom, rows, sizeof(double) * nd * P, E.stream)) || (uni && plat_h2d(H.d_uni, uni, sizeof(double) * nd * nu, E.stream)))
+        return fail(std::string(who) + ": H2D copy failed");
+    return 0;
+}
+// samples (when asked for) | statistic | logp of the nd draws to the host; the caller synchronises
+int hmc_download(pinn_engine& E, HmcState& H, const char* who, size_t nd, double* samples, double* stat, double* logp) {
+    if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * (size_t)H.a.P, E.stream)) || plat_d2h(stat, H.d_stat, sizeof(double) * nd, E.stream) ||
+        plat_d2h(logp, H.d_stat + nd, sizeof(double) * nd, E.stream))
+        return fail(std::string(who) + ": D2H copy failed");
+    return 0;
 }
 
 }  // namespace
@@ -133,50 +163,21 @@ int pinn_hmc_init(pinn_handle h, const double* theta, int64_t p, const double* s
     if (!h || !theta || !stds) return fail(std::string(who) + ": null argument");
     pinn_engine& E = *h;
     if (check_theta(E, who, p)) return 1;
-    const int K = (int)E.terms.size();
-    if (k != K) return fail(std::string(who) + ": " + std::to_string(k) + " standard deviations for " + std::to_string(K) + " loss terms");
-    for (int j = 0; j < K; ++j)
-        if (!(stds[j] > 0.0) || !std::isfinite(stds[j])) return fail(std::string(who) + ": standard deviations must be positive");
-    if (!(nn_sigma > 0.0) || !std::isfinite(nn_sigma) || !std::isfinite(nn_mu)) return fail(std::string(who) + ": the weight prior needs a finite mean and a positive standard deviation");
-    if (n_prior < 0 || n_prior > p) return fail(std::string(who) + ": n_prior must be in 0..P");
-    if (n_prior > 0 && (!prior_kind || !prior_mu || !prior_sigma)) return fail(std::string(who) + ": null prior table");
-    for (int j = 0; j < n_prior; ++j) {
-        if (prior_kind[j] != hmc::PRIOR_NORMAL && prior_kind[j] != hmc::PRIOR_LOGNORMAL) return fail(std::string(who) + ": prior kind must be 0 (Normal) or 1 (LogNormal)");
-        if (!(prior_sigma[j] > 0.0) || !std::isfinite(prior_sigma[j]) || !std::isfinite(prior_mu[j])) return fail(std::string(who) + ": a parameter prior needs a finite mu and a positive sigma");
-    }
-    if (hmc_refuse_target(E, who)) return 1;
+    if (hmc_check_target(E, who, p, stds, k, nullptr, nn_mu, nn_sigma, n_prior, prior_kind, prior_mu, prior_sigma) || hmc_refuse_target(E, who)) return 1;
     DeviceScope scope(E.device);
     if (!E.f64 && ensure_points(E)) return 1;
     const size_t P = (size_t)p;
     std::unique_ptr<HmcState, void (*)(HmcState*)> H(new HmcState, hmc_release);
     H->d_state = (double*)plat_malloc(sizeof(double) * (6 * P + hmc::SC_COUNT));
-    H->d_tab = (double*)plat_malloc(sizeof(double) * (size_t)(2 * n_prior + 3 * K));
-    H->d_kind = (int*)plat_malloc(sizeof(int) * (size_t)std::max(n_prior, 1));
-    if (!H->d_state || !H->d_tab || !H->d_kind) return fail(std::string(who) + ": device allocation failed");
-    // tables: prior, likelihood constants, the evaluation's term weights
-    std::vector<double> tb((size_t)(2 * n_prior + 3 * K)), w((size_t)K);
-    for (int j = 0; j < n_prior; ++j) { tb[j] = prior_mu[j]; tb[n_prior + j] = prior_sigma[j]; }
-    for (int j = 0; j < K; ++j) {
-        const double N = (double)E.terms[j].n, Nn = (double)E.terms[j].n_norm, sd = stds[j];
-        w[j] = Nn / (2.0 * sd * sd);
-        tb[2 * n_prior + j] = -0.5 * N * std::log(2.0 * 3.14159265358979323846) - N * std::log(sd);      // (loglik_from_sse's constants, same order of operations)
-        tb[2 * n_prior + K + j] = 2.0 * sd * sd;
-        tb[2 * n_prior + 2 * K + j] = Nn;
-    }
-    if (H->ev.init(E, who, w.data(), K)) return 1;
-    const bool f64 = H->ev.f64;
+    if (!H->d_state) return fail(std::string(who) + ": device allocation failed");
     hmc::Args& a = H->a;
-    std::memset(&a, 0, sizeof a);
-    a.P = (int)p; a.K = K; a.n_prior = n_prior; a.nn = (int)p - n_prior;
+    std::vector<double> w;                               // the evaluation's term weights
+    if (hmc_target_setup(E, who, p, stds, nn_mu, nn_sigma, n_prior, prior_kind, prior_mu, prior_sigma, H->d_tab, H->d_kind, a, w) || H->ev.init(E, who, w.data(), k)) return 1;
+    const bool f64 = H->ev.f64;
     a.sse_roundtrip = f64 ? 1 : 0;
     a.th_cur = H->d_state; a.th_prop = a.th_cur + P; a.r = a.th_prop + P; a.g_cur = a.r + P; a.g_prop = a.g_cur + P;
     double* minv = a.g_prop + P;
     a.minv = minv; a.sc = minv + P;
-    a.nn_mu = nn_mu; a.nn_sigma = nn_sigma; a.nn_var = nn_sigma * nn_sigma;
-    a.nn_const = (double)a.nn * (std::log(nn_sigma) + 0.5 * std::log(2.0 * 3.14159265358979323846));
-    double* tab = H->d_tab;
-    a.pr_mu = tab; a.pr_sigma = tab + n_prior; a.lik_c = tab + 2 * n_prior; a.lik_d = a.lik_c + K; a.lik_n = a.lik_d + K;
-    a.pr_kind = H->d_kind;
     a.th_eval64 = H->ev.theta64(E);
     a.th_eval32 = H->ev.theta32();
     // host image of the state: theta twice, zero momentum and gradients, unit metric
@@ -184,10 +185,7 @@ int pinn_hmc_init(pinn_handle h, const double* theta, int64_t p, const double* s
     std::copy(theta, theta + P, st.begin());
     std::copy(theta, theta + P, st.begin() + P);
     std::fill(st.begin() + 5 * P, st.begin() + 6 * P, 1.0);
-    std::vector<int> kinds(prior_kind, prior_kind + n_prior);
-    if (plat_h2d(H->d_state, st.data(), sizeof(double) * st.size(), E.stream) || plat_h2d(H->d_tab, tb.data(), sizeof(double) * tb.size(), E.stream) ||
-        (n_prior > 0 && plat_h2d(H->d_kind, kinds.data(), sizeof(int) * kinds.size(), E.stream)))
-        return fail(std::string(who) + ": H2D copy failed");
+    if (plat_h2d(H->d_state, st.data(), sizeof(double) * st.size(), E.stream)) return fail(std::string(who) + ": H2D copy failed");
     if (f64) {
         if (plat_h2d(a.th_eval64, theta, sizeof(double) * P, E.stream)) return fail(std::string(who) + ": H2D copy failed");
     } else {
@@ -197,8 +195,9 @@ int pinn_hmc_init(pinn_handle h, const double* theta, int64_t p, const double* s
     }
     // logp and its gradient at theta: one evaluation, the update kernel with a zero kick (gradient only), the energy kernel at zero momentum
     if (H->ev.eval(E)) return 1;
-    hmc_leap(E, *H, true, 0.0, 0.0, 0);
-    hmc::launch_energy(a, 1, H->ev.sums(P), E.stream);
+    Run R{E, *H};
+    R.leap(hmc::DMODE_EVAL, 0.0, 0.0, 0, 0);
+    R.energy(1);
     plat_d2d(a.g_cur, a.g_prop, sizeof(double) * P, E.stream);
     plat_d2d(a.sc + hmc::SC_LP_CUR, a.sc + hmc::SC_LP_PROP, sizeof(double), E.stream);
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
@@ -215,7 +214,7 @@ int pinn_hmc_set_metric(pinn_handle h, const double* inv_metric, int64_t p) {
     HmcState& H = *E.hmc;
     std::vector<double> m((size_t)p, 1.0);
     for (int64_t i = 0; inv_metric && i < p; ++i) {
-        if (!(inv_metric[i] > 0.0) || !std::isfinite(inv_metric[i])) return fail(std::string(who) + ": the inverse metric must be positive and finite");
+        if (hmc_need_positive(who, "the inverse metric", inv_metric[i])) return 1;
         m[(size_t)i] = inv_metric[i];
     }
     DeviceScope scope(E.device);
@@ -296,43 +295,21 @@ int pinn_hmc_draws(pinn_handle h, int ndraws, int n_leapfrog, double eps, uint64
     if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who)) return 1;
     if (ndraws < 1) return fail(std::string(who) + ": ndraws must be at least 1");
     if (n_leapfrog < 1) return fail(std::string(who) + ": n_leapfrog must be at least 1");
-    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(std::string(who) + ": the step size eps must be positive and finite");
+    if (hmc_need_positive(who, "the step size eps", eps)) return 1;
     HmcState& H = *E.hmc;
     DeviceScope scope(E.device);
     H.a.th_eval64 = H.ev.theta64(E);
     const size_t P = (size_t)p, nd = (size_t)ndraws;
-    if ((samples && !dev_grow(H.d_samples, H.samples_cap, nd * P, E.stream)) || !dev_grow(H.d_stat, H.stat_cap, 2 * nd, E.stream) ||
-        (momenta && !dev_grow(H.d_mom, H.mom_cap, nd * P, E.stream)) || (uniforms && !dev_grow(H.d_uni, H.uni_cap, nd, E.stream)))
-        return fail(std::string(who) + ": device allocation failed");
-    if ((momenta && plat_h2d(H.d_mom, momenta, sizeof(double) * nd * P, E.stream)) || (uniforms && plat_h2d(H.d_uni, uniforms, sizeof(double) * nd, E.stream)))
-        return fail(std::string(who) + ": H2D copy failed");
-    double* d_acc = H.d_stat;
-    double* d_lp = H.d_stat + nd;
-    DenseRun R{E, H};
+    if (hmc_stage(E, H, who, nd, momenta, uniforms, 1, samples != nullptr)) return 1;
+    Run R{E, H};
     for (int d = 0; d < ndraws; ++d) {
         const unsigned ctr = (unsigned)H.draws;
-        if (H.dense) {                                   // the same draw under the dense metric (hmc_dense_kernels.hpp)
-            R.momentum(nullptr, momenta ? H.d_mom + (size_t)d * P : nullptr, seed, ctr);
-            if (R.trajectory(n_leapfrog, eps, 0)) return 1;
-            hmc::launch_accept(R.args(), d, uniforms ? H.d_uni : nullptr, seed, ctr, samples ? H.d_samples : nullptr, d_acc, d_lp, E.stream);
-            ++H.draws;
-            continue;
-        }
-        hmc::launch_momentum(H.a, momenta ? H.d_mom + (size_t)d * P : nullptr, seed, ctr, E.stream);
-        hmc::launch_energy(H.a, 0, nullptr, E.stream);
-        hmc_leap(E, H, false, 0.5 * eps, eps, 1);
-        for (int s = 0; s < n_leapfrog; ++s) {
-            if (H.ev.eval(E)) return 1;                 // (the current state only changes in the accept launch: a failed call leaves the chain at its last completed draw)
-            const bool last = s == n_leapfrog - 1;
-            hmc_leap(E, H, true, last ? 0.5 * eps : eps, eps, last ? 0 : 1);
-        }
-        hmc::launch_energy(H.a, 1, H.ev.sums(P), E.stream);
-        hmc::launch_accept(H.a, d, uniforms ? H.d_uni : nullptr, seed, ctr, samples ? H.d_samples : nullptr, d_acc, d_lp, E.stream);
+        R.momentum(nullptr, momenta ? H.d_mom + (size_t)d * P : nullptr, seed, ctr);
+        if (R.trajectory(n_leapfrog, eps, 0)) return 1;
+        hmc::launch_accept(R.args(), d, uniforms ? H.d_uni : nullptr, seed, ctr, samples ? H.d_samples : nullptr, H.d_stat, H.d_stat + nd, E.stream);
         ++H.draws;
     }
-    if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * P, E.stream)) || plat_d2h(accept_prob, d_acc, sizeof(double) * nd, E.stream) ||
-        plat_d2h(logp, d_lp, sizeof(double) * nd, E.stream))
-        return fail(std::string(who) + ": D2H copy failed");
+    if (hmc_download(E, H, who, nd, samples, accept_prob, logp)) return 1;
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     return 0;
 }
@@ -345,25 +322,20 @@ int pinn_nuts_draws(pinn_handle h, int ndraws, int max_depth, double eps, double
     if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who) || hmc_refuse_dense(E, who, "the U-turn test runs under a diagonal metric")) return 1;
     if (ndraws < 1) return fail(std::string(who) + ": ndraws must be at least 1");
     if (max_depth < 1 || max_depth > nuts::MAX_DEPTH) return fail(std::string(who) + ": max_depth must be in 1.." + std::to_string(nuts::MAX_DEPTH));
-    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(std::string(who) + ": the step size eps must be positive and finite");
-    if (!(delta_max > 0.0) || !std::isfinite(delta_max)) return fail(std::string(who) + ": delta_max must be positive and finite");
+    if (hmc_need_positive(who, "the step size eps", eps) || hmc_need_positive(who, "delta_max", delta_max)) return 1;
     HmcState& H = *E.hmc;
     DeviceScope scope(E.device);
     H.a.th_eval64 = H.ev.theta64(E);
     const size_t P = (size_t)p, nd = (size_t)ndraws, nu = (size_t)(2 * max_depth + (1 << max_depth) - 1);
     if (!H.d_tree) H.d_tree = (double*)plat_malloc(sizeof(double) * (12 + 2 * nuts::MAX_DEPTH) * P);
     if (!H.d_nctl) H.d_nctl = (nuts::Ctl*)plat_malloc(sizeof(nuts::Ctl));
-    if (!H.d_tree || !H.d_nctl || (samples && !dev_grow(H.d_samples, H.samples_cap, nd * P, E.stream)) || !dev_grow(H.d_stat, H.stat_cap, 2 * nd, E.stream) ||
-        !dev_grow(H.d_istat, H.istat_cap, 3 * nd, E.stream) ||
-        (normals && !dev_grow(H.d_mom, H.mom_cap, nd * P, E.stream)) || (uniforms && !dev_grow(H.d_uni, H.uni_cap, nd * nu, E.stream)))
-        return fail(std::string(who) + ": device allocation failed");
+    if (!H.d_tree || !H.d_nctl || !dev_grow(H.d_istat, H.istat_cap, 3 * nd, E.stream)) return fail(std::string(who) + ": device allocation failed");
+    if (hmc_stage(E, H, who, nd, normals, uniforms, nu, samples != nullptr)) return 1;
     nuts::Ctl ctl;
     std::memset(&ctl, 0, sizeof ctl);
     ctl.status = nuts::ST_RUN;
     ctl.fresh = 1;
-    if ((normals && plat_h2d(H.d_mom, normals, sizeof(double) * nd * P, E.stream)) || (uniforms && plat_h2d(H.d_uni, uniforms, sizeof(double) * nd * nu, E.stream)) ||
-        plat_h2d(H.d_nctl, &ctl, sizeof ctl, E.stream))
-        return fail(std::string(who) + ": H2D copy failed");
+    if (plat_h2d(H.d_nctl, &ctl, sizeof ctl, E.stream)) return fail(std::string(who) + ": H2D copy failed");
     nuts::Tree q;
     std::memset(&q, 0, sizeof q);
     q.ctl = H.d_nctl;
@@ -395,9 +367,9 @@ int pinn_nuts_draws(pinn_handle h, int ndraws, int max_depth, double eps, double
         if (read_ctl()) return fail(std::string("device error: ") + plat_last_error());
     }
     H.draws += nd;
-    if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * P, E.stream)) || plat_d2h(accept_stat, q.accept_stat, sizeof(double) * nd, E.stream) ||
-        plat_d2h(logp, q.logp, sizeof(double) * nd, E.stream) || plat_d2h(tree_depth, q.tree_depth, sizeof(int) * nd, E.stream) ||
-        plat_d2h(n_leapfrog, q.n_leapfrog, sizeof(int) * nd, E.stream) || plat_d2h(divergent, q.divergent, sizeof(int) * nd, E.stream))
+    if (hmc_download(E, H, who, nd, samples, accept_stat, logp)) return 1;
+    if (plat_d2h(tree_depth, q.tree_depth, sizeof(int) * nd, E.stream) || plat_d2h(n_leapfrog, q.n_leapfrog, sizeof(int) * nd, E.stream) ||
+        plat_d2h(divergent, q.divergent, sizeof(int) * nd, E.stream))
         return fail(std::string(who) + ": D2H copy failed");
     if (plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
     return 0;
@@ -408,7 +380,7 @@ int pinn_hmc_find_stepsize(pinn_handle h, double eps0, uint64_t seed, const doub
     if (!h || !eps) return fail(std::string(who) + ": null argument");
     pinn_engine& E = *h;
     if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who)) return 1;
-    if (!(eps0 > 0.0) || !std::isfinite(eps0)) return fail(std::string(who) + ": the step size eps0 must be positive and finite");
+    if (hmc_need_positive(who, "the step size eps0", eps0)) return 1;
     HmcState& H = *E.hmc;
     DeviceScope scope(E.device);
     H.a.th_eval64 = H.ev.theta64(E);
@@ -417,29 +389,18 @@ int pinn_hmc_find_stepsize(pinn_handle h, double eps0, uint64_t seed, const doub
         return fail(std::string(who) + ": device allocation failed");
     if (normals && plat_h2d(H.d_mom, normals, sizeof(double) * P, E.stream)) return fail(std::string(who) + ": H2D copy failed");
     // r0 and h0 = -logp(current) + 1/2 sum minv r0^2; the current state, its gradient and logp are only read from here on
-    DenseRun R{E, H};
-    if (H.dense) R.momentum(normals ? H.d_mom : nullptr, nullptr, seed, 0xFFFFFFFFu);
-    else {
-        hmc::launch_momentum_z(H.a, normals ? H.d_mom : nullptr, seed, 0xFFFFFFFFu, E.stream);
-        hmc::launch_energy(H.a, 0, nullptr, E.stream);
-    }
-    plat_d2d(H.d_r0, H.dense ? R.r() : H.a.r, sizeof(double) * P, E.stream);
+    Run R{E, H};
+    R.momentum(normals ? H.d_mom : nullptr, nullptr, seed, 0xFFFFFFFFu);
+    plat_d2d(H.d_r0, R.r(), sizeof(double) * P, E.stream);
     const double log08 = std::log(0.8);
     double e = eps0, direction = 0.0;
     int trials = 0;
     for (int t = 0; t <= 40; ++t) {
         if (t > 0) {
             e *= direction > 0 ? 2.0 : 0.5;
-            plat_d2d(H.dense ? R.r() : H.a.r, H.d_r0, sizeof(double) * P, E.stream);
+            plat_d2d(R.r(), H.d_r0, sizeof(double) * P, E.stream);
         }
-        if (H.dense) {
-            if (R.trajectory(1, e, 0)) return 1;
-        } else {
-            hmc_leap(E, H, false, 0.5 * e, e, 1);
-            if (H.ev.eval(E)) return 1;
-            hmc_leap(E, H, true, 0.5 * e, e, 0);
-            hmc::launch_energy(H.a, 1, H.ev.sums(P), E.stream);
-        }
+        if (R.trajectory(1, e, 0)) return 1;
         double hh[2];                                    // H_old, H_new: neighbours in the scalar block
         if (plat_d2h(hh, H.a.sc + hmc::SC_H_OLD, sizeof hh, E.stream) || plat_sync(E.stream)) return fail(std::string("device error: ") + plat_last_error());
         double d = hh[0] - hh[1];
@@ -464,60 +425,35 @@ int pinn_hmc_warmup(pinn_handle h, int n_adapts, int n_leapfrog, double eps0, do
     if (hmc_ready(E, who) || check_theta(E, who, p) || hmc_refuse_target(E, who)) return 1;
     if (n_adapts < 1) return fail(std::string(who) + ": n_adapts must be at least 1");
     if (n_leapfrog < 1) return fail(std::string(who) + ": n_leapfrog must be at least 1");
-    if (!(eps0 > 0.0) || !std::isfinite(eps0)) return fail(std::string(who) + ": the step size eps0 must be positive and finite");
+    if (hmc_need_positive(who, "the step size eps0", eps0)) return 1;
     if (!(target > 0.0) || !(target < 1.0)) return fail(std::string(who) + ": the target acceptance rate must be in (0, 1)");
     HmcState& H = *E.hmc;
     DeviceScope scope(E.device);
     H.a.th_eval64 = H.ev.theta64(E);
     const size_t P = (size_t)p, nd = (size_t)n_adapts;
-    if (!dev_grow(H.d_samples, H.samples_cap, nd * P, E.stream) || !dev_grow(H.d_stat, H.stat_cap, 2 * nd, E.stream) ||
-        !dev_grow(H.d_steps, H.steps_cap, nd + 1, E.stream) ||
-        (normals && !dev_grow(H.d_mom, H.mom_cap, nd * P, E.stream)) || (uniforms && !dev_grow(H.d_uni, H.uni_cap, nd, E.stream)))
-        return fail(std::string(who) + ": device allocation failed");
+    if (!dev_grow(H.d_steps, H.steps_cap, nd + 1, E.stream)) return fail(std::string(who) + ": device allocation failed");
+    if (hmc_stage(E, H, who, nd, normals, uniforms, 1, true)) return 1;      // (the sample buffer whether or not the caller wants it: the metric's window)
     // eps, mu, hbar, log_eps_bar, m: neighbours in the scalar block; step_sizes[0]
     const double sc0[5] = {eps0, std::log(10.0 * eps0), 0.0, 0.0, 0.0};
-    if ((normals && plat_h2d(H.d_mom, normals, sizeof(double) * nd * P, E.stream)) || (uniforms && plat_h2d(H.d_uni, uniforms, sizeof(double) * nd, E.stream)) ||
-        plat_h2d(H.a.sc + hmc::SC_EPS, sc0, sizeof sc0, E.stream) || plat_h2d(H.d_steps, sc0, sizeof(double), E.stream))
+    if (plat_h2d(H.a.sc + hmc::SC_EPS, sc0, sizeof sc0, E.stream) || plat_h2d(H.d_steps, sc0, sizeof(double), E.stream))
         return fail(std::string(who) + ": H2D copy failed");
     const int w0 = (int)(0.15 * (double)n_adapts), w1 = (int)(0.9 * (double)n_adapts);      // the variance window of the metric
     const bool metric_event = w1 - w0 >= 8 && n_adapts >= 100;
-    double* d_acc = H.d_stat;
-    double* d_lp = H.d_stat + nd;
-    DenseRun R{E, H};
+    Run R{E, H};
     int dflag[hmc::DF_COUNT] = {0, -1, 0, -1};
     if (H.dense && plat_h2d(H.dn.flag, dflag, sizeof dflag, E.stream)) return fail(std::string(who) + ": H2D copy failed");
     for (int d = 0; d < n_adapts; ++d) {
         const unsigned ctr = (unsigned)H.draws;
-        if (H.dense) {                                   // the same draw and adaptation under the dense metric
-            R.momentum(normals ? H.d_mom + (size_t)d * P : nullptr, nullptr, seed, ctr);
-            if (R.trajectory(n_leapfrog, 0.0, 1)) return 1;
-            const bool restart = metric_event && d == w1 - 1;
-            const int flags = (restart ? hmc::ADAPT_RESTART : 0) | (d == n_adapts - 1 ? hmc::ADAPT_LAST : 0);
-            hmc::launch_accept_adapt(R.args(), d, uniforms ? H.d_uni : nullptr, seed, ctr, H.d_samples, d_acc, d_lp, target, flags, H.d_steps, E.stream);
-            if (restart) {                               // the window's regularised covariance, staged; a bad pivot keeps the old metric
-                hmc::launch_cov(H.a, H.dn, H.d_samples, w0, w1, E.stream);
-                dense_refactor(E, H);
-            }
-            ++H.draws;
-            continue;
-        }
-        hmc::launch_momentum_z(H.a, normals ? H.d_mom + (size_t)d * P : nullptr, seed, ctr, E.stream);
-        hmc::launch_energy(H.a, 0, nullptr, E.stream);
-        hmc_leap_dev(E, H, false, 0.5, 1);
-        for (int s = 0; s < n_leapfrog; ++s) {
-            if (H.ev.eval(E)) return 1;                 // (the chain is at its last completed draw, under the metric in force there)
-            const bool last = s == n_leapfrog - 1;
-            hmc_leap_dev(E, H, true, last ? 0.5 : 1.0, last ? 0 : 1);
-        }
-        hmc::launch_energy(H.a, 1, H.ev.sums(P), E.stream);
+        R.momentum(normals ? H.d_mom + (size_t)d * P : nullptr, nullptr, seed, ctr);
+        if (R.trajectory(n_leapfrog, 0.0, 1)) return 1;  // (on failure the chain is at its last completed draw, under the metric in force there)
         const bool restart = metric_event && d == w1 - 1;
         const int flags = (restart ? hmc::ADAPT_RESTART : 0) | (d == n_adapts - 1 ? hmc::ADAPT_LAST : 0);
-        hmc::launch_accept_adapt(H.a, d, uniforms ? H.d_uni : nullptr, seed, ctr, H.d_samples, d_acc, d_lp, target, flags, H.d_steps, E.stream);
-        if (restart) hmc::launch_window_metric(H.a, H.d_samples, w0, w1, E.stream);
+        hmc::launch_accept_adapt(R.args(), d, uniforms ? H.d_uni : nullptr, seed, ctr, H.d_samples, H.d_stat, H.d_stat + nd, target, flags, H.d_steps, E.stream);
+        if (restart) R.metric_event(w0, w1);
         ++H.draws;
     }
-    if ((samples && plat_d2h(samples, H.d_samples, sizeof(double) * nd * P, E.stream)) || plat_d2h(accept_prob, d_acc, sizeof(double) * nd, E.stream) ||
-        plat_d2h(logp, d_lp, sizeof(double) * nd, E.stream) || (step_sizes && plat_d2h(step_sizes, H.d_steps, sizeof(double) * nd, E.stream)) ||
+    if (hmc_download(E, H, who, nd, samples, accept_prob, logp)) return 1;
+    if ((step_sizes && plat_d2h(step_sizes, H.d_steps, sizeof(double) * nd, E.stream)) ||
         plat_d2h(eps_final, H.d_steps + nd, sizeof(double), E.stream) ||
         (inv_metric && plat_d2h(inv_metric, H.dense ? H.dn.diag : H.a.minv, sizeof(double) * P, E.stream)) ||
         (H.dense && plat_d2h(dflag, H.dn.flag, sizeof dflag, E.stream)))

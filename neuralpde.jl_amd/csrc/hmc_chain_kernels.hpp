@@ -103,14 +103,7 @@ DEV void chain_energy(const ChainArgs& ca, const ChainView& v, int w, int mode, 
 #ifdef PINN_EMU
     double q[2][64];
     for (int l = 0; l < 64; ++l) hmc::energy_partial(w * 64 + l, v.a, mode == 1, q[0][l], q[1][l]);
-    for (int j = 0; j < 2; ++j) {
-        for (int m = 32; m >= 1; m >>= 1) {
-            double n[64];
-            for (int l = 0; l < 64; ++l) n[l] = q[j][l] + q[j][l ^ m];
-            for (int l = 0; l < 64; ++l) q[j][l] = n[l];
-        }
-        v.sh[j * 4 + w] = q[j][0];
-    }
+    for (int j = 0; j < 2; ++j) v.sh[j * 4 + w] = hmc::wave_butterfly(q[j]);
 #else
     double kin, pri;
     hmc::energy_partial((int)threadIdx.x, v.a, mode == 1, kin, pri);
@@ -182,7 +175,7 @@ DEV void wave_hmc_chains(const GroupArgs& ga, const ChainArgs& ca, int chain, in
         const unsigned key = chain_key(ca.seed_lo, ca.seed_hi, ca.ctr0 + (unsigned)d, (unsigned)chain);
         const double* row = ca.momenta ? ca.momenta + (c * (size_t)ca.ndraws + (size_t)d) * P : nullptr;
         { CHAIN_THREADS(t, w)
-            for (int i = t; i < a.P; i += hmc::BLOCK) hmc::momentum_body(i, a, row, key); }
+            for (int i = t; i < a.P; i += hmc::BLOCK) hmc::momentum_body(i, a, nullptr, row, key); }
         chain_energy(ca, v, w, 0, ga.nterms_total);
         { CHAIN_THREADS(t, w)
             for (int i = t; i < a.P; i += hmc::BLOCK) {

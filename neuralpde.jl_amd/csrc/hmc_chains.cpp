@@ -3,7 +3,7 @@
 // The state has buffers of its own — per chain: theta / momentum / gradients / energies in double, a weight image, a parameter row, record
 // scratch, a gradient slab, loss partials — so evaluations, pinn_adam_* and pinn_hmc_* on the same handle leave it alone, and it leaves them
 // alone; the handle's kernel plan (launch arguments, reduce map, inverse pack map) is read afresh by every call.
-#include "resident.hpp"
+#include "hmc_host.hpp"
 
 using namespace pe;
 
@@ -101,31 +101,18 @@ int pinn_hmc_chains_init(pinn_handle h, int nchains, const double* theta, int64_
     if (check_theta(E, who, p) || hmc_refuse_dense(E, who, "the chain kernel keeps a diagonal metric in LDS")) return 1;
     if (nchains < 1 || nchains > pk::CHAIN_MAX_CHAINS) return fail(std::string(who) + ": nchains must be in 1.." + std::to_string(pk::CHAIN_MAX_CHAINS));
     if (n_leapfrog < 1) return fail(std::string(who) + ": n_leapfrog must be at least 1");
-    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(std::string(who) + ": the step size eps must be positive and finite");
-    const int K = (int)E.terms.size();
-    if (k != K) return fail(std::string(who) + ": " + std::to_string(k) + " standard deviations for " + std::to_string(K) + " loss terms");
-    for (int j = 0; j < K; ++j)
-        if (!(stds[j] > 0.0) || !std::isfinite(stds[j])) return fail(std::string(who) + ": standard deviations must be positive");
-    for (int64_t i = 0; inv_metric && i < p; ++i)
-        if (!(inv_metric[i] > 0.0) || !std::isfinite(inv_metric[i])) return fail(std::string(who) + ": the inverse metric must be positive and finite");
-    if (!(nn_sigma > 0.0) || !std::isfinite(nn_sigma) || !std::isfinite(nn_mu)) return fail(std::string(who) + ": the weight prior needs a finite mean and a positive standard deviation");
-    if (n_prior < 0 || n_prior > p) return fail(std::string(who) + ": n_prior must be in 0..P");
-    if (n_prior > 0 && (!prior_kind || !prior_mu || !prior_sigma)) return fail(std::string(who) + ": null prior table");
-    for (int j = 0; j < n_prior; ++j) {
-        if (prior_kind[j] != hmc::PRIOR_NORMAL && prior_kind[j] != hmc::PRIOR_LOGNORMAL) return fail(std::string(who) + ": prior kind must be 0 (Normal) or 1 (LogNormal)");
-        if (!(prior_sigma[j] > 0.0) || !std::isfinite(prior_sigma[j]) || !std::isfinite(prior_mu[j])) return fail(std::string(who) + ": a parameter prior needs a finite mu and a positive sigma");
-    }
+    if (hmc_need_positive(who, "the step size eps", eps)) return 1;
+    if (hmc_check_target(E, who, p, stds, k, inv_metric, nn_mu, nn_sigma, n_prior, prior_kind, prior_mu, prior_sigma)) return 1;
     if (chains_eligible(E, who)) return 1;
     DeviceScope scope(E.device);
     if (ensure_points(E)) return 1;
     const pk::SpecInfo& S = *E.groups[0].spec;
+    const int K = (int)E.terms.size();
     const size_t P = (size_t)p, nc = (size_t)nchains, row = 5 * P + hmc::SC_COUNT;
     std::unique_ptr<ChainsState, void (*)(ChainsState*)> C(new ChainsState, chains_release);
     C->nchains = nchains; C->n_leapfrog = n_leapfrog; C->K = K; C->n_prior = n_prior; C->P = p; C->eps = eps; C->seed = seed; C->spec = &S;
     C->d_state = (double*)plat_malloc(sizeof(double) * nc * row);
     C->d_minv = (double*)plat_malloc(sizeof(double) * P);
-    C->d_tab = (double*)plat_malloc(sizeof(double) * (size_t)(2 * n_prior + 3 * K));
-    C->d_kind = (int*)plat_malloc(sizeof(int) * (size_t)std::max(n_prior, 1));
     C->d_packed = (float*)plat_malloc(sizeof(float) * nc * (size_t)S.PACKED);
     C->d_params = (float*)plat_malloc(sizeof(float) * nc * pk::MAX_PARAMS);
     C->d_ev = (float*)plat_malloc(sizeof(float) * nc * P);
@@ -133,35 +120,20 @@ int pinn_hmc_chains_init(pinn_handle h, int nchains, const double* theta, int64_
     C->d_slabs = (float*)plat_malloc(sizeof(float) * nc * (size_t)S.SLAB);
     C->d_losspart = (double*)plat_malloc(sizeof(double) * nc * 4 * (size_t)K);
     C->d_scratch = (float*)plat_malloc(sizeof(float) * std::max<size_t>(nc * 4 * (size_t)S.SCR, 1));      // (register-resident records: SCR = 0)
-    if (!C->d_state || !C->d_minv || !C->d_tab || !C->d_kind || !C->d_packed || !C->d_params || !C->d_ev || !C->d_sse || !C->d_slabs || !C->d_losspart || !C->d_scratch)
+    if (!C->d_state || !C->d_minv || !C->d_packed || !C->d_params || !C->d_ev || !C->d_sse || !C->d_slabs || !C->d_losspart || !C->d_scratch)
         return fail(std::string(who) + ": device allocation failed");
-    // tables: priors, likelihood constants (pinn_hmc_init's, same order of operations), the reverse sweep's seeds
-    std::vector<double> tb((size_t)(2 * n_prior + 3 * K));
-    C->scale.resize((size_t)K);
-    for (int j = 0; j < n_prior; ++j) { tb[j] = prior_mu[j]; tb[n_prior + j] = prior_sigma[j]; }
-    for (int j = 0; j < K; ++j) {
-        const double N = (double)E.terms[j].n, Nn = (double)E.terms[j].n_norm, sd = stds[j];
-        const float w = (float)(Nn / (2.0 * sd * sd));
-        C->scale[(size_t)j] = (float)(2.0 * (double)w / (double)E.terms[j].n_norm);      // (adam.cpp train_common's expression)
-        tb[2 * n_prior + j] = -0.5 * N * std::log(2.0 * 3.14159265358979323846) - N * std::log(sd);
-        tb[2 * n_prior + K + j] = 2.0 * sd * sd;
-        tb[2 * n_prior + 2 * K + j] = Nn;
-    }
+    // the target's tables; the reverse sweep's seeds from the evaluation's term weights, narrowed as the evaluation takes them
     hmc::Args& a = C->a;
-    std::memset(&a, 0, sizeof a);
-    a.P = (int)p; a.K = K; a.n_prior = n_prior; a.nn = (int)p - n_prior;
+    std::vector<double> w;
+    if (hmc_target_setup(E, who, p, stds, nn_mu, nn_sigma, n_prior, prior_kind, prior_mu, prior_sigma, C->d_tab, C->d_kind, a, w)) return 1;
+    C->scale.resize((size_t)K);
+    for (int j = 0; j < K; ++j) C->scale[(size_t)j] = (float)(2.0 * (double)(float)w[(size_t)j] / (double)E.terms[j].n_norm);      // (adam.cpp train_common's expression)
     a.minv = C->d_minv;
-    a.nn_mu = nn_mu; a.nn_sigma = nn_sigma; a.nn_var = nn_sigma * nn_sigma;
-    a.nn_const = (double)a.nn * (std::log(nn_sigma) + 0.5 * std::log(2.0 * 3.14159265358979323846));
-    a.pr_mu = C->d_tab; a.pr_sigma = C->d_tab + n_prior; a.lik_c = C->d_tab + 2 * n_prior; a.lik_d = a.lik_c + K; a.lik_n = a.lik_d + K;
-    a.pr_kind = C->d_kind;
     // host image of the state: per chain theta as current state, everything else zero; the metric (ones when null)
     std::vector<double> st(nc * row, 0.0), minv(P, 1.0);
     for (size_t c = 0; c < nc; ++c) std::copy(theta + c * P, theta + (c + 1) * P, st.begin() + c * row);
     if (inv_metric) std::copy(inv_metric, inv_metric + P, minv.begin());
-    std::vector<int> kinds(prior_kind, prior_kind + n_prior);
-    if (plat_h2d(C->d_state, st.data(), sizeof(double) * st.size(), E.stream) || plat_h2d(C->d_minv, minv.data(), sizeof(double) * P, E.stream) ||
-        plat_h2d(C->d_tab, tb.data(), sizeof(double) * tb.size(), E.stream) || (n_prior > 0 && plat_h2d(C->d_kind, kinds.data(), sizeof(int) * kinds.size(), E.stream)))
+    if (plat_h2d(C->d_state, st.data(), sizeof(double) * st.size(), E.stream) || plat_h2d(C->d_minv, minv.data(), sizeof(double) * P, E.stream))
         return fail(std::string(who) + ": H2D copy failed");
     // the images' padding and the parameter rows start at zero (aux::k_pack writes zeros where no parameter lands)
     plat_memset(C->d_packed, 0, sizeof(float) * nc * (size_t)S.PACKED, E.stream);

@@ -1,12 +1,12 @@
 // hmc_dense_kernels.hpp — the dense Euclidean metric of the resident HMC sampler (pinn_hmc_set_metric_dense).  The chain of
-// hmc_kernels.hpp under a full inverse metric M^-1 = L L^T: r = L^-T z, theta += eps (M^-1 r), kinetic energy 1/2 r.(M^-1 r).  Selected on the host;
-// the diagonal launches of hmc_kernels.hpp are untouched.  M^-1 and L are [ld][ld] row-major, ld = P rounded up to 64, pads zero, L's strict upper zero.
-//   k_hmc_dense_leap<T>    ONE launch per leapfrog step.  Every workgroup rebuilds the whole kicked momentum r' = r + kick g in LDS (g as leap_body forms
-//                          it), then forms its own 16 rows of v = M^-1 r': a wave takes 4 rows at a time, its lanes stride the columns (a row is read in
-//                          whole 512-byte lines), lane partials, then the xor butterfly 32 ... 1.  Lanes 0..3 own the wave's rows: g_prop, r', v, and,
+// hmc_kernels.hpp under a full inverse metric M^-1 = L L^T: r = L^-T z, theta += eps (M^-1 r), kinetic energy 1/2 r.(M^-1 r).  Selected on the host
+// (hmc.cpp: Run); the energy and accept launches are those of hmc_kernels.hpp, k_hmc_energy taking v = M^-1 r.  M^-1 and L are [ld][ld] row-major,
+// ld = P rounded up to 64, pads zero, L's strict upper zero.
+//   k_hmc_dense_leap<T>    ONE launch per leapfrog step.  Every workgroup rebuilds the whole kicked momentum r' = r + kick g in LDS (g = hmc::logp_grad, as
+//                          leap_body forms it), then forms its own 16 rows of v = M^-1 r': a wave takes 4 rows at a time, its lanes stride the columns (a row is
+//                          read in whole 512-byte lines), lane partials, then the xor butterfly 32 ... 1.  Lanes 0..3 own the wave's rows: g_prop, r', v, and,
 //                          drifting, theta and the evaluation's copy of it.  Momentum and theta PING-PONG between two buffers each (every workgroup reads
 //                          all of r and theta): no workgroup reads in a launch what another writes in it.  DMODE_PRODUCT: v = M^-1 r alone.
-//   k_hmc_energy_dense     k_hmc_energy with kin = sum r_i v_i, in energy_partial's thread and wave order
 //   k_hmc_dense_momentum   L^T r = z by back-substitution in ONE workgroup, 64-wide blocks from the last to the first: wave 0 solves the diagonal
 //                          block in registers (lane j holds column j of the block and its right-hand side; 64 shuffle steps), then all four waves
 //                          subtract the block's part from the right-hand side above it (thread t takes elements t, t + 256, ...; the block's 64
@@ -50,7 +50,7 @@ struct LeapIO {                          // the ping-pong pairs of one leap laun
 
 inline int dense_ld(int P) { return (P + DB - 1) / DB * DB; }
 
-// r'_i = r_i + kick g_i with g as leap_body forms it; g and theta_i for the row's owner
+// r'_i = r_i + kick g_i with leap_body's g; g and theta_i for the row's owner
 template <class T> HMC_DEV double dense_kicked(int i, const Args& a, const T* ev, const LeapIO& io, int mode, double kick, double& g, double& x) {
     HMC_NO_CONTRACT
     g = 0.0; x = 0.0;
@@ -60,13 +60,7 @@ template <class T> HMC_DEV double dense_kicked(int i, const Args& a, const T* ev
         x = a.th_cur[i];
     } else {
         x = io.th_in[i];
-        g = -(double)ev[i];
-        if (i < a.nn) g -= (x - a.nn_mu) / a.nn_var;
-        else {
-            double l, d;
-            prior_logpdf_grad(a, i - a.nn, x, l, d);
-            g += d;
-        }
+        g = logp_grad<T>(i, a, ev, x);
     }
     return io.r_in[i] + kick * g;
 }
@@ -93,17 +87,6 @@ template <class T> HMC_DEV void dense_owner(int i, const Args& a, const Dense& d
         io.th_out[i] = x;
         if (a.th_eval64) a.th_eval64[i] = x;
         if (a.th_eval32) a.th_eval32[i] = (float)x;
-    }
-}
-HMC_DEV void energy_partial_dense(int t, const Args& a, const double* v, int with_prior, double& kin, double& pri) {
-    HMC_NO_CONTRACT
-    kin = 0.0; pri = 0.0;
-    for (int i = t; i < a.P; i += BLOCK) {
-        kin += a.r[i] * v[i];
-        if (with_prior && i < a.nn) {
-            const double z = (a.th_prop[i] - a.nn_mu) / a.nn_sigma;
-            pri += z * z;
-        }
     }
 }
 HMC_DEV void dense_mean_body(int i, int P, const Dense& dn, const double* samples, int w0, int w1) {
@@ -183,15 +166,6 @@ HMC_DEV void cov_tile(int P, const Dense& dn, const double* samples, int w0, int
 }
 
 #ifdef PINN_EMU
-inline double dense_butterfly(double* v) {
-    HMC_NO_CONTRACT
-    for (int m = 32; m >= 1; m >>= 1) {
-        double n[64];
-        for (int l = 0; l < 64; ++l) n[l] = v[l] + v[l ^ m];
-        for (int l = 0; l < 64; ++l) v[l] = n[l];
-    }
-    return v[0];
-}
 template <class T> inline void launch_dense_leap(const Args& a, const Dense& dn, const T* ev, const LeapIO& io, int mode, double kick, double eps, int from_sc, int drift, plat_stream) {
     HMC_NO_CONTRACT
     if (from_sc) { eps = a.sc[SC_EPS]; kick = kick * eps; }
@@ -205,21 +179,9 @@ template <class T> inline void launch_dense_leap(const Args& a, const Dense& dn,
             dense_rows_partial(dn, row0, l, sh.data(), acc);
             for (int k = 0; k < 4; ++k) part[k][l] = acc[k];
         }
-        for (int k = 0; k < 4; ++k) v[row0 + k] = dense_butterfly(part[k]);
+        for (int k = 0; k < 4; ++k) v[row0 + k] = wave_butterfly(part[k]);
     }
     for (int i = 0; i < a.P; ++i) dense_owner<T>(i, a, dn, ev, io, mode, kick, eps, drift, v[i]);
-}
-inline void launch_energy_dense(const Args& a, const Dense& dn, int mode, const double* sse, plat_stream) {
-    double tot[2] = {0.0, 0.0};
-    for (int w = 0; w < BLOCK / 64; ++w) {
-        double v[2][64];
-        for (int l = 0; l < 64; ++l) energy_partial_dense(w * 64 + l, a, dn.v, mode == 1, v[0][l], v[1][l]);
-        for (int q = 0; q < 2; ++q) {
-            const double s = dense_butterfly(v[q]);
-            tot[q] = w == 0 ? s : tot[q] + s;
-        }
-    }
-    energy_finish(a, mode, tot[0], tot[1], sse);
 }
 inline void launch_dense_momentum(const Args& a, const Dense& dn, const double* z, uint64_t seed, unsigned draw, double* r_out, plat_stream) {
     HMC_NO_CONTRACT
@@ -303,22 +265,6 @@ template <class T> __global__ void __launch_bounds__(BLOCK) k_hmc_dense_leap(con
         for (int k = 0; k < 4; ++k) acc[k] += __shfl_xor(acc[k], m, 64);
     const double vi = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
     if (lane < 4 && row0 + lane < a.P) dense_owner<T>(row0 + lane, a, dn, ev, io, mode, kick, eps, drift, vi);
-}
-__global__ void __launch_bounds__(BLOCK) k_hmc_energy_dense(const Args a, const Dense dn, int mode, const double* sse) {
-    __shared__ double sh[2][BLOCK / 64];
-    double kin, pri;
-    energy_partial_dense((int)threadIdx.x, a, dn.v, mode == 1, kin, pri);
-    for (int m = 32; m >= 1; m >>= 1) {
-        kin += __shfl_xor(kin, m, 64);
-        pri += __shfl_xor(pri, m, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = kin; sh[1][threadIdx.x >> 6] = pri; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        kin = sh[0][0]; pri = sh[1][0];
-        for (int w = 1; w < BLOCK / 64; ++w) { kin += sh[0][w]; pri += sh[1][w]; }
-        energy_finish(a, mode, kin, pri, sse);
-    }
 }
 __global__ void __launch_bounds__(BLOCK) k_hmc_dense_momentum(const Args a, const Dense dn, const double* z, unsigned seed_lo, unsigned seed_hi, unsigned draw, double* r_out) {
     HMC_NO_CONTRACT
@@ -417,9 +363,6 @@ __global__ void __launch_bounds__(BLOCK) k_hmc_dense_commit(const Args a, const 
 }
 template <class T> inline void launch_dense_leap(const Args& a, const Dense& dn, const T* ev, const LeapIO& io, int mode, double kick, double eps, int from_sc, int drift, plat_stream st) {
     hipLaunchKernelGGL(k_hmc_dense_leap<T>, dim3((a.P + LEAP_ROWS - 1) / LEAP_ROWS), dim3(BLOCK), sizeof(double) * (size_t)dn.ld, st, a, dn, ev, io, mode, kick, eps, from_sc, drift);
-}
-inline void launch_energy_dense(const Args& a, const Dense& dn, int mode, const double* sse, plat_stream st) {
-    hipLaunchKernelGGL(k_hmc_energy_dense, dim3(1), dim3(BLOCK), 0, st, a, dn, mode, sse);
 }
 inline void launch_dense_momentum(const Args& a, const Dense& dn, const double* z, uint64_t seed, unsigned draw, double* r_out, plat_stream st) {
     hipLaunchKernelGGL(k_hmc_dense_momentum, dim3(1), dim3(BLOCK), sizeof(double) * (size_t)dn.ld, st, a, dn, z, (unsigned)seed, (unsigned)(seed >> 32), draw, r_out);

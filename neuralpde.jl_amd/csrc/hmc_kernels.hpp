@@ -2,16 +2,18 @@
 // not the evaluation of the physics / data likelihood.  theta, momentum, inverse metric, log-posterior gradient and the energies live on the
 // device in double; the host queues   momentum -> energy(old) -> [update -> evaluation] x n_leapfrog -> update -> energy(new) -> accept
 // per draw and reads nothing back before the call's single download.
-//   k_hmc_momentum : r_i = z_i / sqrt(minv_i), z from the counter-based generator below (or row i of the caller's momenta)
+//   k_hmc_momentum : r_i = z_i / sqrt(minv_i), z from the counter-based generator (hmc_rules.hpp) or the caller's standard normals — the
+//                    warm-up's metric changes inside the call —, or row i of the caller's finished momenta as given
 //   k_hmc_leap<T>  : ONE launch per leapfrog step: log-posterior gradient from the evaluation's [gradient | sums] vector (T = double in float64
-//                    mode, float otherwise) + the priors' gradient at theta_i, kick, drift, the copy of theta the next evaluation reads
-//   k_hmc_energy   : kinetic energy, log-prior, log-likelihood (from the K sums of squares) and H, one workgroup; double sums in a FIXED order:
-//                    thread t takes elements t, t + 256, ...; per-wave butterfly (xor 32, 16, ... 1); the four waves in order.  No atomics.
+//                    mode, float otherwise) + the priors' gradient at theta_i, kick, drift, the copy of theta the next evaluation reads.
+//                    from_sc (the warm-up; a template flag of the kernel): eps read from the scalar block (a uniform load), kick = kfac * eps,
+//                    kfac in {1/2, 1} from the host
+//   k_hmc_energy   : kinetic energy (sum minv r^2, or sum r v with v = M^-1 r of hmc_dense_kernels.hpp), log-prior, log-likelihood (from the K
+//                    sums of squares) and H, one workgroup; double sums in a FIXED order: thread t takes elements t, t + 256, ...; per-wave
+//                    butterfly (xor 32, 16, ... 1); the four waves in order.  No atomics.
 //   k_hmc_accept   : a = exp(min(0, H_old - H_new)) (0 when H_new is not finite), u < a, elementwise selection of theta / gradient / logp,
 //                    row `draw` of the sample buffer, accept_prob[draw], logp[draw]
 // The warm-up (pinn_hmc_find_stepsize / pinn_hmc_warmup) adds, with the same bodies where a body exists:
-//   k_hmc_momentum_z      : r_i = z_i / sqrt(minv_i) with z from the caller's standard normals (or the generator): the metric changes inside the call
-//   k_hmc_leap_dev<T>     : leap_body with eps read from the scalar block (a uniform load), kick = kfac * eps, kfac in {1/2, 1} from the host
 //   k_hmc_accept_adapt    : accept_body; element 0 then runs adapt_body — dual averaging of eps (bpinn.py `_hmc_device`), the restart after a
 //                           metric event, the final average — and writes the next draw's eps to the scalar block and to step_sizes[draw + 1]
 //   k_hmc_window_metric   : minv_i = (k / (k + 5)) var_i + 1e-3 (5 / (k + 5)), var_i the population variance of column i over sample rows
@@ -25,10 +27,6 @@
 namespace hmc {
 
 // ---- the warm-up ----
-HMC_DEV void momentum_z_body(int i, const Args& a, const double* z, unsigned key) {
-    a.r[i] = (z ? z[i] : rng_normal(key, (unsigned)i)) / sqrt(a.minv[i]);
-}
-
 // bpinn.py `_hmc_device`, the adaptation after a draw with acceptance probability `acc`, in its order of operations; element 0 of the accept
 // launch only.  flags: what the host knows from (draw, n_adapts) alone.  `next` = step_sizes[draw + 1] (the final step size after the last draw).
 HMC_DEV void adapt_body(const Args& a, double acc, double target, int flags, double* next) {
@@ -66,25 +64,26 @@ HMC_DEV void window_metric_body(int i, const Args& a, double* minv, const double
 }
 
 #ifdef PINN_EMU
-inline void launch_momentum(const Args& a, const double* row, uint64_t seed, unsigned draw, plat_stream) {
+inline void launch_momentum(const Args& a, const double* z, const double* given, uint64_t seed, unsigned draw, plat_stream) {
     const unsigned key = rng_key((unsigned)seed, (unsigned)(seed >> 32), draw);
-    for (int i = 0; i < a.P; ++i) momentum_body(i, a, row, key);
+    for (int i = 0; i < a.P; ++i) momentum_body(i, a, z, given, key);
 }
-template <class T> inline void launch_leap(const Args& a, const T* ev, double kick, double eps, int drift, plat_stream) {
+template <class T> inline void launch_leap(const Args& a, const T* ev, double kick, double eps, int from_sc, int drift, plat_stream) {
+    HMC_NO_CONTRACT
+    if (from_sc) { eps = a.sc[SC_EPS]; kick = kick * eps; }
     for (int i = 0; i < a.P; ++i) leap_body<T>(i, a, ev, kick, eps, drift);
 }
-inline void launch_energy(const Args& a, int mode, const double* sse, plat_stream) {
+inline void launch_energy(const Args& a, int mode, const double* sse, const double* v, plat_stream) {
     double tot[2] = {0.0, 0.0};
     for (int w = 0; w < BLOCK / 64; ++w) {
-        double v[2][64];
-        for (int l = 0; l < 64; ++l) energy_partial(w * 64 + l, a, mode == 1, v[0][l], v[1][l]);
+        double part[2][64];
+        for (int l = 0; l < 64; ++l) {
+            if (v) energy_partial<true>(w * 64 + l, a, mode == 1, part[0][l], part[1][l], v);
+            else energy_partial(w * 64 + l, a, mode == 1, part[0][l], part[1][l]);
+        }
         for (int q = 0; q < 2; ++q) {
-            for (int m = 32; m >= 1; m >>= 1) {          // the device's butterfly: every lane adds its partner's value
-                double n[64];
-                for (int l = 0; l < 64; ++l) n[l] = v[q][l] + v[q][l ^ m];
-                for (int l = 0; l < 64; ++l) v[q][l] = n[l];
-            }
-            tot[q] = w == 0 ? v[q][0] : tot[q] + v[q][0];
+            const double s = wave_butterfly(part[q]);
+            tot[q] = w == 0 ? s : tot[q] + s;
         }
     }
     energy_finish(a, mode, tot[0], tot[1], sse);
@@ -92,15 +91,6 @@ inline void launch_energy(const Args& a, int mode, const double* sse, plat_strea
 inline void launch_accept(const Args& a, int draw, const double* uniforms, uint64_t seed, unsigned ctr, double* samples, double* accept_prob, double* logp, plat_stream) {
     const unsigned key = rng_key((unsigned)seed, (unsigned)(seed >> 32), ctr);
     for (int i = a.P - 1; i >= 0; --i) accept_body(i, a, draw, uniforms, key, samples, accept_prob, logp);      // (element 0 last: it overwrites logp(current))
-}
-inline void launch_momentum_z(const Args& a, const double* z, uint64_t seed, unsigned draw, plat_stream) {
-    const unsigned key = rng_key((unsigned)seed, (unsigned)(seed >> 32), draw);
-    for (int i = 0; i < a.P; ++i) momentum_z_body(i, a, z, key);
-}
-template <class T> inline void launch_leap_dev(const Args& a, const T* ev, double kfac, int drift, plat_stream) {
-    HMC_NO_CONTRACT
-    const double eps = a.sc[SC_EPS];
-    for (int i = 0; i < a.P; ++i) leap_body<T>(i, a, ev, kfac * eps, eps, drift);
 }
 inline void launch_accept_adapt(const Args& a, int draw, const double* uniforms, uint64_t seed, unsigned ctr, double* samples, double* accept_prob, double* logp,
                                 double target, int flags, double* step_sizes, plat_stream) {
@@ -112,18 +102,25 @@ inline void launch_window_metric(const Args& a, const double* samples, int w0, i
     for (int i = 0; i < a.P; ++i) window_metric_body(i, a, const_cast<double*>(a.minv), samples, w0, w1);
 }
 #else
-__global__ void __launch_bounds__(BLOCK) k_hmc_momentum(const Args a, const double* row, unsigned seed_lo, unsigned seed_hi, unsigned draw) {
+__global__ void __launch_bounds__(BLOCK) k_hmc_momentum(const Args a, const double* z, const double* given, unsigned seed_lo, unsigned seed_hi, unsigned draw) {
     const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
-    if (i < a.P) momentum_body(i, a, row, rng_key(seed_lo, seed_hi, draw));
+    if (i < a.P) momentum_body(i, a, z, given, rng_key(seed_lo, seed_hi, draw));
 }
-template <class T> __global__ void __launch_bounds__(BLOCK) k_hmc_leap(const Args a, const T* ev, double kick, double eps, int drift) {
+// FROM_SC is a compile-time flag: the kernel of pinn_hmc_draws carries neither the load nor the branch
+template <class T, int FROM_SC> __global__ void __launch_bounds__(BLOCK) k_hmc_leap(const Args a, const T* ev, double kick, double eps, int drift) {
+    HMC_NO_CONTRACT
     const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
+    if (FROM_SC) {
+        eps = a.sc[SC_EPS];                              // (the same address in every lane)
+        kick = kick * eps;
+    }
     if (i < a.P) leap_body<T>(i, a, ev, kick, eps, drift);
 }
-__global__ void __launch_bounds__(BLOCK) k_hmc_energy(const Args a, int mode, const double* sse) {
+__global__ void __launch_bounds__(BLOCK) k_hmc_energy(const Args a, int mode, const double* sse, const double* v) {
     __shared__ double sh[2][BLOCK / 64];
     double kin, pri;
-    energy_partial((int)threadIdx.x, a, mode == 1, kin, pri);
+    if (v) energy_partial<true>((int)threadIdx.x, a, mode == 1, kin, pri, v);      // (the same v in every thread)
+    else energy_partial((int)threadIdx.x, a, mode == 1, kin, pri);
     for (int m = 32; m >= 1; m >>= 1) {
         kin += __shfl_xor(kin, m, 64);
         pri += __shfl_xor(pri, m, 64);
@@ -141,16 +138,6 @@ __global__ void __launch_bounds__(BLOCK) k_hmc_accept(const Args a, int draw, co
     const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
     if (i < a.P) accept_body(i, a, draw, uniforms, rng_key(seed_lo, seed_hi, ctr), samples, accept_prob, logp);
 }
-__global__ void __launch_bounds__(BLOCK) k_hmc_momentum_z(const Args a, const double* z, unsigned seed_lo, unsigned seed_hi, unsigned draw) {
-    const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
-    if (i < a.P) momentum_z_body(i, a, z, rng_key(seed_lo, seed_hi, draw));
-}
-template <class T> __global__ void __launch_bounds__(BLOCK) k_hmc_leap_dev(const Args a, const T* ev, double kfac, int drift) {
-    HMC_NO_CONTRACT
-    const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
-    const double eps = a.sc[SC_EPS];                     // (the same address in every lane)
-    if (i < a.P) leap_body<T>(i, a, ev, kfac * eps, eps, drift);
-}
 __global__ void __launch_bounds__(BLOCK) k_hmc_accept_adapt(const Args a, int draw, const double* uniforms, unsigned seed_lo, unsigned seed_hi, unsigned ctr,
                                                             double* samples, double* accept_prob, double* logp, double target, int flags, double* step_sizes) {
     const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
@@ -161,24 +148,20 @@ __global__ void __launch_bounds__(BLOCK) k_hmc_window_metric(const Args a, doubl
     const int i = (int)(blockIdx.x * BLOCK + threadIdx.x);
     if (i < a.P) window_metric_body(i, a, minv, samples, w0, w1);
 }
-inline void launch_momentum(const Args& a, const double* row, uint64_t seed, unsigned draw, plat_stream st) {
-    hipLaunchKernelGGL(k_hmc_momentum, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, row, (unsigned)seed, (unsigned)(seed >> 32), draw);
+inline void launch_momentum(const Args& a, const double* z, const double* given, uint64_t seed, unsigned draw, plat_stream st) {
+    hipLaunchKernelGGL(k_hmc_momentum, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, z, given, (unsigned)seed, (unsigned)(seed >> 32), draw);
 }
-template <class T> inline void launch_leap(const Args& a, const T* ev, double kick, double eps, int drift, plat_stream st) {
-    hipLaunchKernelGGL(k_hmc_leap<T>, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, ev, kick, eps, drift);
+template <class T> inline void launch_leap(const Args& a, const T* ev, double kick, double eps, int from_sc, int drift, plat_stream st) {
+    const dim3 grid((a.P + BLOCK - 1) / BLOCK);
+    if (from_sc) hipLaunchKernelGGL((k_hmc_leap<T, 1>), grid, dim3(BLOCK), 0, st, a, ev, kick, eps, drift);
+    else hipLaunchKernelGGL((k_hmc_leap<T, 0>), grid, dim3(BLOCK), 0, st, a, ev, kick, eps, drift);
 }
-inline void launch_energy(const Args& a, int mode, const double* sse, plat_stream st) {
-    hipLaunchKernelGGL(k_hmc_energy, dim3(1), dim3(BLOCK), 0, st, a, mode, sse);
+inline void launch_energy(const Args& a, int mode, const double* sse, const double* v, plat_stream st) {
+    hipLaunchKernelGGL(k_hmc_energy, dim3(1), dim3(BLOCK), 0, st, a, mode, sse, v);
 }
 inline void launch_accept(const Args& a, int draw, const double* uniforms, uint64_t seed, unsigned ctr, double* samples, double* accept_prob, double* logp, plat_stream st) {
     hipLaunchKernelGGL(k_hmc_accept, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, draw, uniforms, (unsigned)seed, (unsigned)(seed >> 32), ctr,
                        samples, accept_prob, logp);
-}
-inline void launch_momentum_z(const Args& a, const double* z, uint64_t seed, unsigned draw, plat_stream st) {
-    hipLaunchKernelGGL(k_hmc_momentum_z, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, z, (unsigned)seed, (unsigned)(seed >> 32), draw);
-}
-template <class T> inline void launch_leap_dev(const Args& a, const T* ev, double kfac, int drift, plat_stream st) {
-    hipLaunchKernelGGL(k_hmc_leap_dev<T>, dim3((a.P + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, a, ev, kfac, drift);
 }
 inline void launch_accept_adapt(const Args& a, int draw, const double* uniforms, uint64_t seed, unsigned ctr, double* samples, double* accept_prob, double* logp,
                                 double target, int flags, double* step_sizes, plat_stream st) {

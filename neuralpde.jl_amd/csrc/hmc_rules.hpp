@@ -1,6 +1,7 @@
 // hmc_rules.hpp — the bodies of the resident HMC transition, written once: hmc_kernels.hpp launches them one kernel per
-// phase (pinn_hmc_*), hmc_chain_kernels.hpp runs them inside one workgroup per chain (pinn_hmc_chains_*; section 4.15).  The generator, the
-// priors, the update, energy and accept bodies and their argument block; see hmc_kernels.hpp for what each restates.
+// phase (pinn_hmc_*), hmc_dense_kernels.hpp forms the same gradient and energy under a dense metric (section 4.16), hmc_chain_kernels.hpp runs
+// them inside one workgroup per chain (pinn_hmc_chains_*; section 4.15).  The generator, the priors, the momentum, gradient, update, energy and
+// accept bodies, their argument block and the emulation's wave butterfly; see hmc_kernels.hpp for what each restates.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -72,12 +73,26 @@ HMC_DEV void prior_logpdf_grad(const Args& a, int j, double x, double& l, double
     }
 }
 
-HMC_DEV void momentum_body(int i, const Args& a, const double* row, unsigned key) {
-    a.r[i] = row ? row[i] : rng_normal(key, (unsigned)i) / sqrt(a.minv[i]);
+// `given`: row i of the caller's finished momenta; else z (the caller's standard normals, or the generator) under the metric in force
+HMC_DEV void momentum_body(int i, const Args& a, const double* z, const double* given, unsigned key) {
+    a.r[i] = given ? given[i] : (z ? z[i] : rng_normal(key, (unsigned)i)) / sqrt(a.minv[i]);
 }
 
-// ev == nullptr: the first half kick of a trajectory, from the stored gradient at the current state; otherwise ev = the evaluation's
-// [gradient of sum_k w_k L_k | ...] at th_prop, whose sign-flipped value is d loglik / d theta
+// element i of the gradient of logp at x: ev = the evaluation's [gradient of sum_k w_k L_k | ...] there, whose sign-flipped value is
+// d loglik / d theta; then the weight prior's or the parameter prior's part
+template <class T> HMC_DEV double logp_grad(int i, const Args& a, const T* ev, double x) {
+    HMC_NO_CONTRACT
+    double g = -(double)ev[i];
+    if (i < a.nn) g -= (x - a.nn_mu) / a.nn_var;
+    else {
+        double l, d;
+        prior_logpdf_grad(a, i - a.nn, x, l, d);
+        g += d;
+    }
+    return g;
+}
+
+// ev == nullptr: the first half kick of a trajectory, from the stored gradient at the current state; otherwise ev = the evaluation at th_prop
 template <class T> HMC_DEV void leap_body(int i, const Args& a, const T* ev, double kick, double eps, int drift) {
     HMC_NO_CONTRACT
     double g, x;
@@ -86,13 +101,7 @@ template <class T> HMC_DEV void leap_body(int i, const Args& a, const T* ev, dou
         x = a.th_cur[i];
     } else {
         x = a.th_prop[i];
-        g = -(double)ev[i];
-        if (i < a.nn) g -= (x - a.nn_mu) / a.nn_var;
-        else {
-            double l, d;
-            prior_logpdf_grad(a, i - a.nn, x, l, d);
-            g += d;
-        }
+        g = logp_grad<T>(i, a, ev, x);
         a.g_prop[i] = g;
     }
     const double r = a.r[i] + kick * g;
@@ -105,13 +114,16 @@ template <class T> HMC_DEV void leap_body(int i, const Args& a, const T* ev, dou
     }
 }
 
-// thread t of BLOCK: its part of sum minv r^2 and (with_prior) of sum ((w - mu) / sigma)^2 over the network weights of the proposal
-HMC_DEV void energy_partial(int t, const Args& a, int with_prior, double& kin, double& pri) {
+// thread t of BLOCK: its part of sum minv r^2 (DENSE: of sum r v, v = M^-1 r under a dense metric) and (with_prior) of sum ((w - mu) / sigma)^2
+// over the network weights of the proposal.  The choice is made outside the loop, at compile time: a caller without v — the chain kernel —
+// compiles to the diagonal loop alone
+template <bool DENSE = false> HMC_DEV void energy_partial(int t, const Args& a, int with_prior, double& kin, double& pri, const double* v = nullptr) {
     HMC_NO_CONTRACT
     kin = 0.0; pri = 0.0;
     for (int i = t; i < a.P; i += BLOCK) {
         const double r = a.r[i];
-        kin += a.minv[i] * r * r;
+        if constexpr (DENSE) kin += r * v[i];
+        else kin += a.minv[i] * r * r;
         if (with_prior && i < a.nn) {
             const double z = (a.th_prop[i] - a.nn_mu) / a.nn_sigma;
             pri += z * z;
@@ -146,6 +158,18 @@ HMC_DEV void energy_finish(const Args& a, int mode, double kin, double pri, cons
     a.sc[SC_LP_PROP] = lp;
     a.sc[SC_H_NEW] = -lp + 0.5 * kin;
 }
+
+#ifdef PINN_EMU
+// the device's 64-lane xor butterfly (32, 16, ... 1), restated: every lane adds its partner's value; lane 0's sum
+inline double wave_butterfly(double* v) {
+    for (int m = 32; m >= 1; m >>= 1) {
+        double n[64];
+        for (int l = 0; l < 64; ++l) n[l] = v[l] + v[l ^ m];
+        for (int l = 0; l < 64; ++l) v[l] = n[l];
+    }
+    return v[0];
+}
+#endif
 
 HMC_DEV void accept_body(int i, const Args& a, int draw, const double* uniforms, unsigned key, double* samples, double* accept_prob, double* logp) {
     const double h_old = a.sc[SC_H_OLD], h_new = a.sc[SC_H_NEW];

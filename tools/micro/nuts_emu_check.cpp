@@ -48,7 +48,7 @@ template <class T> static int run(int P, int D, int ndraws, double eps, bool sup
     for (int i = 0; i < P; ++i) { a.th_cur[i] = a.th_prop[i] = 0.3 + 0.1 * ((i % 5) - 2); th[i] = (T)a.th_cur[i]; minv[i] = 0.5 + ((i * 3) % 7) / 7.0; }
     evaluate();
     for (int i = 0; i < P; ++i) hmc::leap_body<T>(i, a, ev.data(), 0.0, 0.0, 0);
-    hmc::launch_energy(a, 1, sse.data(), nullptr);
+    hmc::launch_energy(a, 1, sse.data(), nullptr, nullptr);
     for (int i = 0; i < P; ++i) a.g_cur[i] = a.g_prop[i];
     a.sc[hmc::SC_LP_CUR] = a.sc[hmc::SC_LP_PROP];
 
