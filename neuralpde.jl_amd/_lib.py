@@ -218,6 +218,18 @@ def _f64(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
+def _prior_args(param_priors):
+    """the (count, kinds, mu, sigma) arguments of `pinn_hmc_init` / `pinn_hmc_chains_init`: one (kind, mu, sigma) per trailing PDE parameter, kind
+    0 / "normal" or 1 / "lognormal"; null pointers when there is none"""
+    kinds = {"normal": 0, "lognormal": 1}
+    kd = np.ascontiguousarray([kinds.get(str(q[0]).lower(), q[0]) for q in param_priors], dtype=np.int32)
+    mu, sg = _f64([q[1] for q in param_priors]), _f64([q[2] for q in param_priors])
+    if not kd.size:
+        return 0, None, None, None
+    dp = C.POINTER(C.c_double)
+    return kd.size, kd.ctypes.data_as(C.POINTER(C.c_int)), mu.ctypes.data_as(dp), sg.ctypes.data_as(dp)      # (each pointer keeps its array alive)
+
+
 COMM_ID_BYTES = 128
 
 
@@ -712,13 +724,9 @@ class Engine:
         """`pinn_hmc_init`: put a chain at theta.  stds: one per loss term; nn_prior = (mu, sigma) of the Normal prior on the network weights;
         param_priors: one (kind, mu, sigma) per trailing PDE parameter, kind 0 / "normal" or 1 / "lognormal"."""
         th, sd = _f64(theta), _f64(stds).reshape(-1)
-        kinds = {"normal": 0, "lognormal": 1}
-        kd = np.ascontiguousarray([kinds.get(str(q[0]).lower(), q[0]) for q in param_priors], dtype=np.int32)
-        mu, sg = _f64([q[1] for q in param_priors]), _f64([q[2] for q in param_priors])
         dp = C.POINTER(C.c_double)
         self.L.check(self.L.lib.pinn_hmc_init(self.h, th.ctypes.data_as(dp), th.size, sd.ctypes.data_as(dp), sd.size, float(nn_prior[0]), float(nn_prior[1]),
-                                              kd.size, kd.ctypes.data_as(C.POINTER(C.c_int)) if kd.size else None,
-                                              mu.ctypes.data_as(dp) if kd.size else None, sg.ctypes.data_as(dp) if kd.size else None), "pinn_hmc_init")
+                                              *_prior_args(param_priors)), "pinn_hmc_init")
 
     def hmc_set_metric(self, inv_metric=None):
         """`pinn_hmc_set_metric`: the diagonal inverse mass matrix (None: ones)"""
@@ -772,17 +780,12 @@ class Engine:
         th, sd = np.ascontiguousarray(np.atleast_2d(_f64(theta))), _f64(stds).reshape(-1)
         if th.ndim != 2 or th.shape[1] != self.P:
             raise ValueError("theta: nchains x P values")
-        kinds = {"normal": 0, "lognormal": 1}
-        kd = np.ascontiguousarray([kinds.get(str(q[0]).lower(), q[0]) for q in param_priors], dtype=np.int32)
-        mu, sg = _f64([q[1] for q in param_priors]), _f64([q[2] for q in param_priors])
         m = None if inv_metric is None else _f64(inv_metric).reshape(-1)
         if m is not None and m.size != self.P:
             raise ValueError("inv_metric: P values")
         dp = C.POINTER(C.c_double)
         self.L.check(self.L.lib.pinn_hmc_chains_init(self.h, th.shape[0], th.ctypes.data_as(dp), self.P, float(eps), m.ctypes.data_as(dp) if m is not None else None,
-                                                     sd.ctypes.data_as(dp), sd.size, float(nn_prior[0]), float(nn_prior[1]),
-                                                     kd.size, kd.ctypes.data_as(C.POINTER(C.c_int)) if kd.size else None,
-                                                     mu.ctypes.data_as(dp) if kd.size else None, sg.ctypes.data_as(dp) if kd.size else None,
+                                                     sd.ctypes.data_as(dp), sd.size, float(nn_prior[0]), float(nn_prior[1]), *_prior_args(param_priors),
                                                      int(n_leapfrog), int(seed) & 0xFFFFFFFFFFFFFFFF), "pinn_hmc_chains_init")
         self._nchains = th.shape[0]
 

@@ -15,7 +15,9 @@ uses forward-mode ForwardDiff over every parameter of the network).  By default 
 host as in the reference (`sampler="host"`: one device evaluation and one host round trip per leapfrog step).  `sampler="device"` runs the
 transitions on the device (`pinn_hmc_*`): theta, momentum, metric, gradient and energies stay resident, a call
 makes many draws and downloads once; the step-size search, dual averaging and the windowed metric stay here in Python unless
-`adaptation="device"` runs the whole warm-up in ONE resident call (`pinn_hmc_warmup`).
+`adaptation="device"` runs the whole warm-up in ONE resident call (`pinn_hmc_warmup`).  Every sampler here shares
+one copy of each: `_find_stepsize` is the search, `_adapt_and_draw` the dual-averaging recurrence, the window and the chunked draws around a
+sampler's `transition`, `_DiagMetric` / `_DenseMetric` (`_dense_window_metric`) the metric's arithmetic and its window rule.
 `kernel="nuts"` replaces the fixed-length trajectory by No-U-Turn transitions (`_nuts_transition`, the specification; on the device
 `pinn_nuts_draws`).
 """
@@ -75,88 +77,168 @@ def _dense_window_metric(win):
         return None
 
 
-def _hmc(logp_grad, theta0, draw_samples, n_leapfrog, eps0, target, rng, n_adapts=None, metric="diag"):
-    """HMC with `n_leapfrog` leapfrog steps per draw ([3P] AdvancedHMC.HMC(eps, n_leapfrog)), Stan-style adaptation during the first
-    n_adapts = min(draw_samples / 10, 1000) draws (AdvancedHMC's default): dual averaging of the step size towards `target` acceptance
-    and a diagonal metric from the windowed sample variance (StanHMCAdaptor + DiagEuclideanMetric).  metric="dense": a full inverse metric
-    M^-1 = L L^T from the windowed covariance (DenseEuclideanMetric): r = L^-T z, theta += eps M^-1 r, kinetic energy 1/2 r.(M^-1 r)."""
-    n = theta0.size
-    n_adapts = min(draw_samples // 10, 1000) if n_adapts is None else n_adapts
-    th = theta0.astype(np.float64).copy()
-    lp, g = logp_grad(th)
-    minv = np.ones(n)                                # inverse mass (diagonal metric)
-    dense = metric == "dense"
-    if dense:
-        minv, chol = np.eye(n), np.eye(n)
-    momentum = (lambda z: np.linalg.solve(chol.T, z)) if dense else (lambda z: z / np.sqrt(minv))
-    kinetic = (lambda r: 0.5 * (r @ (minv @ r))) if dense else (lambda r: 0.5 * np.sum(minv * r * r))
+class _DiagMetric:
+    """diagonal Euclidean metric (DiagEuclideanMetric), `minv` the inverse mass vector: what a trajectory needs of a metric — the momentum of
+    standard normals z, the position step M^-1 r, the kinetic energy — and the metric an adaptation window gives"""
 
-    def leap(th, r, g, eps, steps):
-        r = r + 0.5 * eps * g
-        for s in range(steps):
-            th = th + eps * (minv @ r if dense else minv * r)
-            lp, g = logp_grad(th)
-            r = r + (eps if s < steps - 1 else 0.5 * eps) * g
-        return th, r, lp, g
+    def __init__(self, minv):
+        self.minv = minv
 
-    # find_good_stepsize: double / halve until the one-step acceptance crosses 0.8 (AdvancedHMC.find_good_stepsize)
-    eps = eps0
-    r0 = momentum(rng.standard_normal(n))
-    h0 = -lp + kinetic(r0)
-    t1, r1, lp1, _ = leap(th, r0, g, eps, 1)
-    d = h0 - (-lp1 + kinetic(r1))
+    def momentum(self, z):
+        return z / np.sqrt(self.minv)
+
+    def velocity(self, r):
+        return self.minv * r
+
+    def kinetic(self, r):
+        return 0.5 * np.sum(self.minv * r * r)
+
+    def from_window(self, win):
+        """the windowed variance rule: (k/(k+5)) var + 1e-3 (5/(k+5)) over the k window rows"""
+        var = np.var(np.asarray(win), axis=0)
+        k = len(win)
+        return _DiagMetric((k / (k + 5.0)) * var + 1e-3 * (5.0 / (k + 5.0)))
+
+
+class _DenseMetric:
+    """dense Euclidean metric (DenseEuclideanMetric), M^-1 = `minv` = L L^T with L = `chol`: r = L^-T z, theta += eps M^-1 r, kinetic energy
+    1/2 r.(M^-1 r)"""
+
+    def __init__(self, minv, chol):
+        self.minv, self.chol = minv, chol
+
+    def momentum(self, z):
+        return np.linalg.solve(self.chol.T, z)
+
+    def velocity(self, r):
+        return self.minv @ r
+
+    def kinetic(self, r):
+        return 0.5 * (r @ (self.minv @ r))
+
+    def from_window(self, win):
+        """`_dense_window_metric`, or None (the metric in force stays)"""
+        new = _dense_window_metric(win)
+        return None if new is None else _DenseMetric(*new)
+
+
+def _find_stepsize(logp_grad, th, lp, g, metric, eps, z):
+    """the initial step-size search of every sampler here (AdvancedHMC.find_good_stepsize) from (th, lp, g), with the momentum `metric` makes of
+    the standard normals z: double or halve eps until the acceptance of ONE leapfrog step crosses 0.8, at most 40 trials after the first"""
+    r0 = metric.momentum(z)
+
+    def one_step(e):
+        r = r0 + 0.5 * e * g
+        lp1, g1 = logp_grad(th + e * metric.velocity(r))
+        r = r + 0.5 * e * g1
+        return -lp1 + metric.kinetic(r)
+
+    h0 = -lp + metric.kinetic(r0)
+    d = h0 - one_step(eps)
     direction = 1.0 if (np.isfinite(d) and d > np.log(0.8)) else -1.0
     for _ in range(40):
         eps *= 2.0 ** direction
-        t1, r1, lp1, _ = leap(th, r0, g, eps, 1)
-        d = h0 - (-lp1 + kinetic(r1))
+        d = h0 - one_step(eps)
         if not np.isfinite(d):
             d = -np.inf
         if (direction > 0) == (d <= np.log(0.8)):
             break
+    return eps
+
+
+def _chunks(n, chunk=256):
+    """the sizes of the calls that make n draws after the adaptation: `chunk` draws each, the last one the rest"""
+    while n > 0:
+        nd = min(int(chunk), n)
+        yield nd
+        n -= nd
+
+
+def _adapt_and_draw(transition, metric, eps, target, draw_samples, n_adapts, set_metric=None, chunk=256):
+    """The warm-up and the draws of every sampler here, from the step size of `_find_stepsize`.  transition(n, eps, metric) runs n draws of the
+    chain and returns one row (th, acceptance, ...) per draw, th the chain's state after accept/reject.  The first n_adapts draws, one per call,
+    adapt Stan-style (StanHMCAdaptor): dual averaging of the step size towards `target` acceptance after every draw and, at the end of the window
+    [0.15 n_adapts, 0.9 n_adapts), a metric from the window's rows (`metric.from_window`), which set_metric(minv) tells the device about; the dual
+    averaging restarts on it, and the last adaptation draw fixes the step size at the averaged one.  The remaining draws come in calls of `chunk`.
+    -> rows, step size, metric."""
     mu, hbar, log_eps_bar, t0, gamma, kappa = np.log(10 * eps), 0.0, 0.0, 10.0, 0.05, 0.75
     w0, w1 = int(0.15 * n_adapts), int(0.9 * n_adapts)            # variance window of the metric adaptation
-    win = []
-    samples, accs = [], []
+    win, rows = [], []
     m_count = 0
-    for it in range(draw_samples):
-        r = momentum(rng.standard_normal(n))
-        h_old = -lp + kinetic(r)
-        tn, rn, lpn, gn = leap(th, r, g, eps, n_leapfrog)
-        h_new = -lpn + kinetic(rn)
-        a = float(np.exp(min(0.0, h_old - h_new))) if np.isfinite(h_new) else 0.0
-        if rng.random() < a:
-            th, lp, g = tn, lpn, gn
-        samples.append(th.copy())
-        accs.append(a)
-        if it < n_adapts:
-            m_count += 1
-            hbar = (1 - 1 / (m_count + t0)) * hbar + (target - a) / (m_count + t0)
-            log_eps = mu - np.sqrt(m_count) / gamma * hbar
-            eta = m_count ** (-kappa)
-            log_eps_bar = eta * log_eps + (1 - eta) * log_eps_bar
-            eps = float(np.exp(log_eps))
-            if w0 <= it < w1:
-                win.append(th.copy())
-            if it == w1 - 1 and len(win) >= 8 and n_adapts >= 100:       # (a metric from fewer draws is noise; short runs keep the unit metric)
-                if dense:
-                    new = _dense_window_metric(win)
-                    minv, chol = new if new is not None else (minv, chol)
-                else:
-                    var = np.var(np.asarray(win), axis=0)
-                    k = len(win)
-                    minv = (k / (k + 5.0)) * var + 1e-3 * (5.0 / (k + 5.0))
-                mu, hbar, log_eps_bar, m_count = np.log(10 * eps), 0.0, 0.0, 0          # restart the step-size search on the new metric
-            if it == n_adapts - 1:
-                eps = float(np.exp(log_eps_bar)) if m_count > 0 else eps
-    return np.asarray(samples), {"acceptance": np.asarray(accs), "step_size": eps, "inv_metric": minv, "n_adapts": n_adapts}
+    for it in range(min(n_adapts, draw_samples)):
+        row = transition(1, eps, metric)[0]
+        rows.append(row)
+        a = float(row[1])
+        m_count += 1
+        hbar = (1 - 1 / (m_count + t0)) * hbar + (target - a) / (m_count + t0)
+        log_eps = mu - np.sqrt(m_count) / gamma * hbar
+        eta = m_count ** (-kappa)
+        log_eps_bar = eta * log_eps + (1 - eta) * log_eps_bar
+        eps = float(np.exp(log_eps))
+        if w0 <= it < w1:
+            win.append(row[0])
+        if it == w1 - 1 and len(win) >= 8 and n_adapts >= 100:       # (a metric from fewer draws is noise; short runs keep the unit metric)
+            new = metric.from_window(win)
+            if new is not None:
+                metric = new
+                if set_metric is not None:
+                    set_metric(metric.minv)
+            mu, hbar, log_eps_bar, m_count = np.log(10 * eps), 0.0, 0.0, 0          # restart the step-size search on the new metric
+        if it == n_adapts - 1:
+            eps = float(np.exp(log_eps_bar)) if m_count > 0 else eps
+    for nd in _chunks(draw_samples - len(rows), chunk):
+        rows.extend(transition(nd, eps, metric))
+    return rows, eps, metric
+
+
+def _stats(rows, eps, minv, n_adapts):
+    """-> samples, stats: the columns every sampler has"""
+    col = lambda j: np.asarray([r[j] for r in rows], dtype=np.float64)
+    return col(0), {"acceptance": col(1), "step_size": eps, "inv_metric": minv, "n_adapts": n_adapts}
+
+
+def _hmc(logp_grad, theta0, draw_samples, n_leapfrog, eps0, target, rng, n_adapts=None, metric="diag"):
+    """HMC with `n_leapfrog` leapfrog steps per draw ([3P] AdvancedHMC.HMC(eps, n_leapfrog)), Stan-style adaptation during the first
+    n_adapts = min(draw_samples / 10, 1000) draws (AdvancedHMC's default, `_adapt_and_draw`): dual averaging of the step size towards `target`
+    acceptance and a diagonal metric from the windowed sample variance (StanHMCAdaptor + DiagEuclideanMetric).  metric="dense": a full inverse
+    metric M^-1 = L L^T from the windowed covariance (`_DenseMetric`)."""
+    n = theta0.size
+    n_adapts = min(draw_samples // 10, 1000) if n_adapts is None else n_adapts
+    th = theta0.astype(np.float64).copy()
+    lp, g = logp_grad(th)
+    met = _DenseMetric(np.eye(n), np.eye(n)) if metric == "dense" else _DiagMetric(np.ones(n))
+    eps = _find_stepsize(logp_grad, th, lp, g, met, eps0, rng.standard_normal(n))
+
+    def leap(th, r, g, eps, steps, met):
+        r = r + 0.5 * eps * g
+        for s in range(steps):
+            th = th + eps * met.velocity(r)
+            lp, g = logp_grad(th)
+            r = r + (eps if s < steps - 1 else 0.5 * eps) * g
+        return th, r, lp, g
+
+    def transition(nd, eps, met):
+        nonlocal th, lp, g
+        out = []
+        for _ in range(nd):
+            r = met.momentum(rng.standard_normal(n))
+            h_old = -lp + met.kinetic(r)
+            tn, rn, lpn, gn = leap(th, r, g, eps, n_leapfrog, met)
+            h_new = -lpn + met.kinetic(rn)
+            a = float(np.exp(min(0.0, h_old - h_new))) if np.isfinite(h_new) else 0.0
+            if rng.random() < a:
+                th, lp, g = tn, lpn, gn
+            out.append((th.copy(), a))
+        return out
+    rows, eps, met = _adapt_and_draw(transition, met, eps, target, draw_samples, n_adapts)
+    return _stats(rows, eps, met.minv, n_adapts)
 
 
 def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, eps0, target, rng, seed, n_adapts=None, chunk=256, adaptation="host",
                 metric="diag"):
-    """`_hmc` with the transitions on the device (Engine.hmc_*): the same initial step-size search on the host evaluation path (at most 42
-    evaluations), the same dual averaging and windowed metric in Python around `hmc_draws(1, ...)` during adaptation (a new metric goes down
-    through `hmc_set_metric`), then the remaining draws in chunks of `chunk`.  Momenta and uniforms come from the device generator (`seed`).
+    """`_hmc` with the transitions on the device (Engine.hmc_*): the same initial step-size search on the host evaluation path (`_find_stepsize`,
+    at most 42 evaluations), the same dual averaging and windowed metric (`_adapt_and_draw`) around `hmc_draws(1, ...)` during adaptation (a new
+    metric goes down through `hmc_set_metric`), then the remaining draws in chunks of `chunk`.  Momenta and uniforms come from the device generator (`seed`).
     adaptation="device": the adaptation draws are ONE `hmc_warmup` call — the same recurrence and window on the device — after the same host
     search, so both settings start from the same step size.  metric="dense": the chain starts under the dense identity
     (`hmc_set_metric_dense`); the host adaptation sends the windowed covariance down through it, the device adaptation forms and factorises it
@@ -165,81 +247,29 @@ def _hmc_device(eng, logp_grad, theta0, init_chain, draw_samples, n_leapfrog, ep
     n_adapts = min(draw_samples // 10, 1000) if n_adapts is None else n_adapts
     th = theta0.astype(np.float64).copy()
     lp, g = logp_grad(th)
-    minv = np.ones(n)
+    met = _DiagMetric(np.ones(n))
     dense = metric == "dense"
-
-    def one_step(r, eps):
-        r = r + 0.5 * eps * g
-        t1 = th + eps * minv * r
-        lp1, g1 = logp_grad(t1)
-        r = r + 0.5 * eps * g1
-        return -lp1 + 0.5 * np.sum(minv * r * r)
-
-    eps = eps0
-    r0 = rng.standard_normal(n) / np.sqrt(minv)
-    h0 = -lp + 0.5 * np.sum(minv * r0 * r0)
-    d = h0 - one_step(r0, eps)
-    direction = 1.0 if (np.isfinite(d) and d > np.log(0.8)) else -1.0
-    for _ in range(40):
-        eps *= 2.0 ** direction
-        d = h0 - one_step(r0, eps)
-        if not np.isfinite(d):
-            d = -np.inf
-        if (direction > 0) == (d <= np.log(0.8)):
-            break
+    eps = _find_stepsize(logp_grad, th, lp, g, met, eps0, rng.standard_normal(n))
     init_chain(th)
     if dense:                                        # (the search above ran under the unit metric, which the dense identity is)
         eng.hmc_set_metric_dense(None)
-        minv = np.eye(n)
-    mu, hbar, log_eps_bar, t0, gamma, kappa = np.log(10 * eps), 0.0, 0.0, 10.0, 0.05, 0.75
-    w0, w1 = int(0.15 * n_adapts), int(0.9 * n_adapts)
-    win, samples, accs = [], [], []
-    m_count = 0
-    host_adapts = min(n_adapts, draw_samples)
-    if adaptation == "device" and host_adapts >= 1:
+        met = _DenseMetric(np.eye(n), np.eye(n))
+
+    def transition(nd, eps, met):
+        smp, acc, _ = eng.hmc_draws(nd, n_leapfrog, eps, seed)
+        return list(zip(smp, acc))
+    if adaptation == "device" and min(n_adapts, draw_samples) >= 1:
         if n_adapts > draw_samples:
             raise ValueError("adaptation=\"device\": the warm-up is one call of n_adapts draws; draw_samples must be at least n_adapts")
         smp, acc, _, _, eps, minv = eng.hmc_warmup(n_adapts, n_leapfrog, eps, target, seed)
         if dense:
             minv = eng.hmc_get_metric_dense()[0]
-        samples.extend(smp)
-        accs.extend(acc)
-        host_adapts = 0
-    for it in range(host_adapts):
-        smp, acc, _ = eng.hmc_draws(1, n_leapfrog, eps, seed)
-        th, a = smp[0], float(acc[0])
-        samples.append(th)
-        accs.append(a)
-        m_count += 1
-        hbar = (1 - 1 / (m_count + t0)) * hbar + (target - a) / (m_count + t0)
-        log_eps = mu - np.sqrt(m_count) / gamma * hbar
-        eta = m_count ** (-kappa)
-        log_eps_bar = eta * log_eps + (1 - eta) * log_eps_bar
-        eps = float(np.exp(log_eps))
-        if w0 <= it < w1:
-            win.append(th)
-        if it == w1 - 1 and len(win) >= 8 and n_adapts >= 100:
-            if dense:
-                new = _dense_window_metric(win)
-                if new is not None:
-                    minv = new[0]
-                    eng.hmc_set_metric_dense(minv)
-            else:
-                var = np.var(np.asarray(win), axis=0)
-                k = len(win)
-                minv = (k / (k + 5.0)) * var + 1e-3 * (5.0 / (k + 5.0))
-                eng.hmc_set_metric(minv)
-            mu, hbar, log_eps_bar, m_count = np.log(10 * eps), 0.0, 0.0, 0
-        if it == n_adapts - 1:
-            eps = float(np.exp(log_eps_bar)) if m_count > 0 else eps
-    done = len(samples)
-    while done < draw_samples:
-        nd = min(int(chunk), draw_samples - done)
-        smp, acc, _ = eng.hmc_draws(nd, n_leapfrog, eps, seed)
-        samples.extend(smp)
-        accs.extend(acc)
-        done += nd
-    return np.asarray(samples), {"acceptance": np.asarray(accs), "step_size": eps, "inv_metric": minv, "n_adapts": n_adapts}
+        rows = list(zip(smp, acc))
+        for nd in _chunks(draw_samples - n_adapts, chunk):
+            rows.extend(transition(nd, eps, None))
+        return _stats(rows, eps, minv, n_adapts)
+    rows, eps, met = _adapt_and_draw(transition, met, eps, target, draw_samples, n_adapts, eng.hmc_set_metric_dense if dense else eng.hmc_set_metric, chunk)
+    return _stats(rows, eps, met.minv, n_adapts)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -361,86 +391,39 @@ def _nuts_transition(logp_grad, state, minv, eps, z, u, max_depth, delta_max=100
     return prop, {"tree_depth": depth, "n_leapfrog": n_leaf, "accept_stat": sum_acc / n_leaf, "divergent": divergent}
 
 
-def _find_stepsize(logp_grad, th, lp, g, minv, eps, r0):
-    """the initial step-size search of `_hmc` (AdvancedHMC.find_good_stepsize) from (th, lp, g) with the momentum r0"""
-    def one_step(e):
-        r = r0 + 0.5 * e * g
-        lp1, g1 = logp_grad(th + e * minv * r)
-        r = r + 0.5 * e * g1
-        return -lp1 + 0.5 * np.sum(minv * r * r)
-
-    h0 = -lp + 0.5 * np.sum(minv * r0 * r0)
-    d = h0 - one_step(eps)
-    direction = 1.0 if (np.isfinite(d) and d > np.log(0.8)) else -1.0
-    for _ in range(40):
-        eps *= 2.0 ** direction
-        d = h0 - one_step(eps)
-        if not np.isfinite(d):
-            d = -np.inf
-        if (direction > 0) == (d <= np.log(0.8)):
-            break
-    return eps
-
-
 def _nuts(logp_grad, theta0, draw_samples, max_depth, eps0, target, rng, n_adapts=None, transition=None, set_metric=None, init_chain=None, chunk=256):
     """NUTS ([3P] AdvancedHMC.NUTS(delta)) with `_hmc`'s step-size search, dual averaging — on the tree's accept_stat — and windowed diagonal
-    metric during the first n_adapts draws.  transition(n, eps, minv) -> lists of per-draw (th, accept_stat, tree_depth, n_leapfrog,
-    divergent) runs n draws of the chain: by default `_nuts_transition` on the host with z and u from `rng`; `_nuts_device` passes the
-    resident one (and set_metric / init_chain, which tell the device about a new metric / the start)."""
+    metric during the first n_adapts draws (`_find_stepsize`, `_adapt_and_draw`).  transition(n, eps, metric) -> lists of per-draw (th,
+    accept_stat, tree_depth, n_leapfrog, divergent) runs n draws of the chain: by default `_nuts_transition` on the host with z and u from
+    `rng`; `_nuts_device` passes the resident one (and set_metric / init_chain, which tell the device about a new metric / the start)."""
     n = theta0.size
     n_adapts = min(draw_samples // 10, 1000) if n_adapts is None else n_adapts
     th = theta0.astype(np.float64).copy()
     lp, g = logp_grad(th)
-    minv = np.ones(n)
-    eps = _find_stepsize(logp_grad, th, lp, g, minv, eps0, rng.standard_normal(n) / np.sqrt(minv))
+    met = _DiagMetric(np.ones(n))
+    eps = _find_stepsize(logp_grad, th, lp, g, met, eps0, rng.standard_normal(n))
     if init_chain is not None:
         init_chain(th)
     host_state = [(th, lp, g)]
 
-    def host_transition(nd, eps, minv):
+    def host_transition(nd, eps, met):
         out = []
         for _ in range(nd):
             z, u = rng.standard_normal(n), rng.random(nuts_uniforms(max_depth))
-            host_state[0], st = _nuts_transition(logp_grad, host_state[0], minv, eps, z, u, max_depth)
+            host_state[0], st = _nuts_transition(logp_grad, host_state[0], met.minv, eps, z, u, max_depth)
             out.append((host_state[0][0].copy(), st["accept_stat"], st["tree_depth"], st["n_leapfrog"], st["divergent"]))
         return out
-    transition = host_transition if transition is None else transition
-    mu, hbar, log_eps_bar, t0, gamma, kappa = np.log(10 * eps), 0.0, 0.0, 10.0, 0.05, 0.75
-    w0, w1 = int(0.15 * n_adapts), int(0.9 * n_adapts)
-    win, rows = [], []
-    m_count = 0
-    for it in range(min(n_adapts, draw_samples)):
-        row = transition(1, eps, minv)[0]
-        rows.append(row)
-        a = float(row[1])
-        m_count += 1
-        hbar = (1 - 1 / (m_count + t0)) * hbar + (target - a) / (m_count + t0)
-        log_eps = mu - np.sqrt(m_count) / gamma * hbar
-        eta = m_count ** (-kappa)
-        log_eps_bar = eta * log_eps + (1 - eta) * log_eps_bar
-        eps = float(np.exp(log_eps))
-        if w0 <= it < w1:
-            win.append(row[0])
-        if it == w1 - 1 and len(win) >= 8 and n_adapts >= 100:
-            var = np.var(np.asarray(win), axis=0)
-            k = len(win)
-            minv = (k / (k + 5.0)) * var + 1e-3 * (5.0 / (k + 5.0))
-            if set_metric is not None:
-                set_metric(minv)
-            mu, hbar, log_eps_bar, m_count = np.log(10 * eps), 0.0, 0.0, 0
-        if it == n_adapts - 1:
-            eps = float(np.exp(log_eps_bar)) if m_count > 0 else eps
-    while len(rows) < draw_samples:
-        rows.extend(transition(min(int(chunk), draw_samples - len(rows)), eps, minv))
-    col = lambda j, dt: np.asarray([r[j] for r in rows], dtype=dt)
-    return col(0, np.float64), {"acceptance": col(1, np.float64), "step_size": eps, "inv_metric": minv, "n_adapts": n_adapts,
-                                "tree_depth": col(2, np.int64), "n_leapfrog": col(3, np.int64), "divergent": col(4, np.int64)}
+    rows, eps, met = _adapt_and_draw(host_transition if transition is None else transition, met, eps, target, draw_samples, n_adapts, set_metric, chunk)
+    samples, stats = _stats(rows, eps, met.minv, n_adapts)
+    for j, key in ((2, "tree_depth"), (3, "n_leapfrog"), (4, "divergent")):
+        stats[key] = np.asarray([r[j] for r in rows], dtype=np.int64)
+    return samples, stats
 
 
 def _nuts_device(eng, logp_grad, theta0, init_chain, draw_samples, max_depth, eps0, target, rng, seed, n_adapts=None, chunk=256):
     """`_nuts` with the transitions on the device (Engine.nuts_draws): `_hmc_device`'s structure — `nuts_draws(1, ...)` during adaptation (a
     new metric goes down through `hmc_set_metric`), then chunks of `chunk`; normals and uniforms from the device generator (`seed`)."""
-    def transition(nd, eps, minv):
+    def transition(nd, eps, met):
         smp, acc, _, depth, nleap, div = eng.nuts_draws(nd, max_depth, eps, seed)
         return [(smp[i], float(acc[i]), int(depth[i]), int(nleap[i]), int(div[i])) for i in range(nd)]
     return _nuts(logp_grad, theta0, draw_samples, max_depth, eps0, target, rng, n_adapts, transition, eng.hmc_set_metric, init_chain, chunk)
@@ -596,11 +579,10 @@ def ahmc_bayesian_pinn_pde(npde, pde_system, discretization, draw_samples=1000, 
             starts = np.tile(eng.hmc_get(want_grad=False)[0] if n_adapts else theta0, (nchains, 1))
             starts[1:, :nn] = mu0 + sd0 * rng.standard_normal((nchains - 1, nn))
             eng.hmc_chains_init(starts, stats["step_size"], stds, (mu0, sd0), kinds, int(n_leapfrog), stats["inv_metric"], int(seed))
-            parts, accs, left = [], [], int(draw_samples) - n_adapts
-            while left > 0:
-                smp, acc, _ = eng.hmc_chains_draws(min(256, left))
+            parts, accs = [], []
+            for nd in _chunks(int(draw_samples) - n_adapts):
+                smp, acc, _ = eng.hmc_chains_draws(nd)
                 parts.append(smp); accs.append(acc)
-                left -= smp.shape[1]
             chain_samples = np.concatenate(parts, axis=1) if parts else np.zeros((nchains, 0, eng.P))
             samples = chain_samples.transpose(1, 0, 2).reshape(-1, eng.P)          # pooled, draw-major
             stats["acceptance"] = np.concatenate(accs, axis=1) if accs else np.zeros((nchains, 0))

@@ -216,3 +216,35 @@ def test_hmc_sampler_on_a_gaussian(npde):
     assert np.all(np.abs(s.mean(axis=0) - mu) < 0.25 * sd + 0.02)
     assert np.all(np.abs(s.std(axis=0) / sd - 1.0) < 0.25)
     assert 0.6 < stats["acceptance"][400:].mean() <= 1.0 and stats["n_adapts"] == 400
+
+
+@pytest.mark.parametrize("n", (100, 107, 20))
+def test_warmup_loop_meets_the_device_restatement(npde, n):
+    """the one warm-up loop of the BPINN mirror (bpinn._adapt_and_draw) against the restatement the resident warm-up is held to
+    (tests/test_resident_hmc_warmup.py: `recurrence`, `window_metric`, its bar), driven by a scripted transition that returns prescribed
+    acceptances and sample rows: the step size handed to every transition and the final one, the metric at the window's event, and the hook
+    that tells the device about it — once when the event fires (n = 100, 107), never otherwise (n = 20)."""
+    from neuralpde_jl_amd import bpinn
+    from test_resident_hmc_warmup import EPS0, EPS64, TARGET, check_recurrence, relmax, supplied, window, window_metric
+    P = 5
+    rows, acc = supplied(P, n)
+    w0, w1, event = window(n)
+    steps, metrics, hooked = [], [], []
+
+    def transition(nd, eps, metric):
+        assert nd == 1 and len(steps) < n
+        steps.append(eps)
+        metrics.append(metric.minv)
+        return [(rows[len(steps) - 1], acc[len(steps) - 1])]
+    out, eps_final, metric = bpinn._adapt_and_draw(transition, bpinn._DiagMetric(np.ones(P)), EPS0, TARGET, n, n, hooked.append)
+    assert len(out) == n and all(np.array_equal(o[0], r) for o, r in zip(out, rows))
+    check_recurrence(f"mirror n={n}", acc, np.asarray(steps), eps_final)
+    assert len(hooked) == (1 if event else 0)
+    if event:
+        m64, mld = window_metric(rows[w0:w1], np.float64), window_metric(rows[w0:w1], np.longdouble)
+        bar = 100.0 * max(relmax(m64, mld), EPS64)
+        assert relmax(hooked[0], m64) <= bar
+        assert all(np.array_equal(m, np.ones(P)) for m in metrics[:w1]) and all(m is hooked[0] for m in metrics[w1:])
+    else:
+        assert all(np.array_equal(m, np.ones(P)) for m in metrics)
+    assert metric.minv is metrics[-1]

@@ -77,7 +77,7 @@ def window_metric(rows, ft):
 
 
 def search(eng, stds, nn, priors, th0, minv, z, eps0):
-    """bpinn.py `_hmc_device` lines 140-158 -> (eps, trials, smallest |d - log 0.8|, largest |H|)"""
+    """bpinn.py `_find_stepsize` under the diagonal metric -> (eps, trials, smallest |d - log 0.8|, largest |H|)"""
     logp_grad, _ = make_logp(eng, stds, nn, priors)
     th = th0.astype(np.float64).copy()
     lp, g = logp_grad(th)
