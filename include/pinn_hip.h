@@ -452,6 +452,33 @@ int pinn_hmc_chains_get(pinn_handle h, int nchains, int ndraws, int64_t p, doubl
                         double* theta, double* logp_cur, double* grad);
 
 /*
+ * Replica-resident Adam: nrep independent Adam trainings of the handle's discretised problem in ONE launch, one workgroup
+ * per replica — restarts from several initialisations, learning-rate sweeps, deep ensembles (pinn_phi_ensemble / pinn_derivative_ensemble take the
+ * resulting [nrep][p] stack).  Every replica minimises the reference's full_loss_function (src/discretize.jl:567-598) by Optimisers.Adam as
+ * solve(prob, Adam(lr); maxiters) does (test/NNPDE1/nnpde__pde_ii_2d_poisson.jl:83-85).  A replica's theta, m and v stay in LDS for a whole launch;
+ * evaluation and update alternate between workgroup barriers.  Opt-in; the state is the optimiser's own: evaluations, pinn_adam_*, pinn_hmc_* and
+ * the quasi-Newton loops on the same handle leave it alone, and it leaves them alone.  Arithmetic: pinn_adam_steps's update rule and bias
+ * corrections in fp32; the evaluation's tiles are walked by the replica's four waves, so gradient sums associate as a one-workgroup launch's do.
+ *   pinn_adam_replicas_init   theta: [nrep][p] floats, replica r starts at row r; m = v = 0 and the step counter of the bias correction is 0.
+ *   pinn_adam_replicas_steps  nsteps Adam iterations of every replica (launches of at most 4096 steps, bit-equal to one).  lr: [nrep], one learning
+ *                             rate per replica; beta1, beta2, eps and term_w ([k] or NULL: ones) are shared.  loss_history (nullable):
+ *                             [nrep][nsteps], entry s the weighted loss at the iterate BEFORE update s, as pinn_adam_steps records it.  The step
+ *                             counter runs on across calls.
+ *   pinn_adam_replicas_get    theta, m, v: [nrep][p] floats; term_sums: [nrep][k] raw sums of squares of the last evaluation (zeros before the
+ *                             first step).  Every output is nullable.
+ * Covered: one family-1 network of at most 32 hidden units per layer (tanh / sigmoid) whose kernel was compiled ahead of time or by the hipcc back
+ * end, fixed point sets, the fp32 kernels, estimated PDE parameters and data terms.  Refused by name, with the handle left as it was: the float64
+ * mode; communicators; device samplers on a term; integral terms; embedded coordinates; DGM networks; several networks or launch groups; sin /
+ * swish / per-layer activations; wider networks and kernels specialised through hiprtc; nrep outside 1..1024; more than 2048 parameters; an LDS
+ * need above a gfx950 workgroup's 160 KB; a learning rate that is not positive and finite; nsteps below 1; calls before init, and calls after the
+ * handle's kernel plan changed (init again).
+ */
+int pinn_adam_replicas_init(pinn_handle h, int nrep, const float* theta, int64_t p);
+int pinn_adam_replicas_steps(pinn_handle h, int nsteps, const float* lr, float beta1, float beta2, float eps, const float* term_w,
+                             double* loss_history);
+int pinn_adam_replicas_get(pinn_handle h, int nrep, int64_t p, float* theta, float* m, float* v, double* term_sums);
+
+/*
  * RESIDENT L-BFGS: pinn_lbfgs's iteration with the iterate x, its gradient, the trial point, the direction, the curvature
  * pairs (rings of `history` vectors) and the line search's bookkeeping in HBM in double.  Opt-in: pinn_lbfgs is unchanged.  The host queues SLOTS —
  * one state-machine launch (judge the evaluation just finished: Armijo test, accept with the curvature-pair update or halve the step; propose the

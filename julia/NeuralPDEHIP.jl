@@ -458,6 +458,30 @@ function hmc_chains_draws!(e::HIPEngine, nchains::Integer, ndraws::Integer; mome
     return samples, acc, lp
 end
 
+"""
+    adam_replicas!(e, θ0, nsteps, etas; beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-8, term_w = nothing, init = true) -> (θ P × nrep, losses nsteps × nrep)
+
+Replica-resident Adam (`pinn_adam_replicas_*`, DESIGN.md §4.17): `solve(remake(prob, u0 = θ0[:, r]), Adam(etas[r]); maxiters = nsteps)`
+(test/NNPDE1/nnpde__pde_ii_2d_poisson.jl:83-85) for every column of `θ0` in one launch, one workgroup per replica.  `init = false` continues the
+state of an earlier call (the bias correction's step counter runs on).
+"""
+function adam_replicas!(e::HIPEngine, θ0::AbstractMatrix, nsteps::Integer, etas; beta1::Real = 0.9f0, beta2::Real = 0.999f0, eps::Real = 1f-8,
+                        term_w = nothing, init::Bool = true)
+    θ = Matrix{Float32}(θ0); lr = Vector{Float32}(etas); w = term_w === nothing ? Float32[] : Vector{Float32}(term_w)
+    nrep = size(θ, 2)
+    if init
+        GC.@preserve θ check(ccall(sym(:pinn_adam_replicas_init), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}, Int64), e.h, nrep, θ, e.P), "pinn_adam_replicas_init")
+    end
+    losses = zeros(Float64, nsteps, nrep)
+    GC.@preserve lr w losses check(ccall(sym(:pinn_adam_replicas_steps), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float32}, Cfloat, Cfloat, Cfloat, Ptr{Float32}, Ptr{Float64}),
+        e.h, nsteps, lr, Float32(beta1), Float32(beta2), Float32(eps), term_w === nothing ? Ptr{Float32}(C_NULL) : pointer(w), losses), "pinn_adam_replicas_steps")
+    GC.@preserve θ check(ccall(sym(:pinn_adam_replicas_get), Cint,
+        (Ptr{Cvoid}, Cint, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}),
+        e.h, nrep, e.P, θ, Ptr{Float32}(C_NULL), Ptr{Float32}(C_NULL), Ptr{Float64}(C_NULL)), "pinn_adam_replicas_get")
+    return θ, losses
+end
+
 function hmc_get(e::HIPEngine)
     θ = zeros(Float64, e.P); g = zeros(Float64, e.P); lp = Ref{Float64}(0.0)
     GC.@preserve θ g check(ccall(sym(:pinn_hmc_get), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}, Ptr{Float64}),

@@ -42,6 +42,7 @@ SYMBOLS = [
     "pinn_hmc_set_metric_dense", "pinn_hmc_get_metric_dense",
     "pinn_nuts_draws",
     "pinn_hmc_chains_init", "pinn_hmc_chains_draws", "pinn_hmc_chains_get",
+    "pinn_adam_replicas_init", "pinn_adam_replicas_steps", "pinn_adam_replicas_get",
     "pinn_lbfgs_init", "pinn_lbfgs_steps", "pinn_lbfgs_get",
     "pinn_bfgs_init", "pinn_bfgs_steps", "pinn_bfgs_get",
     "pinn_phi_ensemble", "pinn_derivative_ensemble",
@@ -143,6 +144,12 @@ class Library:
                                                C.c_int, C.c_uint64]
             L.pinn_hmc_chains_draws.argtypes = [vp, C.c_int, dp, dp]
             L.pinn_hmc_chains_get.argtypes = [vp, C.c_int, C.c_int, C.c_int64, dp, dp, dp, dp, dp, dp]
+        except AttributeError:
+            pass
+        try:                                     # (replica-resident Adam: variant libraries built before it still load)
+            L.pinn_adam_replicas_init.argtypes = [vp, C.c_int, fp, C.c_int64]
+            L.pinn_adam_replicas_steps.argtypes = [vp, C.c_int, fp, C.c_float, C.c_float, C.c_float, fp, dp]
+            L.pinn_adam_replicas_get.argtypes = [vp, C.c_int, C.c_int64, fp, fp, fp, dp]
         except AttributeError:
             pass
         try:                                     # (resident L-BFGS: variant libraries built before it still load)
@@ -814,6 +821,38 @@ class Engine:
         self.L.check(self.L.lib.pinn_hmc_chains_get(self.h, nc, 0, self.P, None, None, None, th.ctypes.data_as(dp), lp.ctypes.data_as(dp), g.ctypes.data_as(dp)),
                      "pinn_hmc_chains_get")
         return th, lp, g
+
+    # ---- replica-resident Adam (include/pinn_hip.h: pinn_adam_replicas_*) ----
+    def adam_replicas_init(self, theta):
+        """`pinn_adam_replicas_init`: nrep = len(theta) Adam trainings of this problem, replica r starting at theta[r]; m = v = 0, step counter 0"""
+        th = np.ascontiguousarray(np.atleast_2d(_f32(theta)))
+        if th.ndim != 2 or th.shape[1] != self.P:
+            raise ValueError("theta: nrep x P values")
+        self.L.check(self.L.lib.pinn_adam_replicas_init(self.h, th.shape[0], th.ctypes.data_as(C.POINTER(C.c_float)), self.P), "pinn_adam_replicas_init")
+        self._nrep = th.shape[0]
+
+    def adam_replicas_steps(self, nsteps: int, lr, weights=None, beta1=0.9, beta2=0.999, eps=1e-8) -> np.ndarray:
+        """`pinn_adam_replicas_steps`: `nsteps` Adam iterations of every replica in one launch.  lr: one learning rate per replica (a scalar: the
+        same for all).  Returns the loss history [nrep x nsteps], entry s the weighted loss at the iterate before update s."""
+        nr, ns, fp = int(getattr(self, "_nrep", 0)), max(int(nsteps), 0), C.POINTER(C.c_float)
+        rates = np.ascontiguousarray(np.broadcast_to(_f32(lr).reshape(-1), (max(nr, 1),)) if np.size(lr) == 1 else _f32(lr).reshape(-1))
+        if nr and rates.size != nr:
+            raise ValueError("lr: one learning rate per replica")
+        w = _f32(weights) if weights is not None else None
+        hist = np.zeros((nr, ns), dtype=np.float64)
+        self.L.check(self.L.lib.pinn_adam_replicas_steps(self.h, int(nsteps), rates.ctypes.data_as(fp), beta1, beta2, eps,
+                                                         w.ctypes.data_as(fp) if w is not None else None, hist.ctypes.data_as(C.POINTER(C.c_double))),
+                     "pinn_adam_replicas_steps")
+        return hist
+
+    def adam_replicas_get(self):
+        """`pinn_adam_replicas_get`: (theta, m, v [nrep x P] float32, raw per-term sums of squares of the last evaluation [nrep x K])"""
+        nr, fp = int(getattr(self, "_nrep", 0)), C.POINTER(C.c_float)
+        th, m, v = (np.zeros((nr, self.P), dtype=np.float32) for _ in range(3))
+        sums = np.zeros((nr, self.K), dtype=np.float64)
+        self.L.check(self.L.lib.pinn_adam_replicas_get(self.h, nr, self.P, th.ctypes.data_as(fp), m.ctypes.data_as(fp), v.ctypes.data_as(fp),
+                                                       sums.ctypes.data_as(C.POINTER(C.c_double))), "pinn_adam_replicas_get")
+        return th, m, v, sums
 
     def hmc_find_stepsize(self, eps0: float, seed: int = 0, normals=None):
         """`pinn_hmc_find_stepsize`: the initial step-size search from the chain's current state, which it leaves alone.  normals: P standard

@@ -644,6 +644,7 @@ int pinn_destroy(pinn_handle h) {
     plat_sync(E.stream);
     hmc_free(E);
     chains_free(E);
+    replicas_free(E);
     lbfgs_free(E);
     bfgs_free(E);
     ens_free(E);

@@ -228,6 +228,7 @@ struct NetPlan {
 };
 struct HmcState;                     // hmc.cpp
 struct ChainsState;                  // hmc_chains.cpp
+struct ReplicaState;                 // adam_replicas.cpp
 struct LbfgsState;                   // lbfgs.cpp
 struct BfgsState;                    // bfgs.cpp
 struct EnsState;                     // ensemble.cpp
@@ -328,6 +329,7 @@ struct pinn_engine {
     int phi_chan = 0;                // jet channels d_phi_out holds per point
     pe::HmcState* hmc = nullptr;     // resident HMC sampler state (hmc.cpp; pinn_hmc_init), nullptr = none
     pe::ChainsState* chains = nullptr;   // chain-resident HMC state (hmc_chains.cpp; pinn_hmc_chains_init), nullptr = none
+    pe::ReplicaState* replicas = nullptr;    // replica-resident Adam state (adam_replicas.cpp; pinn_adam_replicas_init), nullptr = none
     pe::LbfgsState* lbfgs = nullptr; // resident L-BFGS state (lbfgs.cpp; pinn_lbfgs_init), nullptr = none
     int lbfgs_history = 0;           // its history length (pinn_describe)
     int nuts_chunk = 8;              // option "nuts_chunk": slots pinn_nuts_draws queues between two downloads of its control block, 1..64
@@ -446,6 +448,7 @@ void hmc_free(pinn_engine& E);
 // hmc.cpp: nonzero (and the error set) when the handle's chain of pinn_hmc_init holds a dense metric (pinn_hmc_set_metric_dense); `why`: the caller's reason
 int hmc_refuse_dense(const pinn_engine& E, const char* who, const char* why);
 void chains_free(pinn_engine& E);
+void replicas_free(pinn_engine& E);
 void lbfgs_free(pinn_engine& E);
 void bfgs_free(pinn_engine& E);
 int bfgs_params(const pinn_engine& E);          // P of the resident BFGS state (pinn_describe), 0 = none

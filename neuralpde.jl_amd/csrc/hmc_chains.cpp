@@ -35,30 +35,10 @@ void chains_release(ChainsState* C) {
     delete C;
 }
 
-// the set-ups the kernel's evaluation covers; everything else is refused by name, the handle untouched
+// the set-ups the kernel's evaluation covers (resident.hpp: shared with the replica-resident Adam)
 int chains_eligible(pinn_engine& E, const char* who) {
-    const std::string w = std::string(who) + ": ";
-    if (E.f64) return fail(w + "the float64 mode is not covered by the chain-resident sampler (precision = f32)");
-    if (E.comm) return fail(w + "the handle belongs to a communicator; the chain-resident sampler runs on one device");
-    for (auto& T : E.terms) {
-        if (T.sampler != 0) return fail(w + "a term redraws its points on the device; HMC needs a fixed target (fixed point sets)");
-        if (!T.inodes.empty()) return fail(w + "integral terms are not covered by the chain-resident sampler");
-        if (!T.emb_cols.empty()) return fail(w + "embedded coordinates are not covered by the chain-resident sampler");
-    }
-    for (auto& NP : E.netplans)          // (before the counts: a DGM network may run several launch groups)
-        if (NP.spec && NP.spec->family == 3) return fail(w + "DGM networks are not covered by the chain-resident sampler");
-    if (E.nets.size() != 1 || E.groups.size() != 1 || !E.coupled.empty())
-        return fail(w + "several networks or launch groups are not covered by the chain-resident sampler (one network, one fused launch group)");
-    const Group& G = E.groups[0];
-    if (G.kind != 0 || !G.spec) return fail(w + "the launch group is not a fused single-network group");
-    if (G.ga.act != pk::ACT_TANH && G.ga.act != pk::ACT_SIGMOID)
-        return fail(w + "sin, swish and per-layer activations are not covered by the chain-resident sampler (tanh or sigmoid)");
-    if (G.spec->family != 1 || G.spec->HP > 32 || !G.spec->chains)
-        return fail(w + "no chain kernel for this network: family-1 kernels of at most 32 hidden units, compiled ahead of time or by the hipcc back end");
-    if (E.ntheta > 256 * (int64_t)pk::CHAIN_MAX_ELEMS)
-        return fail(w + std::to_string(E.ntheta) + " parameters are more than the " + std::to_string(256 * pk::CHAIN_MAX_ELEMS) + " the chain-resident sampler takes");
-    if (!E.inv_ok || !E.d_inv_ptr || !E.d_gr_ptr) return fail(w + "the handle has no inverse pack map");
-    return 0;
+    return wg_resident_eligible(E, who, "the chain-resident sampler", "HMC needs a fixed target", "chain",
+                                [](const pk::SpecInfo& s) { return s.chains != nullptr; }, 256 * (int64_t)pk::CHAIN_MAX_ELEMS);
 }
 int chains_ready(pinn_engine& E, const char* who) {
     if (!E.chains) return fail(std::string(who) + ": no sampler state (call pinn_hmc_chains_init first)");

@@ -84,6 +84,36 @@ inline int resident_refuse_target(const pinn_engine& E, const char* who, const c
     return 0;
 }
 
+// The set-ups a kernel covers that runs the fused fp32 evaluation of ONE family-1 network inside one workgroup per chain / replica
+// (hmc_chains.cpp, adam_replicas.cpp); everything else is refused by name, the handle untouched.  `what`: the solver's name in the refusals
+// ("the chain-resident sampler"); `fixed_what`: its words for redrawn point sets; `kernel`: the SpecInfo member's name ("chain"); has_kernel:
+// whether the spec carries it; max_p: the parameters it takes.
+inline int wg_resident_eligible(pinn_engine& E, const char* who, const std::string& what, const char* fixed_what, const char* kernel,
+                                bool (*has_kernel)(const pk::SpecInfo&), int64_t max_p) {
+    const std::string w = std::string(who) + ": ";
+    if (E.f64) return fail(w + "the float64 mode is not covered by " + what + " (precision = f32)");
+    if (E.comm) return fail(w + "the handle belongs to a communicator; " + what + " runs on one device");
+    for (auto& T : E.terms) {
+        if (T.sampler != 0) return fail(w + "a term redraws its points on the device; " + fixed_what + " (fixed point sets)");
+        if (!T.inodes.empty()) return fail(w + "integral terms are not covered by " + what);
+        if (!T.emb_cols.empty()) return fail(w + "embedded coordinates are not covered by " + what);
+    }
+    for (auto& NP : E.netplans)          // (before the counts: a DGM network may run several launch groups)
+        if (NP.spec && NP.spec->family == 3) return fail(w + "DGM networks are not covered by " + what);
+    if (E.nets.size() != 1 || E.groups.size() != 1 || !E.coupled.empty())
+        return fail(w + "several networks or launch groups are not covered by " + what + " (one network, one fused launch group)");
+    const Group& G = E.groups[0];
+    if (G.kind != 0 || !G.spec) return fail(w + "the launch group is not a fused single-network group");
+    if (G.ga.act != pk::ACT_TANH && G.ga.act != pk::ACT_SIGMOID)
+        return fail(w + "sin, swish and per-layer activations are not covered by " + what + " (tanh or sigmoid)");
+    if (G.spec->family != 1 || G.spec->HP > 32 || !has_kernel(*G.spec))
+        return fail(w + "no " + kernel + " kernel for this network: family-1 kernels of at most 32 hidden units, compiled ahead of time or by the hipcc back end");
+    if (E.ntheta > max_p)
+        return fail(w + std::to_string(E.ntheta) + " parameters are more than the " + std::to_string(max_p) + " " + what + " takes");
+    if (!E.inv_ok || !E.d_inv_ptr || !E.d_gr_ptr) return fail(w + "the handle has no inverse pack map");
+    return 0;
+}
+
 // The noise-floor switch of the quasi-Newton routines (pinn_lbfgs, pinn_lbfgs_steps, pinn_bfgs_steps).  A line search that cannot decrease the objective along a descent
 // direction has reached the evaluation's noise floor; the split-operand GEMMs' floor is 2-4 x that of the fp32 MFMA kernels:
 // a handle in "split" mode is switched to them once per call and goes on from the same iterate.  The switch only changes arithmetic where a launch

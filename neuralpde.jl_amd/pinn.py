@@ -430,6 +430,47 @@ def solve(prob: OptimizationProblem, alg: Adam, maxiters: int = 1000, callback: 
     return OptimizationSolution(th32.astype(prob.u0.dtype), float(losses[-1]), losses)
 
 
+@dataclass
+class ReplicaSolution:
+    """nrep trainings of one problem: u [nrep x P], losses [nrep x maxiters], objective [nrep] (the last recorded loss of every replica) and
+    best = argmin(objective)."""
+    u: np.ndarray
+    losses: np.ndarray
+    objective: np.ndarray
+    best: int
+
+
+def solve_replicas(prob: OptimizationProblem, alg: Adam, u0s, maxiters: int = 1000, etas=None, callback: Optional[Callable] = None) -> ReplicaSolution:
+    """`solve(remake(prob, u0 = u0s[r]), Adam(etas[r]); maxiters)` for every row r of `u0s` in ONE launch, one workgroup per replica
+    (pinn_adam_replicas_*): restarts from several initialisations, learning-rate sweeps (`etas`, default `alg.eta` for
+    every replica), deep ensembles.  Deep-ensemble mean and std of a depvar: `mean, std = eng.phi_ensemble(sol.u, x)`.
+    The kernel trains against one fixed objective: a callback, `additional_loss`, adaptive reweighting, resampling strategies and adaptive
+    cubature with `refresh` raise a ValueError that names the condition; set-ups the kernel does not cover raise the engine's EngineError.
+    There is no fall-back to a loop over `solve`."""
+    if not isinstance(alg, Adam):
+        raise ValueError("solve_replicas: the replicas are trained by Adam")
+    rep = prob.pinnrep
+    eng = rep.engine
+    refresh = int(getattr(rep.strategy, "refresh", 0)) if getattr(rep, "_refine", None) is not None else 0
+    for unmet, why in ((callback is not None, "a callback needs every iterate on the host"),
+                       (rep.additional_loss is not None, "additional_loss is a host function"),
+                       (rep.adaloss.reweight_every > 0, "adaptive reweighting changes the objective between steps"),
+                       (bool(getattr(rep, "_device_samplers", None)) or rep._state.get("resample") is not None,
+                        "resampling strategies redraw the point sets between steps"),
+                       (refresh > 0, "adaptive cubature with refresh re-meshes between steps")):
+        if unmet:
+            raise ValueError(f"solve_replicas: {why}; the replicas train inside one launch against one fixed objective")
+    th = np.ascontiguousarray(np.atleast_2d(np.asarray(u0s, dtype=np.float32)))
+    lr = np.full(th.shape[0], alg.eta, dtype=np.float32) if etas is None else np.asarray(etas, dtype=np.float32).reshape(-1)
+    if lr.size != th.shape[0]:
+        raise ValueError("solve_replicas: etas holds one learning rate per row of u0s")
+    eng.adam_replicas_init(th)
+    losses = eng.adam_replicas_steps(int(maxiters), lr, rep._weights_now(), alg.beta[0], alg.beta[1], alg.epsilon)
+    u = eng.adam_replicas_get()[0]
+    objective = losses[:, -1].copy()
+    return ReplicaSolution(u.astype(prob.u0.dtype), losses, objective, int(np.argmin(objective)))
+
+
 def _host_adam(prob: OptimizationProblem, alg: Adam, maxiters: int, callback) -> OptimizationSolution:
     """[3P] Optimisers.Adam on the host over `prob.f.value_and_grad` (the objective of src/discretize.jl:567-598 incl. a host-side
     `additional_loss`, which must return `(value, gradient)` here: the Python mirror has no AD to differentiate a bare value)."""
