@@ -479,6 +479,32 @@ int pinn_adam_replicas_steps(pinn_handle h, int nsteps, const float* lr, float b
 int pinn_adam_replicas_get(pinn_handle h, int nrep, int64_t p, float* theta, float* m, float* v, double* term_sums);
 
 /*
+ * Replica-resident L-BFGS: the quasi-Newton finisher of nrep trainings of the handle's discretised problem in ONE launch,
+ * one workgroup per replica — the second half of the reference's schedule solve(prob, Adam(); ...) then solve(prob, LBFGS(); ...) for the stack
+ * pinn_adam_replicas_get returns.  The iteration is pinn_lbfgs_steps's, slot by slot (one slot = one evaluation and one judgement; a rejected trial
+ * costs a full evaluation): a replica's x, gradient, trial point and direction (double), its control block, the trial theta and the evaluation's
+ * gradient (float) stay in LDS for a whole launch; the rings S, Y, rho stay in HBM per replica.  Replicas run different numbers of slots; a replica
+ * that reaches a terminal status retires its workgroup.  Opt-in; the state is the finisher's own: evaluations, pinn_adam_*, pinn_adam_replicas_*,
+ * pinn_hmc_* and the single-training quasi-Newton loops on the same handle leave it alone, and it leaves them alone.  Arithmetic: the fp32 lane of
+ * pinn_lbfgs_steps (objective sum_k w_k sums_k / n_k in double on the evaluation's raw sums); the evaluation's tiles are walked by the replica's
+ * four waves, so gradient sums associate as a one-workgroup launch's do.
+ *   pinn_lbfgs_replicas_init   theta: [nrep][p] doubles, replica r starts at row r; one evaluation per replica gives (f, g); the rings are empty.
+ *                              history: pairs kept, 1..64.  term_w ([k] or NULL: ones) is fixed here: the curvature belongs to one objective.
+ *   pinn_lbfgs_replicas_steps  at most maxiters further iterations and max_evals further trial evaluations of every replica (launches of at most
+ *                              4096 slots; the host reads the nrep control blocks in between).  A call that ends inside a line search resumes
+ *                              there.  loss_history (nullable): [nrep][maxiters], the objective after every iteration, padded with the last
+ *                              objective.  iters_done, evals_done, status (nullable): [nrep] each; status as pinn_lbfgs_steps: 0 RUN, 1 RETRY,
+ *                              2 CONVERGED (max |g_i| <= gtol), 3 STALLED (30 rejected trials), 4 MAXITER.
+ *   pinn_lbfgs_replicas_get    theta: [nrep][p], f: [nrep], grad: [nrep][p] of the current iterates.  Every output is nullable.
+ * Covered and refused as pinn_adam_replicas_* (the learning rate apart); also refused by name, with the handle left as it was: history outside
+ * 1..64; maxiters or max_evals below 1; calls before init, and calls after the handle's kernel plan changed (init again).
+ */
+int pinn_lbfgs_replicas_init(pinn_handle h, int nrep, const double* theta, int64_t p, int history, const float* term_w);
+int pinn_lbfgs_replicas_steps(pinn_handle h, int maxiters, int max_evals, double gtol, double* loss_history, int* iters_done, int* evals_done,
+                              int* status);
+int pinn_lbfgs_replicas_get(pinn_handle h, int nrep, int64_t p, double* theta, double* f, double* grad);
+
+/*
  * RESIDENT L-BFGS: pinn_lbfgs's iteration with the iterate x, its gradient, the trial point, the direction, the curvature
  * pairs (rings of `history` vectors) and the line search's bookkeeping in HBM in double.  Opt-in: pinn_lbfgs is unchanged.  The host queues SLOTS —
  * one state-machine launch (judge the evaluation just finished: Armijo test, accept with the curvature-pair update or halve the step; propose the

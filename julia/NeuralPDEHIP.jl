@@ -482,6 +482,31 @@ function adam_replicas!(e::HIPEngine, θ0::AbstractMatrix, nsteps::Integer, etas
     return θ, losses
 end
 
+"""
+    lbfgs_replicas!(e, θ0, maxiters; history = 10, gtol = 1e-8, max_evals = 31 * maxiters, term_w = nothing, init = true)
+        -> (θ P × nrep, losses maxiters × nrep, status nrep)
+
+Replica-resident L-BFGS (`pinn_lbfgs_replicas_*`, DESIGN.md §4.18): `solve(remake(prob, u0 = θ0[:, r]), LBFGS(); maxiters)` for every column of
+`θ0` in one launch, one workgroup per replica — the finisher of the stack `adam_replicas!` returns.  `init = false` continues the state of an
+earlier call.  `losses` is padded with a replica's last objective; `status`: 0 RUN, 1 RETRY, 2 CONVERGED, 3 STALLED, 4 MAXITER.
+"""
+function lbfgs_replicas!(e::HIPEngine, θ0::AbstractMatrix, maxiters::Integer; history::Integer = 10, gtol::Real = 1e-8,
+                         max_evals::Integer = 31 * maxiters, term_w = nothing, init::Bool = true)
+    θ = Matrix{Float64}(θ0); w = term_w === nothing ? Float32[] : Vector{Float32}(term_w)
+    nrep = size(θ, 2)
+    if init
+        GC.@preserve θ w check(ccall(sym(:pinn_lbfgs_replicas_init), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64, Cint, Ptr{Float32}),
+            e.h, nrep, θ, e.P, history, term_w === nothing ? Ptr{Float32}(C_NULL) : pointer(w)), "pinn_lbfgs_replicas_init")
+    end
+    losses = zeros(Float64, maxiters, nrep); its = zeros(Cint, nrep); evs = zeros(Cint, nrep); status = zeros(Cint, nrep)
+    GC.@preserve losses its evs status check(ccall(sym(:pinn_lbfgs_replicas_steps), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}),
+        e.h, maxiters, max_evals, Float64(gtol), losses, its, evs, status), "pinn_lbfgs_replicas_steps")
+    GC.@preserve θ check(ccall(sym(:pinn_lbfgs_replicas_get), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        e.h, nrep, e.P, θ, Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL)), "pinn_lbfgs_replicas_get")
+    return θ, losses, status
+end
+
 function hmc_get(e::HIPEngine)
     θ = zeros(Float64, e.P); g = zeros(Float64, e.P); lp = Ref{Float64}(0.0)
     GC.@preserve θ g check(ccall(sym(:pinn_hmc_get), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}, Ptr{Float64}),

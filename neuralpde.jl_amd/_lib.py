@@ -43,6 +43,7 @@ SYMBOLS = [
     "pinn_nuts_draws",
     "pinn_hmc_chains_init", "pinn_hmc_chains_draws", "pinn_hmc_chains_get",
     "pinn_adam_replicas_init", "pinn_adam_replicas_steps", "pinn_adam_replicas_get",
+    "pinn_lbfgs_replicas_init", "pinn_lbfgs_replicas_steps", "pinn_lbfgs_replicas_get",
     "pinn_lbfgs_init", "pinn_lbfgs_steps", "pinn_lbfgs_get",
     "pinn_bfgs_init", "pinn_bfgs_steps", "pinn_bfgs_get",
     "pinn_phi_ensemble", "pinn_derivative_ensemble",
@@ -150,6 +151,9 @@ class Library:
             L.pinn_adam_replicas_init.argtypes = [vp, C.c_int, fp, C.c_int64]
             L.pinn_adam_replicas_steps.argtypes = [vp, C.c_int, fp, C.c_float, C.c_float, C.c_float, fp, dp]
             L.pinn_adam_replicas_get.argtypes = [vp, C.c_int, C.c_int64, fp, fp, fp, dp]
+            L.pinn_lbfgs_replicas_init.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int, fp]
+            L.pinn_lbfgs_replicas_steps.argtypes = [vp, C.c_int, C.c_int, C.c_double, dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.pinn_lbfgs_replicas_get.argtypes = [vp, C.c_int, C.c_int64, dp, dp, dp]
         except AttributeError:
             pass
         try:                                     # (resident L-BFGS: variant libraries built before it still load)
@@ -853,6 +857,38 @@ class Engine:
         self.L.check(self.L.lib.pinn_adam_replicas_get(self.h, nr, self.P, th.ctypes.data_as(fp), m.ctypes.data_as(fp), v.ctypes.data_as(fp),
                                                        sums.ctypes.data_as(C.POINTER(C.c_double))), "pinn_adam_replicas_get")
         return th, m, v, sums
+
+    # ---- replica-resident L-BFGS (include/pinn_hip.h: pinn_lbfgs_replicas_*) ----
+    def lbfgs_replicas_init(self, theta, weights=None, history: int = 10):
+        """`pinn_lbfgs_replicas_init`: nrep = len(theta) L-BFGS finishers of this problem, replica r starting at theta[r]; the term weights are
+        fixed here."""
+        th = np.ascontiguousarray(np.atleast_2d(_f64(theta)))
+        if th.ndim != 2 or th.shape[1] != self.P:
+            raise ValueError("theta: nrep x P values")
+        w = _f32(weights) if weights is not None else None
+        self.L.check(self.L.lib.pinn_lbfgs_replicas_init(self.h, th.shape[0], th.ctypes.data_as(C.POINTER(C.c_double)), self.P, int(history),
+                                                         w.ctypes.data_as(C.POINTER(C.c_float)) if w is not None else None), "pinn_lbfgs_replicas_init")
+        self._nrep_lbfgs = th.shape[0]
+
+    def lbfgs_replicas_steps(self, maxiters: int, max_evals: int = None, gtol: float = 1e-8):
+        """`pinn_lbfgs_replicas_steps`: at most `maxiters` further iterations / `max_evals` further trial evaluations (default: 31 per iteration,
+        which never binds) of every replica.  Returns (loss history [nrep x maxiters], padded with the last objective; iterations, evaluations,
+        status codes [nrep] each: indices into LBFGS_STATUS)."""
+        nr, mi, ip = int(getattr(self, "_nrep_lbfgs", 0)), max(int(maxiters), 0), C.POINTER(C.c_int)
+        hist = np.zeros((nr, mi), dtype=np.float64)
+        it, ev, st = (np.zeros(nr, dtype=np.int32) for _ in range(3))
+        me = 31 * max(mi, 1) if max_evals is None else int(max_evals)
+        self.L.check(self.L.lib.pinn_lbfgs_replicas_steps(self.h, int(maxiters), me, float(gtol), hist.ctypes.data_as(C.POINTER(C.c_double)),
+                                                          it.ctypes.data_as(ip), ev.ctypes.data_as(ip), st.ctypes.data_as(ip)), "pinn_lbfgs_replicas_steps")
+        return hist, it, ev, st
+
+    def lbfgs_replicas_get(self):
+        """`pinn_lbfgs_replicas_get`: (theta [nrep x P], objective [nrep], gradient [nrep x P]) of the current iterates"""
+        nr, dp = int(getattr(self, "_nrep_lbfgs", 0)), C.POINTER(C.c_double)
+        th, f, g = np.zeros((nr, self.P)), np.zeros(nr), np.zeros((nr, self.P))
+        self.L.check(self.L.lib.pinn_lbfgs_replicas_get(self.h, nr, self.P, th.ctypes.data_as(dp), f.ctypes.data_as(dp), g.ctypes.data_as(dp)),
+                     "pinn_lbfgs_replicas_get")
+        return th, f, g
 
     def hmc_find_stepsize(self, eps0: float, seed: int = 0, normals=None):
         """`pinn_hmc_find_stepsize`: the initial step-size search from the chain's current state, which it leaves alone.  normals: P standard

@@ -70,13 +70,17 @@ DEV void replica_scatter(int i, const ReplicaArgs& ra, const ReplicaView& v, flo
     for (int q = ra.inv_ptr[i]; q < q1; ++q) v.image[ra.inv_pos[q] & 0xFFFFFF] = x;
     if (i >= ra.p_off && i < ra.p_off + ra.ne) v.params[i - ra.p_off] = x;
 }
-// element i after an evaluation: its slab entries in map order, one double accumulator, narrowed; the Adam rule on the LDS state
-DEV void replica_update(int i, const ReplicaArgs& ra, const ReplicaView& v, float lr, float c1, float c2) {
+// element i of the evaluation's gradient: its slab entries in map order, one double accumulator (lbfgs_replica_kernels.hpp sums likewise)
+DEV double replica_slab_sum(int i, const ReplicaArgs& ra, const ReplicaView& v) {
     double s = 0.0;
     const int e1 = ra.row_ptr[i + 1];
     for (int e = ra.row_ptr[i]; e < e1; ++e) s += (double)v.slab[ra.row_ent[e]];
+    return s;
+}
+// element i after an evaluation: the gradient narrowed; the Adam rule on the LDS state
+DEV void replica_update(int i, const ReplicaArgs& ra, const ReplicaView& v, float lr, float c1, float c2) {
     float mi = v.m[i], vi = v.v[i];
-    const float t = ur::adam_update(v.th[i], mi, vi, (float)s, lr, ra.b1, ra.b2, ra.eps, c1, c2);
+    const float t = ur::adam_update(v.th[i], mi, vi, (float)replica_slab_sum(i, ra, v), lr, ra.b1, ra.b2, ra.eps, c1, c2);
     v.m[i] = mi;
     v.v[i] = vi;
     v.th[i] = t;

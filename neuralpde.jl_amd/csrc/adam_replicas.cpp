@@ -125,16 +125,8 @@ int pinn_adam_replicas_steps(pinn_handle h, int nsteps, const float* lr, float b
     if (plat_h2d(R.d_c12, c12.data(), sizeof(float) * c12.size(), E.stream) || plat_h2d(R.d_wn, wn.data(), sizeof(float) * wn.size(), E.stream) ||
         plat_h2d(R.d_lr, lr, sizeof(float) * nr, E.stream))
         return fail(std::string(who) + ": H2D copy failed");
-    // the group's launch arguments with the replicas' buffers in place of the handle's, the handle's maps as they are now; the term weights
-    // fold into the reverse sweep's seeds (adam.cpp train_common's expression)
     const Group& G = E.groups[0];
-    pk::GroupArgs ga = G.ga;
-    for (size_t j = 0; j < G.terms.size(); ++j) {
-        const int ti = G.terms[j];
-        ga.terms[j].scale = (float)(2.0 * (double)(term_w ? term_w[ti] : 1.0f) / (double)E.terms[ti].n_norm);
-    }
-    ga.packed = R.d_packed; ga.params = R.d_params; ga.slabs = R.d_slabs; ga.losspart = R.d_losspart; ga.scratch = R.d_scratch;
-    ga.chain = 0;
+    const pk::GroupArgs ga = wg_resident_group_args(E, term_w, R.d_packed, R.d_params, R.d_slabs, R.d_losspart, R.d_scratch);
     pk::ReplicaArgs ra;
     std::memset(&ra, 0, sizeof ra);
     ra.state = R.d_state; ra.packed = R.d_packed; ra.params = R.d_params; ra.sse = R.d_sse;

@@ -645,6 +645,7 @@ int pinn_destroy(pinn_handle h) {
     hmc_free(E);
     chains_free(E);
     replicas_free(E);
+    lbfgs_replicas_free(E);
     lbfgs_free(E);
     bfgs_free(E);
     ens_free(E);

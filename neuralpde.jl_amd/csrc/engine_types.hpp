@@ -229,6 +229,7 @@ struct NetPlan {
 struct HmcState;                     // hmc.cpp
 struct ChainsState;                  // hmc_chains.cpp
 struct ReplicaState;                 // adam_replicas.cpp
+struct LbfgsReplicaState;            // lbfgs_replicas.cpp
 struct LbfgsState;                   // lbfgs.cpp
 struct BfgsState;                    // bfgs.cpp
 struct EnsState;                     // ensemble.cpp
@@ -330,6 +331,7 @@ struct pinn_engine {
     pe::HmcState* hmc = nullptr;     // resident HMC sampler state (hmc.cpp; pinn_hmc_init), nullptr = none
     pe::ChainsState* chains = nullptr;   // chain-resident HMC state (hmc_chains.cpp; pinn_hmc_chains_init), nullptr = none
     pe::ReplicaState* replicas = nullptr;    // replica-resident Adam state (adam_replicas.cpp; pinn_adam_replicas_init), nullptr = none
+    pe::LbfgsReplicaState* lbfgs_replicas = nullptr;     // replica-resident L-BFGS state (lbfgs_replicas.cpp; pinn_lbfgs_replicas_init), nullptr = none
     pe::LbfgsState* lbfgs = nullptr; // resident L-BFGS state (lbfgs.cpp; pinn_lbfgs_init), nullptr = none
     int lbfgs_history = 0;           // its history length (pinn_describe)
     int nuts_chunk = 8;              // option "nuts_chunk": slots pinn_nuts_draws queues between two downloads of its control block, 1..64
@@ -449,6 +451,7 @@ void hmc_free(pinn_engine& E);
 int hmc_refuse_dense(const pinn_engine& E, const char* who, const char* why);
 void chains_free(pinn_engine& E);
 void replicas_free(pinn_engine& E);
+void lbfgs_replicas_free(pinn_engine& E);
 void lbfgs_free(pinn_engine& E);
 void bfgs_free(pinn_engine& E);
 int bfgs_params(const pinn_engine& E);          // P of the resident BFGS state (pinn_describe), 0 = none

@@ -13,6 +13,7 @@ typedef struct ihipStream_t* plat_stream;       // (= hipStream_t; only the type
 #include "plat.hpp"
 #include "hmc_chain_kernels.hpp"       // (double-precision library calls: ahead-of-time and hipcc-specialised members only)
 #include "adam_replica_kernels.hpp"    // (likewise)
+#include "lbfgs_replica_kernels.hpp"   // (likewise)
 #endif
 
 namespace pk {
@@ -20,6 +21,7 @@ namespace pk {
 constexpr int MAX_GEN_CHANNELS = 24;
 struct ChainArgs;                    // hmc_chain_kernels.hpp
 struct ReplicaArgs;                  // adam_replica_kernels.hpp
+struct LbfgsReplicaArgs;             // lbfgs_replica_kernels.hpp
 
 struct SpecInfo {
     int family;                      // 1: one wave per tile (pinn_kernels.hpp); 2: neuron-split workgroups (pinn_kernels2.hpp)
@@ -53,17 +55,21 @@ struct SpecInfo {
     void (*chains)(const GroupArgs&, const ChainArgs&, int nchains, plat_stream);
     // family 1, at most 32 wide: replica-resident Adam, one workgroup per replica (adam_replica_kernels.hpp: k_adam_replicas, tanh / sigmoid variants); nullptr: not compiled for this spec
     void (*replicas)(const GroupArgs&, const ReplicaArgs&, int nrep, plat_stream);
+    // family 1, at most 32 wide: replica-resident L-BFGS, one workgroup per replica (lbfgs_replica_kernels.hpp: k_lbfgs_replicas, tanh / sigmoid variants); nullptr: not compiled for this spec
+    void (*lbfgs_replicas)(const GroupArgs&, const LbfgsReplicaArgs&, int nrep, plat_stream) = nullptr;
 };
 
 template <class S>
 HD SpecInfo make_info(void (*launch)(const GroupArgs&, int, int, plat_stream), int has_sin = 0,
                       void (*train)(const GroupArgs&, const TrainArgs&, int, plat_stream) = nullptr,
                       void (*chains)(const GroupArgs&, const ChainArgs&, int, plat_stream) = nullptr,
-                      void (*replicas)(const GroupArgs&, const ReplicaArgs&, int, plat_stream) = nullptr) {
+                      void (*replicas)(const GroupArgs&, const ReplicaArgs&, int, plat_stream) = nullptr,
+                      void (*lbfgs_replicas)(const GroupArgs&, const LbfgsReplicaArgs&, int, plat_stream) = nullptr) {
     SpecInfo s = {};
     s.train = train;
     s.chains = chains;
     s.replicas = replicas;
+    s.lbfgs_replicas = lbfgs_replicas;
     s.has_sin = has_sin;
     s.jit = 0;
     s.act1 = s.act2 = s.dgm_rows = 0;
@@ -152,6 +158,14 @@ __global__ void __launch_bounds__(256, 1) k_adam_replicas(const GroupArgs ga, co
     __shared__ __attribute__((aligned(16))) float lds_all[S::LDS_WG + 3 * REPLICA_MAX_P];
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     wave_adam_replicas<S, ACTK>(ga, ra, (int)blockIdx.x, w, lds_all);
+}
+// nrep L-BFGS finishers, one workgroup each (lbfgs_replica_kernels.hpp): the replica's x | g | xn | d, its control block, the trial theta and the
+// evaluation's gradient sit in LDS behind the evaluation's floats for the whole launch; workgroup barriers only, so any number may queue
+template <class S, int ACTK>
+__global__ void __launch_bounds__(256, 1) k_lbfgs_replicas(const GroupArgs ga, const LbfgsReplicaArgs la) {
+    __shared__ __attribute__((aligned(16))) float lds_all[lbfgs_replica_lds(S::LDS_WG)];
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    wave_lbfgs_replicas<S, ACTK>(ga, la, (int)blockIdx.x, w, lds_all);
 }
 #endif
 // family 2: two waves per SIMD => at most 256 VGPR+AGPR per lane: two 4-wave workgroups per CU (H = 64), or one 8-wave workgroup

@@ -114,6 +114,21 @@ inline int wg_resident_eligible(pinn_engine& E, const char* who, const std::stri
     return 0;
 }
 
+// The launch arguments of such a kernel: the group's, with the solver's per-replica buffers in place of the handle's and the handle's maps as they
+// are now; the term weights fold into the reverse sweep's seeds (adam.cpp train_common's expression)
+inline pk::GroupArgs wg_resident_group_args(const pinn_engine& E, const float* term_w, float* packed, float* params, float* slabs, double* losspart,
+                                            float* scratch) {
+    const Group& G = E.groups[0];
+    pk::GroupArgs ga = G.ga;
+    for (size_t j = 0; j < G.terms.size(); ++j) {
+        const int ti = G.terms[j];
+        ga.terms[j].scale = (float)(2.0 * (double)(term_w ? term_w[ti] : 1.0f) / (double)E.terms[ti].n_norm);
+    }
+    ga.packed = packed; ga.params = params; ga.slabs = slabs; ga.losspart = losspart; ga.scratch = scratch;
+    ga.chain = 0;
+    return ga;
+}
+
 // The noise-floor switch of the quasi-Newton routines (pinn_lbfgs, pinn_lbfgs_steps, pinn_bfgs_steps).  A line search that cannot decrease the objective along a descent
 // direction has reached the evaluation's noise floor; the split-operand GEMMs' floor is 2-4 x that of the fp32 MFMA kernels:
 // a handle in "split" mode is switched to them once per call and goes on from the same iterate.  The switch only changes arithmetic where a launch

@@ -111,6 +111,23 @@ void run_emu_replicas(const GroupArgs& ga, const ReplicaArgs& ra, int nrep) {
         for (int w = 0; w < 4; ++w) th[w].join();
     }
 }
+// replica-resident L-BFGS: likewise
+template <class S, int ACTK>
+void run_emu_lbfgs_replicas(const GroupArgs& ga, const LbfgsReplicaArgs& la, int nrep) {
+    std::vector<float> lds((size_t)lbfgs_replica_lds(S::LDS_WG));
+    for (int r = 0; r < nrep; ++r) {
+        std::fill(lds.begin(), lds.end(), std::nanf(""));
+        EmuBarrier bar;
+        std::thread th[4];
+        for (int w = 0; w < 4; ++w)
+            th[w] = std::thread([&, w] {
+                wv::emu_barrier_hook = &EmuBarrier::wait;
+                wv::emu_barrier_ctx = &bar;
+                wave_lbfgs_replicas<S, ACTK>(ga, la, r, w, lds.data());
+            });
+        for (int w = 0; w < 4; ++w) th[w].join();
+    }
+}
 template <class S, int MODE, int ACTK>
 void run_emu2(const GroupArgs& ga, int blocks) {
     std::vector<float> lds((size_t)S::LDS_WG);
@@ -151,6 +168,7 @@ void run_emu2m(const GroupArgs& ga, int blocks) {
 #define PINN_LAUNCH_TRAIN(S, ACTK, ga, ta, blocks, st) run_emu_train<S, ACTK>(ga, ta, blocks)
 #define PINN_LAUNCH_CHAINS(S, ACTK, ga, ca, nchains, st) run_emu_chains<S, ACTK>(ga, ca, nchains)
 #define PINN_LAUNCH_REPLICAS(S, ACTK, ga, ra, nrep, st) run_emu_replicas<S, ACTK>(ga, ra, nrep)
+#define PINN_LAUNCH_LBFGS_REPLICAS(S, ACTK, ga, la, nrep, st) run_emu_lbfgs_replicas<S, ACTK>(ga, la, nrep)
 #else
 #define PINN_LAUNCH2(S, MODE, ACTK, ga, blocks, st) hipLaunchKernelGGL((k_wave2<S, MODE, ACTK>), dim3(blocks), dim3(64 * S::NW), 0, st, ga)
 #define PINN_LAUNCH2M(S0, S1, ACTK, MODE, ga, blocks, st) hipLaunchKernelGGL((k_wave2m<S0, S1, ACTK, MODE>), dim3(blocks), dim3(64 * S0::NW), 0, st, ga)
@@ -158,6 +176,7 @@ void run_emu2m(const GroupArgs& ga, int blocks) {
 #define PINN_LAUNCH_TRAIN(S, ACTK, ga, ta, blocks, st) hipLaunchKernelGGL((k_train<S, ACTK>), dim3(blocks), dim3(256), 0, st, ga, ta)
 #define PINN_LAUNCH_CHAINS(S, ACTK, ga, ca, nchains, st) hipLaunchKernelGGL((k_hmc_chains<S, ACTK>), dim3(nchains), dim3(256), 0, st, ga, ca)
 #define PINN_LAUNCH_REPLICAS(S, ACTK, ga, ra, nrep, st) hipLaunchKernelGGL((k_adam_replicas<S, ACTK>), dim3(nrep), dim3(256), 0, st, ga, ra)
+#define PINN_LAUNCH_LBFGS_REPLICAS(S, ACTK, ga, la, nrep, st) hipLaunchKernelGGL((k_lbfgs_replicas<S, ACTK>), dim3(nrep), dim3(256), 0, st, ga, la)
 #endif
 
 // The activation kind is a template parameter of the kernels (ACTK): tanh and sigmoid variants for every spec; sin variants (sincos in
@@ -213,6 +232,16 @@ template <class S> void launch_replicas(const GroupArgs& ga, const ReplicaArgs& 
 }
 template <class S> void (*replicas_of())(const GroupArgs&, const ReplicaArgs&, int, plat_stream) {
     if constexpr (S::HP <= 32) return &launch_replicas<S>; else return nullptr;
+}
+// replica-resident L-BFGS of a family-1 spec (tanh / sigmoid), for the same widths
+template <class S> void launch_lbfgs_replicas(const GroupArgs& ga, const LbfgsReplicaArgs& la, int nrep, plat_stream st) {
+    (void)st;
+    static_assert(sizeof(GroupArgs) + sizeof(LbfgsReplicaArgs) <= 4096, "kernel arguments of k_lbfgs_replicas");
+    static_assert(4 * lbfgs_replica_lds(S::LDS_WG) <= 160 * 1024, "LDS of k_lbfgs_replicas: a gfx950 workgroup has 160 KB");
+    if (ga.act == ACT_TANH) PINN_LAUNCH_LBFGS_REPLICAS(S, ACT_TANH, ga, la, nrep, st); else PINN_LAUNCH_LBFGS_REPLICAS(S, ACT_SIGMOID, ga, la, nrep, st);
+}
+template <class S> void (*lbfgs_replicas_of())(const GroupArgs&, const LbfgsReplicaArgs&, int, plat_stream) {
+    if constexpr (S::HP <= 32) return &launch_lbfgs_replicas<S>; else return nullptr;
 }
 template <class S0, class S1> void launch_pair2(const GroupArgs& ga, int mode, int blocks, plat_stream st) {
     (void)st;
@@ -342,6 +371,15 @@ PairInfo make_pair_info() {
 #else
 #define PINN_REPLICAS_OF(S) nullptr
 #endif
+// the replica-resident L-BFGS kernels of a family-1 spec (nullptr beyond 32 hidden units); PINN_F1_LBFGS_REPLICAS=0 leaves them out of a translation unit
+#ifndef PINN_F1_LBFGS_REPLICAS
+#define PINN_F1_LBFGS_REPLICAS 1
+#endif
+#if PINN_F1_LBFGS_REPLICAS
+#define PINN_LBFGS_REPLICAS_OF(S) pk::lbfgs_replicas_of<S>()
+#else
+#define PINN_LBFGS_REPLICAS_OF(S) nullptr
+#endif
 template <class S> struct Launch2Plain { static void fn(const GroupArgs& ga, int mode, int blocks, plat_stream st) { launch_spec2<S>(ga, mode, blocks, st); } };
 template <class S> struct Launch2Sin { static void fn(const GroupArgs& ga, int mode, int blocks, plat_stream st) { launch_spec2_var<S, VARIANT_SIN>(ga, mode, blocks, st); } };
 template <class S> struct Launch2Swish { static void fn(const GroupArgs& ga, int mode, int blocks, plat_stream st) { launch_spec2_var<S, VARIANT_SWISH>(ga, mode, blocks, st); } };
@@ -365,13 +403,13 @@ template <class S0, class S1> struct PairRegistrar2<S0, S1, false> { PairRegistr
 #define PINN_INSTANTIATE_HI(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)                  \
     namespace {                                                                              \
     using NAME##_spec = pk::Spec<HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI>;                  \
-    pk::Registrar NAME##_reg(pk::make_info<NAME##_spec>(&pk::launch_spec<NAME##_spec>, 0, PINN_TRAIN_OF(NAME##_spec), PINN_CHAINS_OF(NAME##_spec), PINN_REPLICAS_OF(NAME##_spec))); \
+    pk::Registrar NAME##_reg(pk::make_info<NAME##_spec>(&pk::launch_spec<NAME##_spec>, 0, PINN_TRAIN_OF(NAME##_spec), PINN_CHAINS_OF(NAME##_spec), PINN_REPLICAS_OF(NAME##_spec), PINN_LBFGS_REPLICAS_OF(NAME##_spec))); \
     }
 // family 1 spec with extra kernel variants compiled in as well (VARIANTS: bits as SpecInfo::has_sin)
 #define PINN_INSTANTIATE_HI_VAR(NAME, VARIANTS, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)    \
     namespace {                                                                              \
     using NAME##_spec = pk::Spec<HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI>;                  \
-    pk::Registrar NAME##_reg(pk::make_info<NAME##_spec>(&pk::launch_spec_var<NAME##_spec, (VARIANTS)>, (VARIANTS), PINN_TRAIN_OF(NAME##_spec), PINN_CHAINS_OF(NAME##_spec), PINN_REPLICAS_OF(NAME##_spec))); \
+    pk::Registrar NAME##_reg(pk::make_info<NAME##_spec>(&pk::launch_spec_var<NAME##_spec, (VARIANTS)>, (VARIANTS), PINN_TRAIN_OF(NAME##_spec), PINN_CHAINS_OF(NAME##_spec), PINN_REPLICAS_OF(NAME##_spec), PINN_LBFGS_REPLICAS_OF(NAME##_spec))); \
     }
 // the sin-activation kernels; the swish kernels; both
 #define PINN_INSTANTIATE2_HI_SIN(NAME, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI) PINN_INSTANTIATE2_ANY(NAME, Launch2Sin, pk::VARIANT_SIN, HP, NHH, D, D1MASK, PAIRS, NPAIR, PG, HI)

@@ -433,11 +433,12 @@ def solve(prob: OptimizationProblem, alg: Adam, maxiters: int = 1000, callback: 
 @dataclass
 class ReplicaSolution:
     """nrep trainings of one problem: u [nrep x P], losses [nrep x maxiters], objective [nrep] (the last recorded loss of every replica) and
-    best = argmin(objective)."""
+    best = argmin(objective); status [nrep] (LBFGS only): the finisher's status code per replica (indices into Engine.LBFGS_STATUS)."""
     u: np.ndarray
     losses: np.ndarray
     objective: np.ndarray
     best: int
+    status: Optional[np.ndarray] = None
 
 
 def solve_replicas(prob: OptimizationProblem, alg: Adam, u0s, maxiters: int = 1000, etas=None, callback: Optional[Callable] = None) -> ReplicaSolution:
@@ -446,9 +447,14 @@ def solve_replicas(prob: OptimizationProblem, alg: Adam, u0s, maxiters: int = 10
     every replica), deep ensembles.  Deep-ensemble mean and std of a depvar: `mean, std = eng.phi_ensemble(sol.u, x)`.
     The kernel trains against one fixed objective: a callback, `additional_loss`, adaptive reweighting, resampling strategies and adaptive
     cubature with `refresh` raise a ValueError that names the condition; set-ups the kernel does not cover raise the engine's EngineError.
-    There is no fall-back to a loop over `solve`."""
-    if not isinstance(alg, Adam):
-        raise ValueError("solve_replicas: the replicas are trained by Adam")
+    There is no fall-back to a loop over `solve`.
+    `alg = LBFGS(m, gtol)` runs the quasi-Newton finisher of every row instead (pinn_lbfgs_replicas_*; `etas` must be
+    None): `sol = solve_replicas(prob, Adam(eta), u0s); fin = solve_replicas(prob, LBFGS(), sol.u, maxiters=200)`.  `fin.status` holds the
+    finisher's status per replica; `losses` is padded with the last objective where a replica stopped early."""
+    if not isinstance(alg, (Adam, LBFGS)):
+        raise ValueError("solve_replicas: the replicas are trained by Adam or finished by LBFGS")
+    if isinstance(alg, LBFGS) and etas is not None:
+        raise ValueError("solve_replicas: etas are Adam's learning rates; LBFGS takes none")
     rep = prob.pinnrep
     eng = rep.engine
     refresh = int(getattr(rep.strategy, "refresh", 0)) if getattr(rep, "_refine", None) is not None else 0
@@ -460,6 +466,11 @@ def solve_replicas(prob: OptimizationProblem, alg: Adam, u0s, maxiters: int = 10
                        (refresh > 0, "adaptive cubature with refresh re-meshes between steps")):
         if unmet:
             raise ValueError(f"solve_replicas: {why}; the replicas train inside one launch against one fixed objective")
+    if isinstance(alg, LBFGS):
+        eng.lbfgs_replicas_init(np.atleast_2d(np.asarray(u0s, dtype=np.float64)), rep._weights_now(), history=alg.m)
+        losses, _, _, status = eng.lbfgs_replicas_steps(int(maxiters), gtol=alg.gtol)
+        u, objective, _ = eng.lbfgs_replicas_get()
+        return ReplicaSolution(u.astype(prob.u0.dtype), losses, objective, int(np.argmin(objective)), status)
     th = np.ascontiguousarray(np.atleast_2d(np.asarray(u0s, dtype=np.float32)))
     lr = np.full(th.shape[0], alg.eta, dtype=np.float32) if etas is None else np.asarray(etas, dtype=np.float32).reshape(-1)
     if lr.size != th.shape[0]:
